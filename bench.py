@@ -108,10 +108,50 @@ def parse():
                     help="layout of the inverse canonical gradient handed to cage_deform: 'per-gaussian' = (P,3,3), the form the reference "
                          "stores (lib/cage.py:329) and therefore the drop-in path (default since round 5, ADVICE r4); 'per-tet' = one matrix per "
                          "tetrahedron read through tetra_id (an extension: -3 us per frame at C3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the loss and what a caller "
+                         "of the step receives: the parameter gradients; --train-step: the updated parameters) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all: above that, the per-Gaussian arrays keep the rows of a fixed seeded sample "
+                         "(their indices in gaussian_rows.npy).  Not with --field-mlp")
     ap.add_argument("--pmc", action="store_true",
                     help="collect the HBM / SQ counters of the compositing kernels with rocprofv3 (separate --pmc passes of this "
                          "same command, MI355X_MICROARCH.md) into profiles/pmc_<workload>.json, then run normally")
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000       # --dump-outputs: everything written, .npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, n_gaussians):
+    """--dump-outputs: arrays (name -> device tensor, in a fixed order) as out_dir/<name>.npy in float32 (float64 stays float64).
+    When the whole set exceeds DUMP_BYTES_MAX, every array with one row per Gaussian keeps the same rows, a sorted sample drawn
+    with a fixed seed and saved as gaussian_rows.npy (float64): with the same arguments two runs write files of the same shapes."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+    header = 128                                                   # bytes of an .npy header for these shapes
+    per_gaussian = [k for k, t in host.items() if t.dim() > 0 and t.shape[0] == n_gaussians]
+    total = sum(t.numel() * t.element_size() + header for t in host.values())
+    if total > DUMP_BYTES_MAX and per_gaussian:
+        fixed = sum(t.numel() * t.element_size() + header for k, t in host.items() if k not in per_gaussian) + header
+        row = 8 + sum(host[k][0].numel() * host[k].element_size() for k in per_gaussian)
+        n = min(n_gaussians, (DUMP_BYTES_MAX - fixed - header * len(per_gaussian)) // row)
+        assert n > 0, "--dump-outputs: the arrays without a Gaussian axis alone exceed the budget"
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_gaussians, size=n, replace=False))
+        idx = torch.from_numpy(rows).to(next(iter(host.values())).device)
+        for k in per_gaussian:
+            host[k] = host[k].index_select(0, idx)
+        host["gaussian_rows"] = torch.from_numpy(rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, t in host.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, t.cpu().contiguous().numpy())
+        written += os.path.getsize(path)
+    assert written <= DUMP_BYTES_MAX, written
+    print(f"[bench] --dump-outputs: {len(host)} arrays, {written / 1e6:.1f} MB in {out_dir}", file=sys.stderr, flush=True)
 
 
 class Frame:
@@ -889,6 +929,16 @@ def color_train_bench(args):
         losses.append(timed_step().detach().clone())
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss and the parameters its optimiser step left behind
+        names = {id(q): "param_" + k for k, q in p.items()}
+        names.update({id(frame.color_feat): "color_feat", id(frame.frame_enc): "frame_enc"})
+        for net, module in (("color_field", frame.color_field), ("canonical_field", frame.canon_field),
+                            ("deformation_field", frame.deform_field)):
+            names.update({id(q): f"{net}.{n}" for n, q in module.named_parameters()})
+        outs = {"loss": losses[-1]}
+        outs.update({names[id(q)]: q for q in leaves})
+        dump_outputs(args.dump_outputs, outs, frame.barys0.shape[0])
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     ones = torch.ones(1, device=dev)
     if world > 1:
@@ -1113,6 +1163,8 @@ def _self_launch(n):
 def main():
     args = parse()
     if args.field_mlp:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: not available with --field-mlp")
         return field_mlp_bench(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.force_cut:
         sys.exit(_self_launch(args.gpus))
@@ -1179,7 +1231,7 @@ def main():
                 keep, frame.grad_sync = frame.grad_sync, eager_sync
                 eager_sync.deferred = True
                 try:
-                    CapturedCutStep._eager(_CutShim(eager_sync), frame.upstream, frame.loss_from)
+                    return CapturedCutStep._eager(_CutShim(eager_sync), frame.upstream, frame.loss_from)
                 finally:
                     eager_sync.deferred = False
                     frame.grad_sync = keep
@@ -1275,21 +1327,21 @@ def main():
             exchange_note = (exchange_note or "") + f" graph capture of the N>1 step failed ({type(e).__name__}); eager"
             graph = None
 
+    last_loss = [None]          # the loss of the latest timed_step (--dump-outputs)
+
     def timed_step():
         i = step_no[0]; step_no[0] += 1
         if graph is not None:
             if cycle:
                 b, t = views[i % len(views)]
-                graph.replay(camera=b, target=t)      # gradients land in the graph's static .grad tensors
+                last_loss[0] = graph.replay(camera=b, target=t)      # gradients land in the graph's static .grad tensors
             else:
-                graph.replay()
+                last_loss[0] = graph.replay()
         else:
             set_view(i)
             flat.zero()
-            if cut_eager[0] is not None:
-                cut_eager[0]()
-            else:
-                frame.step()
+            loss = cut_eager[0]() if cut_eager[0] is not None else frame.step()
+            last_loss[0] = None if loss is None else loss.detach()      # (not the autograd graph of a finished step)
         reduce_params()
         if watchdog is not None:
             watchdog.arm(("step", i))
@@ -1430,6 +1482,11 @@ def main():
     dt = time.perf_counter() - t0
     cnt_end = R.last_counters()
     assert not cnt_end["overflow"], f"binning capacity overflowed inside the timed region: result invalid ({cnt} -> {cnt_end})"
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything below runs the step again: its loss and the parameter gradients
+        outs = {"loss": last_loss[0]} if last_loss[0] is not None else {}
+        outs.update({"grad_" + k: p.grad for k, p in frame.params.items() if p.grad is not None})
+        dump_outputs(args.dump_outputs, outs, frame.barys0.shape[0])
 
     # Per-stage kernel times: HIP events on the launch stream around every rasterizer stage, over the same K steps.
     # Events cannot be recorded inside a graph replay, so with --graph this is a second, eager pass over the same

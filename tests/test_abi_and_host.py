@@ -428,3 +428,33 @@ def test_field_column_layout_is_resolved_into_merged_ranges():
     assert seen[-1] == ((P, 12), None, (((0, 12),), ()))
     with pytest.raises(ValueError):
         f.forward(torch.zeros(P, 4), torch.zeros(7))
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files (float64 stays float64), at most DUMP_BYTES_MAX bytes in all.  Above the budget every
+    per-Gaussian array keeps the same seeded, sorted sample of rows (gaussian_rows.npy), identical from run to run; arrays without
+    a Gaussian axis stay whole.  Below it nothing is sampled."""
+    import bench
+    P, budget = 5000, 200_000
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", budget)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor(0.25), "grad_nodes": torch.randn(300, 3, generator=g),
+              "grad_features": torch.randn(P, 16, 3, generator=g), "grad_opacity": torch.randn(P, 1, generator=g, dtype=torch.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, P)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["gaussian_rows.npy", "grad_features.npy", "grad_nodes.npy", "grad_opacity.npy", "loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    load = lambda f: np.load(tmp_path / "a" / f)
+    rows = load("gaussian_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < P and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(load("grad_features.npy"), arrays["grad_features"].numpy()[rows.astype(np.int64)])
+    np.testing.assert_array_equal(load("grad_opacity.npy"), arrays["grad_opacity"].numpy()[rows.astype(np.int64)])
+    np.testing.assert_array_equal(load("grad_nodes.npy"), arrays["grad_nodes"].numpy())
+    assert load("grad_opacity.npy").dtype == np.float64 and load("loss.npy").shape == () and float(load("loss.npy")) == 0.25
+    small = {"loss": torch.tensor(0.5), "grad_features": torch.randn(10, 16, 3, generator=g)}
+    bench.dump_outputs(str(tmp_path / "small"), small, 10)
+    assert sorted(os.listdir(tmp_path / "small")) == ["grad_features.npy", "loss.npy"]

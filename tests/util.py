@@ -6,6 +6,11 @@ from d3ga_amd import synthetic as syn
 from oracle import camera as oc
 from oracle import deform as od
 
+# A shared GPU machine admits at most this many processes with the GPU open at once, the test process included.  On ROCm every
+# process that runs autograd opens the GPU, even on CPU tensors (the engine asks the HIP runtime for its device count), so
+# tests that start ranks of their own size them to stay below this limit.
+MAX_GPU_PROCESSES = 6
+
 
 def rel_err(a, b):
     """max |a-b| / max |b|  (the gradient-parity metric: <= 1e-3 per BASELINE.md)."""
