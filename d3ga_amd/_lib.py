@@ -11,7 +11,7 @@ ACC_STRIDE = 16          # D3GA_ACC_STRIDE (include/d3ga.h): floats per Gaussian
 # touching their `_version`, so host-side caches keyed by (data_ptr, _version) -- the packed weight panels of mlp.py --
 # carry this epoch in their key as well (eager forward -> replays with in-graph Adam -> eager forward used stale panels).
 replay_epoch = [0]
-ABI_VERSION = 110       # D3GA_VERSION (include/d3ga.h)
+ABI_VERSION = 111       # D3GA_VERSION (include/d3ga.h)
 # D3GA_KNOB_* (include/d3ga.h), in key order
 KNOBS = ("composite_variant", "merge_slots", "tile_assign", "bwd_split", "sort_merge", "ssim_impl", "wgrad_ws", "chain_abl", "chain_grid")
 LOSS_PARTIALS = 2048     # D3GA_LOSS_PARTIALS (include/d3ga.h): floats of scratch behind a two-stage loss reduction
@@ -33,7 +33,7 @@ class RasterParams(ctypes.Structure):
                 ("antialiasing", ctypes.c_int32), ("prefiltered", ctypes.c_int32), ("debug", ctypes.c_int32),
                 ("opacity_activation", ctypes.c_int32), ("forward_only", ctypes.c_int32),
                 ("acc_self_clearing", ctypes.c_int32), ("n_views", ctypes.c_int32), ("per_view_geometry", ctypes.c_int32),
-                ("factor_rows", ctypes.c_int32)]
+                ("factor_rows", ctypes.c_int32), ("per_view_appearance", ctypes.c_int32), ("per_view_background", ctypes.c_int32)]
 
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float

@@ -51,7 +51,8 @@ __device__ unsigned long long g_diag_fwd_waves[32768 * 4];    // per active wave
 // DEPTH: the inverse-depth image of branch dr_aa is accumulated and written (the D3GA renderer uses the colour only:
 // renderer.py:141 takes [0]; without it the blend loop is one FMA per entry shorter and 4 B per pixel are not written)
 // L1V: the L1 loss value against a target image is formed here as well (d3ga_raster_composite_fwd_l1; never with DUAL)
-template <bool DUAL, bool DEPTH, bool L1V>
+// PVB: bg is (k,3), one background per view (d3ga.h: per_view_background); the quadrant's view picks its row once per wavefront
+template <bool DUAL, bool DEPTH, bool L1V, bool PVB = false>
 __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) void composite_fwd_q_kernel(
     int W, int H, int gx, int gy, int gyv /* tile rows per view (= gy for one view) */, const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
     uint64_t dcap, const float2 *xy /* = xyh viewed as float2: the centre is record[0..1], stride 2 (round 4: no separate xy array) */, const float4 *__restrict__ conic_o,
@@ -62,6 +63,7 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     uint32_t *__restrict__ blk_count, bool exact_cull, L1Value l1v, int P /* Gaussians per view: colors2 is indexed by Gaussian, the lists by (view, Gaussian) */) {
     const Quad q = tile_order ? quad_of_block_ordered(gx, gx * gy, gyv, tile_order) : quad_of_block(gx, gy, gyv);
     if (!q.valid) return;                                 // wave-uniform
+    const float *const bgv = PVB ? bg + 3 * q.view : bg;  // (wave-uniform; the single-background instantiations read bg itself)
     if (q.qx0 >= W || q.qy0 >= H) {                       // a quadrant without pixels: its L1 partial is zero
         if (L1V && threadIdx.x == 0) l1v.partials[4 * (size_t)q.tile + q.quad] = 0.f;
         return;
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     if constexpr (L1V) {
         // fused L1 value (d3ga_raster_composite_fwd_l1): every quadrant leaves sum |colour - target| / n of its pixels; the
         // launcher's second kernel adds the partials in index order (reproducible), no pass over the finished image
-        float d = inside ? fabsf(C0 + T * bg[0] - tg0) + fabsf(C1 + T * bg[1] - tg1) + fabsf(C2 + T * bg[2] - tg2) : 0.f;
+        float d = inside ? fabsf(C0 + T * bgv[0] - tg0) + fabsf(C1 + T * bgv[1] - tg1) + fabsf(C2 + T * bgv[2] - tg2) : 0.f;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) d += __shfl_xor(d, off);
         if (lane == 0) l1v.partials[4 * (size_t)q.tile + q.quad] = d * l1v.inv_n;
@@ -327,9 +329,9 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
         const size_t pid1 = hw * q.view + (size_t)rg.py * W + rg.px, pid = pid1 + 2 * hw * q.view;      // one-plane / three-plane images of the view
         final_T[pid1] = T;
         n_contrib[pid1] = last;
-        out_color[pid] = C0 + T * bg[0];
-        out_color[hw + pid] = C1 + T * bg[1];
-        out_color[2 * hw + pid] = C2 + T * bg[2];
+        out_color[pid] = C0 + T * bgv[0];
+        out_color[hw + pid] = C1 + T * bgv[1];
+        out_color[2 * hw + pid] = C2 + T * bgv[2];
         if constexpr (DEPTH) out_invdepth[pid1] = Dp;
         if constexpr (DUAL) {
             out_color2[pid] = E0 + T * bg2[0];
@@ -422,15 +424,19 @@ static int composite_fwd_impl(const d3ga_raster_params *prm, const float *bg, co
     const bool ordered = (composite_variant() & kVariantOrdered) != 0, exact = (composite_variant() & kVariantExactCull) != 0;
     const dim3 grid(ordered ? quad_grid_ordered(gx * gy) : quad_grid(gx, gy));
     const uint32_t *order = ordered ? (const uint32_t *)bin.tile_order : (const uint32_t *)nullptr;
-#define D3GA_LAUNCH_FWD(DUALV, DEPTHV, L1VV)                                                                                    \
-    hipLaunchKernelGGL((composite_fwd_q_kernel<DUALV, DEPTHV, L1VV>), grid, dim3(64), 0, s, prm->W, prm->H, gx, gy, gyv, bin.tile_start, \
+    const bool pvb = views > 1 && prm->per_view_background;      // bg (k,3)
+#define D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, PVBV)                                                                            \
+    hipLaunchKernelGGL((composite_fwd_q_kernel<DUALV, DEPTHV, L1VV, PVBV>), grid, dim3(64), 0, s, prm->W, prm->H, gx, gy, gyv, bin.tile_start, \
                        bin.point_list, (uint64_t)d_capacity, reinterpret_cast<const float2 *>(g.xyh), g.conic_o, g.rgb_invd, g.xyh, bg, im.final_T, im.n_contrib,     \
                        out_color, out_invdepth, order, colors2, bg2, out_color2, im.blk_list, im.blk_count, exact, l1v, prm->P)
+#define D3GA_LAUNCH_FWD(DUALV, DEPTHV, L1VV)                                                                                    \
+    do { if (pvb) D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, true); else D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, false); } while (0)
     if (colors2 && l1v.partials) return D3GA_E_CONFIG;
     if (colors2) { if (out_invdepth) D3GA_LAUNCH_FWD(true, true, false); else D3GA_LAUNCH_FWD(true, false, false); }
     else if (l1v.partials) { if (out_invdepth) D3GA_LAUNCH_FWD(false, true, true); else D3GA_LAUNCH_FWD(false, false, true); }
     else { if (out_invdepth) D3GA_LAUNCH_FWD(false, true, false); else D3GA_LAUNCH_FWD(false, false, false); }
 #undef D3GA_LAUNCH_FWD
+#undef D3GA_LAUNCH_FWD_B
     return check_launch(s, prm->debug);
 }
 

@@ -399,7 +399,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
 // wavefronts per tile.  2 / 4: 8 / 16 wavefronts per tile, a block's list runs over 2 / 4 rows (32 / 64 entries per group), a
 // wavefront takes 2 / 1 blocks -- the same pixel steps in total, but the tile's longest list is walked in half / a quarter of
 // the groups: the critical path of a heavy tile (18 groups of one wavefront at C3) shrinks with it.
-template <bool DUAL, int S, bool INVD = false, int R = 1>
+template <bool DUAL, int S, bool INVD = false, int R = 1, bool PVB = false>      // PVB: bg is (k,3), one row per view (d3ga.h: per_view_background)
 __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_WAVES : 3) : D3GA_TILE_WAVES)) void composite_bwd_tile_kernel(   // (DUAL: 12-float pixel records -- the LDS of three workgroups per CU)
    
     int W, int H, int gx, int gy, int gyv, const uint32_t *__restrict__ tile_start, uint64_t dcap, const float2 *__restrict__ xy,
@@ -489,7 +489,8 @@ __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_W
             const int by = assign ? 2 * (row >> 1) + (wave >> 1) : 2 * (wave >> 1) + (row >> 1);
             blk = 4 * ((bx >> 1) + 2 * (by >> 1)) + ((bx & 1) + 2 * (by & 1));
         }
-        const BwdArgs A = {W, H, gx, gyv, P, xy, conic_o, rgb_invd, bg, final_T, n_contrib, dL_dpix, acc, colors2, bg2, dL_dpix2, blk_list, blk_count, l1, dL_dinvd};
+        const float *const bgv = PVB ? bg + 3 * ((tile / gx) / gyv) : bg;      // the tile's view: uniform over the workgroup
+        const BwdArgs A = {W, H, gx, gyv, P, xy, conic_o, rgb_invd, bgv, final_T, n_contrib, dL_dpix, acc, colors2, bg2, dL_dpix2, blk_list, blk_count, l1, dL_dinvd};
         if (R == 1 && half >= 0) {
             blk = s_perm[2 * (2 * ((wave + (int)blockIdx.x) & 3) + (lane >> 5)) + half];
             bwd_tile_wave<DUAL, S, INVD, (R == 1 ? 2 : R)>(A, tile, begin, end, blk, s_cache, s_pix, s_dump, lane, dg);
@@ -566,13 +567,14 @@ int launch_composite_bwd_scan(const d3ga_raster_params *prm, int gx, int gy, con
     const uint32_t *split_cnt = (ordered && split_knob < 0) ? (const uint32_t *)(bin.counters + D3GA_CNT_HEAVY) : (const uint32_t *)nullptr;
     const dim3 tgrid(gx * gy + split_cap);
     const int S = composite_merge_slots();
-#define D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, RV)                                                                              \
-    hipLaunchKernelGGL((composite_bwd_tile_kernel<DUALV, SV, INVDV, RV>), tgrid, dim3(256 * RV),                                \
+    const bool pvb = n_views_of(prm) > 1 && prm->per_view_background;      // bg (k,3)
+#define D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, RV, PVBV)                                                                        \
+    hipLaunchKernelGGL((composite_bwd_tile_kernel<DUALV, SV, INVDV, RV, PVBV>), tgrid, dim3(256 * RV),                          \
                        0, s, prm->W, prm->H, gx, gy, gy / n_views_of(prm), bin.tile_start, \
                        (uint64_t)d_capacity, reinterpret_cast<const float2 *>(g.xyh), g.conic_o, g.rgb_invd, bg, im.final_T, im.n_contrib, dL_dpix, acc, order,   \
                        colors2, bg2, dL_dpix2, (const uint2 *)im.blk_list, (const uint32_t *)im.blk_count, composite_tile_assign(), l1, dL_dinvd, split_cap, split_cnt, prm->P)
 #define D3GA_LAUNCH_TILE(DUALV, SV, INVDV)                                                                                    \
-    D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1)
+    do { if (pvb) D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, true); else D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, false); } while (0)
     if (dL_dinvd) {                                          // inverse-depth gradient (branch dr_aa): single-image launches only
         if (colors2) return D3GA_E_CONFIG;
         if (S >= 512) D3GA_LAUNCH_TILE(false, 512, true); else D3GA_LAUNCH_TILE(false, 256, true);

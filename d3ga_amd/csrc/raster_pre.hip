@@ -554,7 +554,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
 // project_bwd, the direction term from the forward's Jacobian), views added in ascending order like the per-view launches add them.
 // SH colours need the forward's dcol planes (staged coefficients, forward_only == 0): the launcher falls back to per-view launches
 // otherwise, and for the factored SH output of the camera-sharded exchange.  accum: a later group of a batch of more than kMaxGroup
-// views -- every output is added to.
+// views -- every output is added to, except the per-view ones.  pva (d3ga.h: per_view_appearance, precomputed colours): dL/dopacity
+// and dL/dcolour are written per view at record v P + i of the group (a view that culled the Gaussian writes zeros), not summed.
 constexpr int kMaxGroup = 8;
 struct ViewCamsN { const float *vm[kMaxGroup], *pm[kMaxGroup], *cp[kMaxGroup]; };
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
@@ -563,7 +564,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
     const float *__restrict__ acc /* first view of the group */, float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D /* first view | null */,
     float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors, float *__restrict__ dL_dcov3D,
     float *__restrict__ dL_dscales, float *__restrict__ dL_drots, bool accum,
-    size_t pv /* records between the views' geometry AND geometry gradients: 0 = shared (summed), P = a batch of frames (written per view) */) {
+    size_t pv /* records between the views' geometry AND geometry gradients: 0 = shared (summed), P = a batch of frames (written per view) */,
+    bool pva /* per-view appearance: dL_dopacity / dL_dcolors are (kv,P) / (kv,P,3) of the group's first view */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_sh = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -622,6 +624,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
             }
             if (!visible) {
                 if (pv) geometry_out(pv * v, zero3, zero6, false, false);      // a batch of frames: every view's geometry gradients are written
+                if (pva) {                                                     // ... and per-view appearance every view's opacity / colour gradients
+                    if (dL_dopacity) dL_dopacity[j] = 0.f;
+                    if (dL_dcolors) { dL_dcolors[3 * j] = 0.f; dL_dcolors[3 * j + 1] = 0.f; dL_dcolors[3 * j + 2] = 0.f; }
+                }
                 continue;
             }
             if (pv) {                                                        // this view's own geometry
@@ -656,12 +662,16 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
 #pragma unroll
                 for (int k = 0; k < 16; ++k)
                     if (k < nb) { out[3 * k] += B[k] * gr[0]; out[3 * k + 1] += B[k] * gr[1]; out[3 * k + 2] += B[k] * gr[2]; }
+            } else if (pva) {
+                if (dL_dcolors) { dL_dcolors[3 * j] = a[7]; dL_dcolors[3 * j + 1] = a[8]; dL_dcolors[3 * j + 2] = a[9]; }
             } else {
                 gcol[0] += a[7]; gcol[1] += a[8]; gcol[2] += a[9];
             }
             {
                 const float op = act_opacity / aa, g_op = a[6] * aa;
-                gop += prm.opacity_activation == D3GA_OPACITY_SIGMOID ? g_op * op * (1.0f - op) : g_op;
+                const float g = prm.opacity_activation == D3GA_OPACITY_SIGMOID ? g_op * op * (1.0f - op) : g_op;
+                if (!pva) gop += g;
+                else if (dL_dopacity) dL_dopacity[j] = g;
             }
             if (pv) geometry_out(pv * v, gm_v, g6_v, true, false);
             else {
@@ -671,8 +681,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
             }
         }
         if (!pv) geometry_out(0, gmean, g6, true, accum);
-        if (dL_dopacity) put(dL_dopacity + i, gop, accum);
-        if (!sh_path && dL_dcolors) { put(dL_dcolors + 3 * (size_t)i, gcol[0], accum); put(dL_dcolors + 3 * (size_t)i + 1, gcol[1], accum); put(dL_dcolors + 3 * (size_t)i + 2, gcol[2], accum); }
+        if (dL_dopacity && !pva) put(dL_dopacity + i, gop, accum);
+        if (!sh_path && !pva && dL_dcolors) { put(dL_dcolors + 3 * (size_t)i, gcol[0], accum); put(dL_dcolors + 3 * (size_t)i + 1, gcol[1], accum); put(dL_dcolors + 3 * (size_t)i + 2, gcol[2], accum); }
         if (sh_path && dL_dsh) {
             float *row = slab + lane * kShRow;
 #pragma unroll
@@ -788,6 +798,8 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     D3GA_HIP(zero_async(bin.counters, 256 + align256(4 * tiles), s));
     if (prm->P == 0) return D3GA_OK;          // empty scene: every per-Gaussian tensor is empty (NULL)
     if ((shs != nullptr) == (colors_precomp != nullptr)) return D3GA_E_CONFIG;
+    const bool pva = views > 1 && prm->per_view_appearance;   // (k,P) opacities and (k,P,3) colours: precomputed colours only (d3ga.h)
+    if (pva && shs) return D3GA_E_CONFIG;
     const bool sr = scales != nullptr && rotations != nullptr;
     if (sr == (cov3D_precomp != nullptr)) return D3GA_E_CONFIG;
     if (shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M) return D3GA_E_CONFIG;
@@ -801,11 +813,13 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     // a batch of views writes view v's records at v P + i of the batch's buffers: grouped launches below when the SH row can be
     // shared, else one launch per view (a streaming kernel at the copy rate gains nothing from a taller grid)
     const size_t pv = (views > 1 && prm->per_view_geometry) ? (size_t)prm->P : 0;      // records between the views' geometry (0: shared)
+    const size_t pa = pva ? (size_t)prm->P : 0;                                        // ... and between their opacities / colours
     const dim3 grid((prm->P + kBlock - 1) / kBlock), block(kBlock);
     int v0 = 0;
     // k cameras of ONE set of Gaussians with staged SH colours: groups of up to four views per pass (preprocess_views_kernel: the
-    // 12 M-byte coefficient row, the mean and the covariance are read once per group instead of once per view)
-    const bool grouped = views > 1 && shs && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
+    // 12 M-byte coefficient row, the mean and the covariance are read once per group instead of once per view).  SH only, so never
+    // with per-view appearance (refused above): the group kernel reads one opacity per Gaussian for all its views
+    const bool grouped = views > 1 && shs && !pva && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
 #define D3GA_PRE_VIEWS(KVV)                                                                                                        \
     do {                                                                                                                           \
         ViewCams<KVV> vc;                                                                                                          \
@@ -833,13 +847,14 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
         const float *vm = viewmatrix + 16 * (size_t)v, *pm = projmatrix + 16 * (size_t)v, *cp = campos + (size_t)cam_stride * v;
         const float *mv = means3D + 3 * pv * v, *sv = scales ? scales + 3 * pv * v : nullptr, *rq = rotations ? rotations + 4 * pv * v : nullptr;
         const float *cv = cov3D_precomp ? cov3D_precomp + 6 * pv * v : nullptr;
+        const float *ov = opacities + pa * v, *colv = colors_precomp ? colors_precomp + 3 * pa * v : nullptr;      // (per-view appearance)
         int32_t *rv = radii + (size_t)prm->P * v;
         if (want_j)
             hipLaunchKernelGGL(preprocess_kernel<true>, grid, block, lds, s, *prm, mv, shs,
-                               colors_precomp, opacities, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
+                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
         else
             hipLaunchKernelGGL(preprocess_kernel<false>, grid, block, lds, s, *prm, mv, shs,
-                               colors_precomp, opacities, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
+                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
     }
     return check_launch(s, prm->debug & 0xff);
 }
@@ -885,6 +900,8 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
     if (!cov3D_precomp && !(scales && rotations)) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
     const int views = n_views_of(prm);
+    const bool pva = views > 1 && prm->per_view_appearance;      // per-view opacity / colour gradients: precomputed colours only (d3ga.h)
+    if (pva && shs) return D3GA_E_CONFIG;
     const GeomBuf g = carve_geom(const_cast<void *>(geom), (int64_t)prm->P * views);
     const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? kShLdsBytes : 0;
     if (views == 1) {
@@ -909,18 +926,19 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
                     const int v = v0 + (q < kv ? q : 0);
                     vc.vm[q] = viewmatrix + 16 * (size_t)v; vc.pm[q] = projmatrix + 16 * (size_t)v; vc.cp[q] = campos + (size_t)cam_stride * v;
                 }
-                const size_t o = (size_t)prm->P * v0, og = pvl * v0;
+                const size_t o = (size_t)prm->P * v0, og = pvl * v0, oa = pva ? o : 0;      // oa: the group's first per-view opacity / colour gradient
                 hipLaunchKernelGGL(preprocess_bwd_views_kernel, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), shs ? kShLdsBytes : 0, s, *prm, kv,
                                    means3D + 3 * og, shs != nullptr, scales ? scales + 3 * og : nullptr, rotations ? rotations + 4 * og : nullptr,
                                    cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, vc, geom_view(g, prm->P, v0), acc + D3GA_ACC_STRIDE * o,
-                                   dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity, dL_dsh, dL_dcolors,
-                                   dL_dcov3D ? dL_dcov3D + 6 * og : nullptr, dL_dscales ? dL_dscales + 3 * og : nullptr,
-                                   dL_drots ? dL_drots + 4 * og : nullptr, v0 > 0, pvl);
+                                   dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity ? dL_dopacity + oa : nullptr, dL_dsh,
+                                   dL_dcolors ? dL_dcolors + 3 * oa : nullptr, dL_dcov3D ? dL_dcov3D + 6 * og : nullptr,
+                                   dL_dscales ? dL_dscales + 3 * og : nullptr, dL_drots ? dL_drots + 4 * og : nullptr, v0 > 0, pvl, pva);
             }
             return check_launch(s, prm->debug);
         }
     }
     // otherwise: one launch per view on ITS records; view 0 writes the gradients of the view-independent
+    if (pva) return D3GA_E_CONFIG;                                 // (SH colours only come here: per-view appearance is refused above)
     if (shs && !dL_dcolors) return D3GA_E_NULL;
     const size_t pv = prm->per_view_geometry ? (size_t)prm->P : 0;      // a batch of frames: every view has its own geometry and geometry gradients
     if (prm->factor_rows != 0 && prm->factor_rows < prm->P) return D3GA_E_SIZE;

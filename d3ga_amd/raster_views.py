@@ -89,8 +89,14 @@ class _RasterizeViews(torch.autograd.Function):
         geo = [t for t in (means3D, scales, rotations, cov3Ds_precomp) if t is not None]
         if any((t.dim() == 3) != per_view for t in geo) or (per_view and any(t.shape[0] != k for t in geo)):
             raise ValueError("rasterize_gaussians_views: means3D and the covariance inputs must all be (P,.) or all be (k,P,.)")
-        if opacities.shape[0] != P:
-            raise ValueError("rasterize_gaussians_views: opacities (and the colours) are shared by the views: (P,.)")
+        # per-view appearance (the ColorField configuration: colour and opacity evaluated per frame / camera): opacities (k,P[,1]) and
+        # colors_precomp (k,P,3) -- the wrapper below has given both the same form; the gradients come back per view
+        pva = _appearance_per_view(opacities, colors_precomp, sh, k, P)
+        ctx.opacities_shape = tuple(opacities.shape)
+        pvb = _background_per_view(bg, k)
+        if pva and grad_sync is not None:
+            raise ValueError("rasterize_gaussians_views: grad_sync (camera-sharded exchange at the cut) needs view-independent appearance; "
+                             "per-view colours and opacities are reduced at the parameters (dist.BucketedGradReducer)")
         M = sh.shape[1] if sh is not None else 0
         fwd_only = not any(ctx.needs_input_grad[:7])
         dual = colors2 is not None
@@ -98,10 +104,12 @@ class _RasterizeViews(torch.autograd.Function):
             raise ValueError("rasterize_gaussians_views: the fused L1 loss and a second colour set cannot be combined")
         if dual:
             colors2, bg2 = f32(colors2.detach()), f32(bg2)
+            if tuple(colors2.shape) != (P, 3) or bg2.numel() != 3:
+                raise ValueError("rasterize_gaussians_views: colors2 is (P,3) and bg2 (3,), shared by the views")
         prm = RasterParams(P=P, M=M, sh_degree=int(sh_degree), W=W, H=H, tanfovx=0.0, tanfovy=0.0,
                            scale_modifier=float(scale_modifier), antialiasing=int(bool(antialiasing)), prefiltered=0, debug=0,
                            opacity_activation=_R._ACTIVATIONS[opacity_activation], forward_only=int(fwd_only), n_views=k,
-                           per_view_geometry=int(per_view))
+                           per_view_geometry=int(per_view), per_view_appearance=int(pva), per_view_background=int(pvb))
         colors2_img = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev) if dual else None
         colors = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((k, P), dtype=torch.int32, device=dev)
@@ -152,7 +160,7 @@ class _RasterizeViews(torch.autograd.Function):
             cap = k * _R._hwm[dev.index]
         ctx.prm, ctx.cap, ctx.cams = prm, cap, cams
         ctx.l1 = tgt is not None and P > 0
-        ctx.dual, ctx.per_view = dual, per_view
+        ctx.dual, ctx.per_view, ctx.pva = dual, per_view, pva
         # camera-sharded training (d3ga_amd/dist.py: ViewShardedGrads): every gradient that leaves this op is summed over the ranks
         # at this cut -- this rank's k views arrive already summed, their k SH factors travel in one all-gather
         ctx.grad_sync = grad_sync if (grad_sync is not None and (grad_sync.world > 1 or getattr(grad_sync, "always", False)) and P > 0) else None
@@ -193,9 +201,10 @@ class _RasterizeViews(torch.autograd.Function):
         sync, flat, factor = ctx.grad_sync, None, None
         if sync is None:
             gshape = (k, P) if ctx.per_view else (P,)                 # a batch of frames: geometry gradients per view
-            g_means3D, g_opac = new(*gshape, 3), new(P, 1)
+            g_means3D = new(*gshape, 3)
+            g_opac = new(*ctx.opacities_shape) if ctx.pva else new(P, 1)        # per-view appearance: (k,P[,1]) and (k,P,3), per view
             g_sh = new(P, prm.M, 3) if sh is not None else None
-            g_col = new(k, P, 3) if sh is not None else new(P, 3)      # SH: the per-view factors of the rank-1 SH gradient (scratch)
+            g_col = new(k, P, 3) if (sh is not None or ctx.pva) else new(P, 3)  # SH: the per-view factors of the rank-1 SH gradient (scratch)
             g_cov = None if from_sr else new(*gshape, 6)
             g_scales = new(*gshape, 3) if from_sr else None
             g_rots = new(*gshape, 4) if from_sr else None
@@ -266,17 +275,61 @@ class _RasterizeViews(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None, None)
 
 
+def _appearance_per_view(opacities, colors_precomp, sh, k, P):
+    """True for per-view opacities (k,P) | (k,P,1) with colours (k,P,3); False for the shared (P,) | (P,1) and (P,3).  Anything else
+    -- a leading dimension that is not k, SH colours with per-view opacities, one of the two per view and the other not -- raises."""
+    def form(t, width, what):
+        if t is None:
+            return None
+        shared = ((P,), (P, 1)) if width == 1 else ((P, width),)
+        per_view = ((k, P), (k, P, 1)) if width == 1 else ((k, P, width),)
+        shape = tuple(t.shape)
+        if shape in shared:
+            return False
+        if shape in per_view:
+            return True
+        raise ValueError(f"rasterize_gaussians_views: {what} must be {' or '.join(map(str, shared))} (shared by the {k} views) or "
+                         f"{' or '.join(map(str, per_view))} (one per view), got {shape}")
+    op, col = form(opacities, 1, "opacities"), form(colors_precomp, 3, "colors_precomp")
+    if op and sh is not None:
+        raise ValueError("rasterize_gaussians_views: per-view opacities need precomputed colours (k,P,3); SH colours are view-dependent "
+                         "already and their coefficients are shared")
+    if col is not None and op != col:
+        raise ValueError("rasterize_gaussians_views: opacities and colors_precomp must both be shared (P,.) or both per view (k,P,.)")
+    return bool(op)
+
+
+def _background_per_view(bg, k):
+    if tuple(bg.shape) in ((3,), (1, 3)):
+        return False
+    if tuple(bg.shape) == (k, 3):
+        return True
+    raise ValueError(f"rasterize_gaussians_views: bg must be (3,) (shared by the {k} views) or ({k}, 3) (one per view), got {tuple(bg.shape)}")
+
+
 def rasterize_gaussians_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cameras, bg, sh_degree=0,
                               scale_modifier=1.0, antialiasing=False, opacity_activation=None, l1_targets=None, colors2=None, bg2=None,
                               grad_sync=None):
-    """k views in one grid per stage.  cameras: a CameraBatch; bg (3,) shared by the views.
+    """k views in one grid per stage.  cameras: a CameraBatch; bg (3,) shared by the views or (k,3), one per view (the reference
+    draws a background per frame, models/trainer.py:95-100).
     Geometry: means3D (P,3) with cov3Ds_precomp (P,6) | scales + rotations -- k CAMERAS of one set of Gaussians -- or all of them
-    (k,P,.) -- k FRAMES, the avatar deformed per pose (the reference's batch, train.py:218-221); opacities and the colours are shared.
+    (k,P,.) -- k FRAMES, the avatar deformed per pose (the reference's batch, train.py:218-221).  Appearance: opacities (P,[1]) and
+    sh | colors_precomp (P,3) shared by the views, or -- the ColorField configuration, colour and opacity evaluated per frame
+    (models/cage_net.py:232-258) -- opacities (k,P[,1]) with colors_precomp (k,P,3), one per view; a shared one of the two beside a
+    per-view one is broadcast to (k,P,.) here.
     -> (colors (k,3,H,W), radii (k,P)); with l1_targets (k,3,H,W): (colors, radii, loss), loss = mean |colors - targets| over all k
     images (= the mean over the frames of the reference's per-frame l1_loss: equal sizes), its gradient formed inside the compositing
     backward; with colors2 (P,3) + bg2: (colors, radii, colors2_image (k,3,H,W)) -- the reference's RGB + silhouette pair
     (models/trainer.py:102-110) from one pass, colors2 constant.  Gradients as `rasterize_gaussians`: summed over the views for
     shared inputs, per view for (k,P,.) geometry.  grad_sync: a dist.ViewShardedGrads -- the returned gradients are then already
-    averaged over the ranks of a camera-sharded run (every rank renders its own k cameras of the pose)."""
+    averaged over the ranks of a camera-sharded run (every rank renders its own k cameras of the pose); not with per-view appearance."""
+    k = cameras.n_views
+    if k > 1 and opacities is not None and colors_precomp is not None:
+        P = means3D.shape[-2]
+        op_pv = opacities.dim() == 3 or (opacities.dim() == 2 and tuple(opacities.shape) != (P, 1))
+        if op_pv and colors_precomp.dim() == 2:
+            colors_precomp = colors_precomp.unsqueeze(0).expand(k, *colors_precomp.shape)      # (autograd sums the views back)
+        elif colors_precomp.dim() == 3 and not op_pv:
+            opacities = opacities.reshape(1, P, 1).expand(k, P, 1)
     return _RasterizeViews.apply(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cameras, bg,
                                  sh_degree, scale_modifier, antialiasing, opacity_activation, l1_targets, colors2, bg2, grad_sync)

@@ -60,24 +60,36 @@ def render_l1(batch, pkg, bg_color, target, grad_sync=None):
 def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=None, bg_color2=None, grad_sync=None):
     """k views in one pass (extension; the reference renders one camera per call and averages the losses of a batch of frames,
     train.py:218-221): -> {"render": (k,3,H,W)}; with targets (k,3,H,W) also "l1" = the mean over the views of `l1_loss(render,
-    target)` (its gradient formed inside the compositing backward); with colors2 (P,3) + bg_color2 also "render2" (k,3,H,W), the
-    reference's silhouette pass (models/trainer.py:102-110) from the same pass.
+    target)` (its gradient formed inside the compositing backward); with colors2 (P,3) + bg_color2 (3,) also "render2" (k,3,H,W), the
+    reference's silhouette pass (models/trainer.py:102-110) from the same pass.  bg_color: (3,) shared, or (k,3) one per view (the
+    reference's random background per frame, models/trainer.py:95-100).
     pkg: one package seen from k CAMERAS -- or a LIST of k packages, one per FRAME of the batch (the avatar deformed per pose:
-    their means3D and covariances are stacked to (k,P,.)); appearance (opacities, shs | rgb) is taken from the first package and
-    must be the same tensors in all of them.  Every image equals `render(batch_v, pkg_v, bg_color)["render"]`, the gradients equal
-    the sum over the k calls (d3ga_amd/raster_views.py).  The views share the raster size and must not be cropped
-    (lib/batch.py:186-198: centred principal point).  cameras: a `raster_views.CameraBatch` to reuse (a captured step keeps one and
+    their means3D and covariances are stacked to (k,P,.)).  Appearance: `shs` and `sh_degree` must be the same in all packages;
+    `rgb` / `opacities` / `opacity_logits` that are the same tensor in every package are shared, ones that differ (the ColorField
+    configuration, use_shs false: colour and opacity evaluated per frame) are stacked to (k,P,.) and rendered per view.  One package
+    seen from k cameras may carry `rgb` (k,P,3) and `opacities` (k,P,1) itself (ColorField evaluated once per camera).  Every image
+    equals `render(batch_v, pkg_v, bg_color_v)["render"]`, the gradients equal the sum over the k calls (d3ga_amd/raster_views.py).
+    The views share the raster size and must not be cropped (lib/batch.py:186-198: centred principal point).  cameras: a `raster_views.CameraBatch` to reuse (a captured step keeps one and
     calls `cameras.set(batches)` before every replay); batches may then be None."""
     from .raster_views import CameraBatch, rasterize_gaussians_views
     frames = pkg if isinstance(pkg, (list, tuple)) else None
     if frames is not None:
         first = frames[0]
         for f in frames[1:]:
-            for key in ("opacities", "opacity_logits", "shs", "rgb"):
-                if f.get(key) is not first.get(key):
-                    raise ValueError(f"render_views: the frames of a batch share their appearance; `{key}` differs between the packages")
+            if f.get("shs") is not first.get("shs"):
+                raise ValueError("render_views: the frames of a batch share their SH coefficients; `shs` differs between the packages")
+            if f.get("sh_degree", 0) != first.get("sh_degree", 0):
+                raise ValueError(f"render_views: `sh_degree` differs between the packages ({first.get('sh_degree', 0)} and {f.get('sh_degree', 0)})")
+            for key in ("opacities", "opacity_logits", "rgb"):
+                if (f.get(key) is None) != (first.get(key) is None):
+                    raise ValueError(f"render_views: `{key}` is given in some packages of the batch and not in others")
         stack = lambda key: None if first.get(key) is None else torch.stack([f[key] for f in frames])
-        pkg = dict(first, means3D=stack("means3D"), cov3D_precomp=stack("cov3D_precomp"), scales=stack("scales"), rotations=stack("rotations"))
+        # appearance: the same tensor in every package stays (P,.) (shared by the views, gradients summed); tensors that differ --
+        # the ColorField configuration evaluates colour and opacity per frame -- are stacked to (k,P,.) (per-view appearance)
+        same = lambda key: all(f.get(key) is first.get(key) for f in frames)
+        look = {key: first.get(key) if same(key) else stack(key) for key in ("opacities", "opacity_logits", "rgb")}
+        pkg = dict(first, means3D=stack("means3D"), cov3D_precomp=stack("cov3D_precomp"), scales=stack("scales"), rotations=stack("rotations"),
+                   **look)
     means3D = pkg["means3D"]
     if cameras is None:
         for b in batches:

@@ -27,7 +27,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 110 /* round 6 (frozen for the round): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 111 /* per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -186,11 +186,11 @@ typedef struct d3ga_raster_params {
      * grid per stage -- the launches of a single avatar view fill a third of the chip, k views fill it.  Then
      *   viewmatrix / projmatrix are (k,16), campos (k,3) -- (k,5) for camera slots -- radii (k,P);
      *   geom / binning / img are sized by d3ga_raster_scratch_bytes_views and hold k x P records / k x tiles lists: view v's Gaussian
-     *   i is record v P + i, its tile (tx, ty) is tile (v gy + ty) gx + tx; W, H, tanfov*, bg are shared by the views;
+     *   i is record v P + i, its tile (tx, ty) is tile (v gy + ty) gx + tx; W, H, tanfov* are shared by the views, bg too unless per_view_background;
      *   out_color (k,3,H,W), out_invdepth (k,H,W), dL_dpix (k,3,H,W), the L1 target (k,3,H,W) and its loss = mean over all k images;
      *   d3ga_raster_composite_fwd2 / _bwd2: colors2 stays (P,3) (shared by the views), out_color2 / dL_dpix2 are (k,3,H,W);
      *   acc (k P, D3GA_ACC_STRIDE);  d3ga_raster_preprocess_bwd SUMS dL/dmeans3D, dL/dopacity, dL/dcov3D | (dL/dscales, dL/drots) and a
-     *   precomputed colour's gradient over the views, writes dL_dmeans2D per view (k,P,3), and for SH colours needs dL_dcolors
+     *   precomputed colour's gradient over the views (see per_view_geometry / per_view_appearance for the per-view forms), writes dL_dmeans2D per view (k,P,3), and for SH colours needs dL_dcolors
      *   (k,P,3) = the per-view factors of the rank-1 SH gradient, from which dL_dsh (P,M,3), when given, is rebuilt in one pass
      *   (d3ga_sh_grad_from_views) -- one 12 M-byte row per Gaussian and BATCH instead of per view.
      * Every view's image and the summed gradients equal k single-view calls (same kernels, same arithmetic per view).
@@ -199,12 +199,27 @@ typedef struct d3ga_raster_params {
     /* n_views > 1 only.  != 0: a batch of FRAMES, not only of cameras -- every view has its own geometry (the reference's batch
      * holds frames of different poses, train.py:218-221: the avatar is deformed per frame, its appearance parameters are shared):
      * means3D is (k,P,3) and cov3D_precomp (k,P,6) | scales (k,P,3) + rotations (k,P,4); their gradients are written PER VIEW,
-     * (k,P,.), not summed; opacities, shs | colors_precomp stay (P,.) with gradients summed over the views. */
+     * (k,P,.), not summed; opacities and shs | colors_precomp stay (P,.) with gradients summed over the views unless
+     * per_view_appearance is set. */
     int32_t per_view_geometry;
     /* n_views > 1, SH colours: rows between consecutive views' factors in the dL_dcolors handed to d3ga_raster_preprocess_bwd (0 = P).
      * The camera-sharded exchange keeps one extra row per view (the view's camera position) so that factors and positions travel in
      * ONE all-gather (d3ga_amd/dist.py): P + 1. */
     int32_t factor_rows;
+    /* n_views > 1 only (ABI 111).  != 0: every view has its own colour and opacity -- the reference's ColorField configuration
+     * (use_shs: false) evaluates both per frame from that camera's view direction and that frame's encodings
+     * (models/cage_net.py:232-258): opacities is (k,P) -- view v's opacity of Gaussian i is opacities[v P + i], activated values or
+     * logits under D3GA_OPACITY_SIGMOID alike -- and colors_precomp (k,P,3); d3ga_raster_preprocess_bwd writes dL_dopacity (k,P) and
+     * dL_dcolors (k,P,3) PER VIEW, not summed (zeros for a view in which the Gaussian is culled).  Precomputed colours only: with
+     * shs != NULL the preprocess entry points return D3GA_E_CONFIG (SH colours are view-dependent already).  Independent of
+     * per_view_geometry: both together are the ColorField batch of frames.  With n_views <= 1 accepted and without effect (a
+     * (1,P,.) tensor is a (P,.) one). */
+    int32_t per_view_appearance;
+    /* n_views > 1 only (ABI 111).  != 0: every view has its own background (the reference draws one per frame,
+     * models/trainer.py:95-100): `bg` is (k,3) for d3ga_raster_composite_fwd / _fwd_l1 / _fwd2 / _bwd / _bwd_l1 / _bwd2 / _bwd_depth
+     * and d3ga_raster_forward / _backward / _backward_l1.  bg2 (the silhouette background of _fwd2 / _bwd2, black in the reference)
+     * stays (3,), shared by the views.  With n_views <= 1 accepted and without effect. */
+    int32_t per_view_background;
 } d3ga_raster_params;
 #define D3GA_OPACITY_SIGMOID 1
 
@@ -256,7 +271,7 @@ int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float *means3D, 
 /* R2+R3 tile offsets (scan), scatter of (depth,index) keys, per-tile sort in LDS. */
 int d3ga_raster_bin_sort(const d3ga_raster_params *prm, void *geom, void *binning, int64_t d_capacity,
                          d3ga_stream_t stream);
-/* R4 front-to-back compositing.  bg (3) device.  out_color (3,H,W); out_invdepth (H,W)|NULL. */
+/* R4 front-to-back compositing.  bg (3) device; (k,3) for a batch of views with per_view_background.  out_color (3,H,W); out_invdepth (H,W)|NULL. */
 int d3ga_raster_composite_fwd(const d3ga_raster_params *prm, const float *bg, const void *geom, const void *binning,
                               int64_t d_capacity, void *img, float *out_color, float *out_invdepth,
                               d3ga_stream_t stream);
