@@ -14,6 +14,7 @@ replay_epoch = [0]
 ABI_VERSION = 111       # D3GA_VERSION (include/d3ga.h)
 # D3GA_KNOB_* (include/d3ga.h), in key order
 KNOBS = ("composite_variant", "merge_slots", "tile_assign", "bwd_split", "sort_merge", "ssim_impl", "wgrad_ws", "chain_abl", "chain_grid")
+CAMERA_SLOT_WINDOWED = -1.0    # D3GA_CAMERA_SLOT_WINDOWED (include/d3ga.h): tanfovx of a windowed camera slot, 9 floats per view in campos
 LOSS_PARTIALS = 2048     # D3GA_LOSS_PARTIALS (include/d3ga.h): floats of scratch behind a two-stage loss reduction
 
 
@@ -57,6 +58,8 @@ _SIGNATURES = {
     "d3ga_fem_energy_bwd": ([_i, _i] + [_vp] * 5 + [_vp], _i),
     "d3ga_raster_scratch_bytes": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_scratch_bytes_views": ([ctypes.c_int32] * 4 + [_i64, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_raster_scratch_bytes_window": ([ctypes.c_int32] * 4 + [_i64, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_raster_binning_layout_window": ([ctypes.c_int32] * 3 + [_i64, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_binning_layout": ([ctypes.c_int32, ctypes.c_int32, _i64, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_img_layout": ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_img_layout_blocks": ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _i),

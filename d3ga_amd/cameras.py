@@ -12,6 +12,41 @@ import numpy as np
 import torch
 
 ZNEAR, ZFAR = 0.01, 100.0          # lib/cameras.py:62-63
+CAMERA_SLOT_WINDOWED = -1.0        # D3GA_CAMERA_SLOT_WINDOWED (include/d3ga.h): tanfovx of a windowed camera slot
+
+
+def crop_window(batch):
+    """The window that `renderer.paste` cuts out of a render of `batch` (lib/batch.py:186-198, renderer.py:36-47):
+    -> (w, h, ox, oy, W, H) -- the full raster size, the window's offset in it and the window size.  ox = 0 if left_w > right_w
+    else w - W, oy likewise; a centred crop is (w, h, 0, 0, w, h)."""
+    crop = batch["crop"]
+    left_w, right_w, top_h, bottom_h, W, H = crop[0], crop[1], crop[2], crop[3], int(crop[4]), int(crop[5])
+    w, h = int(batch["width"]), int(batch["height"])
+    if not (0 < W <= w and 0 < H <= h):
+        raise ValueError(f"crop window {W}x{H} does not fit the {w}x{h} raster")
+    ox = 0 if (W == w or left_w > right_w) else w - W
+    oy = 0 if (H == h or top_h > bottom_h) else h - H
+    return w, h, ox, oy, W, H
+
+
+def is_cropped(batch):
+    """True when `renderer.paste` cuts something off a render of `batch` (an off-centre principal point)."""
+    crop = batch["crop"]
+    return int(crop[4]) != int(batch["width"]) or int(crop[5]) != int(batch["height"])
+
+
+def window_row_host(batch):
+    """The 9 float32 numbers of a windowed camera row (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): centre (3) | tan(FoVx/2) |
+    tan(FoVy/2) | w | h | ox | oy, with the 51 matrix numbers in front -> (60,): view | projection | full | row."""
+    m = Camera.pack_host_cached(batch)
+    w, h, ox, oy, _, _ = crop_window(batch)
+    out = np.empty(60, dtype=np.float32)
+    out[:48] = m[:48]
+    out[48:51] = m[48:51]
+    out[51:53] = m[51:53]
+    out[53:57] = (w, h, ox, oy)
+    out[57:] = 0.0
+    return out
 
 
 def _view_matrix(R, T):
@@ -103,17 +138,21 @@ class CameraSlot:
     _RING = 16
     _CAM_BYTES = 224                                          # 53 floats, padded to a multiple of 8 bytes for the cells behind
 
-    def __init__(self, width, height, device="cuda", cells=0):
+    def __init__(self, width, height, device="cuda", cells=0, _windowed=False):
         """cells: number of 8-byte ADDRESS CELLS kept behind the camera in the same device buffer (`cell(i)`): a
         `graph.TensorSlot(first, arena=slot, index=i)` then lives there, and `set()` moves the camera AND the cells with the ONE
         host-to-device copy it makes anyway (a step that repoints its target image needs one copy per replay instead of two)."""
         self.image_width, self.image_height = int(width), int(height)
         dev = torch.device(device)
         self.n_cells = int(cells)
-        nbytes = self._CAM_BYTES + 8 * self.n_cells
+        # windowed slot (CameraSlot.windowed): the centre row carries (w, h, ox, oy) as well -- 57 floats, padded to 232 bytes
+        self.windowed = bool(_windowed)
+        self._n_cam = 57 if self.windowed else 53
+        self._cam_bytes = 232 if self.windowed else self._CAM_BYTES
+        nbytes = self._cam_bytes + 8 * self.n_cells
         self.buffer = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.matrices = self.buffer[:212].view(torch.float32)
-        self.cells = self.buffer[self._CAM_BYTES:].view(torch.int64) if self.n_cells else None
+        self.matrices = self.buffer[:4 * self._n_cam].view(torch.float32)
+        self.cells = self.buffer[self._cam_bytes:].view(torch.int64) if self.n_cells else None
         # pinned staging ring: the host runs many steps ahead of the GPU, so a staging buffer may only be rewritten once the
         # asynchronous copy that reads it has executed (an event per slot of the ring)
         self._ring = [torch.zeros(nbytes, dtype=torch.uint8) for _ in range(self._RING)]
@@ -121,7 +160,7 @@ class CameraSlot:
         self._next = 0
         if dev.type == "cuda":
             self._ring = [t.pin_memory() for t in self._ring]
-        self._host_cam = torch.zeros(53, dtype=torch.float32)   # what the device holds / will hold: re-sent with every copy
+        self._host_cam = torch.zeros(self._n_cam, dtype=torch.float32)   # what the device holds / will hold: re-sent with every copy
         self._host_cam_np = self._host_cam.numpy()              # (numpy views of the host tensors: an element write through torch costs ~2 us)
         self._ring_np = [t.numpy() for t in self._ring]
         self._host_cells = torch.zeros(max(self.n_cells, 1), dtype=torch.int64)
@@ -130,9 +169,17 @@ class CameraSlot:
         self.world_view_transform = self.matrices[0:16].view(4, 4)
         self.projection_matrix = self.matrices[16:32].view(4, 4)
         self.full_proj_transform = self.matrices[32:48].view(4, 4)
-        self.camera_center = self.matrices[48:53]              # 3 used as the centre; [3], [4] = the tangents
-        self.tanfovx = self.tanfovy = 0.0                      # marker: read them from the buffer
+        self.camera_center = self.buffer[192:4 * self._n_cam].view(torch.float32)     # 3 used as the centre; [3], [4] = the tangents (+ w, h, ox, oy)
+        self.tanfovx = self.tanfovy = CAMERA_SLOT_WINDOWED if self.windowed else 0.0    # marker: read them from the buffer
         self.znear, self.zfar = ZNEAR, ZFAR
+
+    @classmethod
+    def windowed(cls, width, height, device="cuda", cells=0):
+        """A slot for every camera whose crop pastes to width x height (the dataset's image size), whatever its raster size and
+        principal point: the kernels rasterize the pasted window directly (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED), with the
+        raster size and the window offset read from the buffer -- one captured step serves all the cameras of a dataset.
+        `render()` then returns the (3, height, width) window itself."""
+        return cls(width, height, device=device, cells=cells, _windowed=True)
 
     def cell(self, i):
         """(1,) int64 device view of address cell i (for graph.TensorSlot)."""
@@ -153,9 +200,9 @@ class CameraSlot:
             self._events[i].synchronize()                      # the copy that last read this staging buffer has run
         stage = self._ring[i]
         snp = self._ring_np[i]
-        snp[:212].view(np.float32)[:] = self._host_cam_np
+        snp[:4 * self._n_cam].view(np.float32)[:] = self._host_cam_np
         if self.n_cells:
-            snp[self._CAM_BYTES:].view(np.int64)[:] = self._host_cells_np[:self.n_cells]
+            snp[self._cam_bytes:].view(np.int64)[:] = self._host_cells_np[:self.n_cells]
         self.buffer.copy_(stage, non_blocking=True)
         self._cells_dirty = False
         if self.buffer.is_cuda:
@@ -165,6 +212,13 @@ class CameraSlot:
         return self
 
     def set(self, batch):
+        if self.windowed:
+            w, h, ox, oy, W, H = crop_window(batch)
+            if (W, H) != (self.image_width, self.image_height):
+                raise ValueError(f"CameraSlot is a {self.image_width}x{self.image_height} window; the batch's crop pastes to {W}x{H}")
+            self._host_cam_np[:53] = Camera.pack_host_cached(batch)
+            self._host_cam_np[53:57] = (w, h, ox, oy)
+            return self.flush()
         if int(batch["width"]) != self.image_width or int(batch["height"]) != self.image_height:
             raise ValueError(f"CameraSlot is {self.image_width}x{self.image_height}; the batch is "
                              f"{batch['width']}x{batch['height']} (one slot / captured step per raster size)")
@@ -175,6 +229,25 @@ class CameraSlot:
 _cache = OrderedDict()
 _host_cache = OrderedDict()
 _CACHE_MAX = 512
+
+
+_window_cache = OrderedDict()
+
+
+def window_camera(batch, device="cuda"):
+    """(matrices (51,), campos (9,)) device tensors of a batch's WINDOWED camera row (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED),
+    from one H2D copy, cached on the numbers that define them (like batch_to_camera)."""
+    row = window_row_host(batch)
+    key = (row.tobytes(), str(device))
+    hit = _window_cache.get(key)
+    if hit is None:
+        buf = torch.from_numpy(row).to(torch.device(device))
+        hit = _window_cache[key] = (buf[:51], buf[48:57])
+        if len(_window_cache) > _CACHE_MAX:
+            _window_cache.popitem(last=False)
+    else:
+        _window_cache.move_to_end(key)
+    return hit
 
 
 def batch_to_camera(batch, device="cuda"):

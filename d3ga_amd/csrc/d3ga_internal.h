@@ -165,6 +165,13 @@ static inline int tiles_x(int W) { return (W + kTile - 1) / kTile; }
 static inline int tiles_y(int H) { return (H + kTile - 1) / kTile; }
 // cameras in the batch (d3ga_raster_params::n_views: 0 and 1 both mean one)
 static inline int n_views_of(const d3ga_raster_params *prm) { return prm->n_views > 1 ? prm->n_views : 1; }
+// windowed camera slot (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): W, H are the window, the tile grid has one spare column and row per view
+static inline bool is_windowed(const d3ga_raster_params *prm) { return prm->tanfovx == D3GA_CAMERA_SLOT_WINDOWED; }
+static inline int grid_x(const d3ga_raster_params *prm) { return tiles_x(prm->W) + (is_windowed(prm) ? 1 : 0); }
+static inline int grid_y(const d3ga_raster_params *prm) { return tiles_y(prm->H) + (is_windowed(prm) ? 1 : 0); }
+// the window table behind the binning buffer's sections (one int4 {ox, oy, w, h} per view): null unless windowed
+static inline int4 *win_table(void *binning, int64_t tiles, int64_t dcap) { return (int4 *)((char *)binning + bin_bytes(tiles, dcap)); }
+static inline int64_t win_table_bytes(int64_t views) { return align256(16 * views); }
 
 // launch check: returns hipError (>0) or 0; in debug mode also synchronises
 static inline int check_launch(hipStream_t s, int debug) {

@@ -67,6 +67,37 @@ extern "C" int d3ga_raster_scratch_bytes_views(int32_t P, int32_t W, int32_t H, 
     return D3GA_OK;
 }
 
+extern "C" int d3ga_raster_scratch_bytes_window(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t d_capacity,
+                                                int32_t forward_only, int64_t sizes[3]) {
+    if (!sizes) return D3GA_E_NULL;
+    if (P < 0 || W <= 0 || H <= 0 || d_capacity < 0 || n_views < 0) return D3GA_E_SIZE;
+    const int64_t k = n_views > 1 ? n_views : 1;
+    const int64_t gx = tiles_x(W) + 1, gy = tiles_y(H) + 1;                 // the window grid (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED)
+    if (gy * k > 65535 || gx > 65535 || (int64_t)P * k >= (1ll << 31)) return D3GA_E_SIZE;
+    const int64_t tiles = gx * gy * k, cap = d_capacity > 0 ? d_capacity : 1;
+    sizes[0] = geom_bytes(P > 0 ? P * k : 1);
+    sizes[1] = bin_bytes(tiles, cap) + win_table_bytes(k);
+    sizes[2] = forward_only ? 2 * align256(4 * (int64_t)W * H * k) : img_bytes(W, H, tiles, cap, k);
+    return D3GA_OK;
+}
+
+extern "C" int d3ga_raster_binning_layout_window(int32_t W, int32_t H, int32_t n_views, int64_t d_capacity, int64_t offsets[7]) {
+    if (!offsets) return D3GA_E_NULL;
+    if (W <= 0 || H <= 0 || d_capacity < 0 || n_views < 0) return D3GA_E_SIZE;
+    const int64_t k = n_views > 1 ? n_views : 1, cap = d_capacity > 0 ? d_capacity : 1;
+    const int64_t tiles = (int64_t)(tiles_x(W) + 1) * (tiles_y(H) + 1) * k;
+    char *base = (char *)nullptr + 256;
+    const BinBuf b = carve_bin(base, tiles, cap);
+    offsets[0] = (char *)b.counters - base;
+    offsets[1] = (char *)b.tile_count - base;
+    offsets[2] = (char *)b.tile_start - base;
+    offsets[3] = (char *)b.tile_cursor - base;
+    offsets[4] = (char *)b.keys - base;
+    offsets[5] = (char *)b.point_list - base;
+    offsets[6] = (char *)win_table(base, tiles, cap) - base;
+    return D3GA_OK;
+}
+
 extern "C" int d3ga_raster_scratch_bytes(int32_t P, int32_t W, int32_t H, int64_t d_capacity, int64_t sizes[3]) {
     return d3ga_raster_scratch_bytes_views(P, W, H, 1, d_capacity, 0, sizes);
 }

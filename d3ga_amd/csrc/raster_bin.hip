@@ -583,8 +583,8 @@ extern "C" int d3ga_raster_bin_sort(const d3ga_raster_params *prm, void *geom, v
     hipStream_t s = (hipStream_t)stream;
     // a batch of views is one tall frame for this stage: views x P records, views x tiles lists (d3ga.h: n_views)
     const int views = n_views_of(prm);
-    const int gx = tiles_x(prm->W);
-    const int tiles = gx * tiles_y(prm->H) * views;
+    const int gx = grid_x(prm);                  // (a windowed slot: the window's grid, d3ga.h D3GA_CAMERA_SLOT_WINDOWED)
+    const int tiles = gx * grid_y(prm) * views;
     const int64_t P = (int64_t)prm->P * views;
     BinBuf bin = carve_bin(binning, tiles, d_capacity);
     GeomBuf g = carve_geom(geom, P);

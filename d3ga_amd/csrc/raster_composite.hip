@@ -52,7 +52,10 @@ __device__ unsigned long long g_diag_fwd_waves[32768 * 4];    // per active wave
 // renderer.py:141 takes [0]; without it the blend loop is one FMA per entry shorter and 4 B per pixel are not written)
 // L1V: the L1 loss value against a target image is formed here as well (d3ga_raster_composite_fwd_l1; never with DUAL)
 // PVB: bg is (k,3), one background per view (d3ga.h: per_view_background); the quadrant's view picks its row once per wavefront
-template <bool DUAL, bool DEPTH, bool L1V, bool PVB = false>
+// WIN: windowed camera slot (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): W x H is the window; the quadrant's view reads {ox, oy} from the
+// window table, pixels are placed in full-raster coordinates (tile grid from (ox / 16, oy / 16)), only pixels inside the window
+// blend and are written, at ((y - oy) W + (x - ox))
+template <bool DUAL, bool DEPTH, bool L1V, bool PVB = false, bool WIN = false>
 __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) void composite_fwd_q_kernel(
     int W, int H, int gx, int gy, int gyv /* tile rows per view (= gy for one view) */, const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
     uint64_t dcap, const float2 *xy /* = xyh viewed as float2: the centre is record[0..1], stride 2 (round 4: no separate xy array) */, const float4 *__restrict__ conic_o,
@@ -60,17 +63,26 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     float *__restrict__ final_T, uint32_t *__restrict__ n_contrib, float *__restrict__ out_color,
     float *__restrict__ out_invdepth, const uint32_t *__restrict__ tile_order, const float *__restrict__ colors2,
     const float *__restrict__ bg2, float *__restrict__ out_color2, uint2 *__restrict__ blk_list,
-    uint32_t *__restrict__ blk_count, bool exact_cull, L1Value l1v, int P /* Gaussians per view: colors2 is indexed by Gaussian, the lists by (view, Gaussian) */) {
-    const Quad q = tile_order ? quad_of_block_ordered(gx, gx * gy, gyv, tile_order) : quad_of_block(gx, gy, gyv);
+    uint32_t *__restrict__ blk_count, bool exact_cull, L1Value l1v, int P /* Gaussians per view: colors2 is indexed by Gaussian, the lists by (view, Gaussian) */,
+    const int4 *__restrict__ win /* WIN: the window table ({ox, oy, w, h} per view) */) {
+    Quad q = tile_order ? quad_of_block_ordered(gx, gx * gy, gyv, tile_order) : quad_of_block(gx, gy, gyv);
     if (!q.valid) return;                                 // wave-uniform
+    int ox = 0, oy = 0;
+    if constexpr (WIN) {                                  // full-raster pixel coordinates: the grid starts at the window's first tile
+        const int4 wv = win[q.view];
+        ox = wv.x; oy = wv.y;
+        const int sx = ox & ~(kTile - 1), sy = oy & ~(kTile - 1);
+        q.qx0 += sx; q.qy0 += sy; q.px += sx; q.py += sy;
+    }
     const float *const bgv = PVB ? bg + 3 * q.view : bg;  // (wave-uniform; the single-background instantiations read bg itself)
-    if (q.qx0 >= W || q.qy0 >= H) {                       // a quadrant without pixels: its L1 partial is zero
+    if (WIN ? (q.qx0 >= ox + W || q.qy0 >= oy + H || q.qx0 + 8 <= ox || q.qy0 + 8 <= oy) : (q.qx0 >= W || q.qy0 >= H)) {   // a quadrant without pixels: its L1 partial is zero
         if (L1V && threadIdx.x == 0) l1v.partials[4 * (size_t)q.tile + q.quad] = 0.f;
         return;
     }
     const int lane = threadIdx.x & 63;
     const RowGeom rg = row_geom(q, lane);
-    const bool inside = rg.px < W && rg.py < H;
+    const bool inside = WIN ? (rg.px >= ox && rg.px < ox + W && rg.py >= oy && rg.py < oy + H) : (rg.px < W && rg.py < H);
+    const int ix = WIN ? rg.px - ox : rg.px, iy = WIN ? rg.py - oy : rg.py;      // the pixel in the output image
     const float fx = (float)rg.px, fy = (float)rg.py;
     const float bx0 = (float)q.qx0, by0 = (float)q.qy0;
     const uint32_t begin = (uint32_t)min((uint64_t)tile_start[q.tile], dcap);
@@ -83,7 +95,7 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     float tg0 = 0.f, tg1 = 0.f, tg2 = 0.f;
     if (L1V && inside) {
         const float *tg = l1v.target_cell ? *l1v.target_cell : l1v.target;
-        const size_t hw = (size_t)H * W, pid = 3 * hw * q.view + (size_t)rg.py * W + rg.px;
+        const size_t hw = (size_t)H * W, pid = 3 * hw * q.view + (size_t)iy * W + ix;
         tg0 = tg[pid]; tg1 = tg[hw + pid]; tg2 = tg[2 * hw + pid];
     }
     uint2 *const blk_base = blk_list ? blk_list + 16 * (size_t)begin + (size_t)(4 * q.quad) * blk_cap : nullptr;
@@ -326,7 +338,7 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     }
     if (inside) {
         const size_t hw = (size_t)H * W;
-        const size_t pid1 = hw * q.view + (size_t)rg.py * W + rg.px, pid = pid1 + 2 * hw * q.view;      // one-plane / three-plane images of the view
+        const size_t pid1 = hw * q.view + (size_t)iy * W + ix, pid = pid1 + 2 * hw * q.view;      // one-plane / three-plane images of the view
         final_T[pid1] = T;
         n_contrib[pid1] = last;
         out_color[pid] = C0 + T * bgv[0];
@@ -416,21 +428,27 @@ static int composite_fwd_impl(const d3ga_raster_params *prm, const float *bg, co
     if (colors2 && (!bg2 || !out_color2)) return D3GA_E_NULL;
     const int views = n_views_of(prm);
     hipStream_t s = (hipStream_t)stream;
-    const int gx = tiles_x(prm->W), gyv = tiles_y(prm->H), gy = gyv * views;
+    const int gx = grid_x(prm), gyv = grid_y(prm), gy = gyv * views;
     const BinBuf bin = carve_bin(const_cast<void *>(binning), (int64_t)gx * gy, d_capacity);
     const GeomBuf g = carve_geom(const_cast<void *>(geom), (int64_t)prm->P * views);
     ImgBuf im = carve_img(img, prm->W, prm->H, (int64_t)gx * gy, views);
+    const bool wnd = is_windowed(prm);
+    const int4 *wtab = wnd ? win_table(const_cast<void *>(binning), (int64_t)gx * gy, d_capacity) : nullptr;
     if (prm->forward_only) { im.blk_list = nullptr; im.blk_count = nullptr; }     // the buffer ends behind n_contrib
     const bool ordered = (composite_variant() & kVariantOrdered) != 0, exact = (composite_variant() & kVariantExactCull) != 0;
     const dim3 grid(ordered ? quad_grid_ordered(gx * gy) : quad_grid(gx, gy));
     const uint32_t *order = ordered ? (const uint32_t *)bin.tile_order : (const uint32_t *)nullptr;
     const bool pvb = views > 1 && prm->per_view_background;      // bg (k,3)
-#define D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, PVBV)                                                                            \
-    hipLaunchKernelGGL((composite_fwd_q_kernel<DUALV, DEPTHV, L1VV, PVBV>), grid, dim3(64), 0, s, prm->W, prm->H, gx, gy, gyv, bin.tile_start, \
+#define D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, PVBV, WINV)                                                                      \
+    hipLaunchKernelGGL((composite_fwd_q_kernel<DUALV, DEPTHV, L1VV, PVBV, WINV>), grid, dim3(64), 0, s, prm->W, prm->H, gx, gy, gyv, bin.tile_start, \
                        bin.point_list, (uint64_t)d_capacity, reinterpret_cast<const float2 *>(g.xyh), g.conic_o, g.rgb_invd, g.xyh, bg, im.final_T, im.n_contrib,     \
-                       out_color, out_invdepth, order, colors2, bg2, out_color2, im.blk_list, im.blk_count, exact, l1v, prm->P)
+                       out_color, out_invdepth, order, colors2, bg2, out_color2, im.blk_list, im.blk_count, exact, l1v, prm->P, wtab)
 #define D3GA_LAUNCH_FWD(DUALV, DEPTHV, L1VV)                                                                                    \
-    do { if (pvb) D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, true); else D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, false); } while (0)
+    do {                                                                                                                        \
+        if (wnd) { if (pvb) D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, true, true); else D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, false, true); } \
+        else if (pvb) D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, true, false);                                                      \
+        else D3GA_LAUNCH_FWD_B(DUALV, DEPTHV, L1VV, false, false);                                                              \
+    } while (0)
     if (colors2 && l1v.partials) return D3GA_E_CONFIG;
     if (colors2) { if (out_invdepth) D3GA_LAUNCH_FWD(true, true, false); else D3GA_LAUNCH_FWD(true, false, false); }
     else if (l1v.partials) { if (out_invdepth) D3GA_LAUNCH_FWD(false, true, true); else D3GA_LAUNCH_FWD(false, false, true); }
@@ -456,7 +474,7 @@ extern "C" int d3ga_raster_composite_fwd_l1(const d3ga_raster_params *prm, const
     const L1Value l1v = {target, (const float *const *)target_cell, partials, 1.0f / (3.0f * (float)prm->W * (float)prm->H * (float)views)};
     D3GA_TRY(composite_fwd_impl(prm, bg, geom, binning, d_capacity, img, out_color, out_invdepth, nullptr, nullptr, nullptr,
                                 stream, l1v));
-    launch_sum_partials(4 * tiles_x(prm->W) * tiles_y(prm->H) * views, partials, loss, (hipStream_t)stream);
+    launch_sum_partials(4 * grid_x(prm) * grid_y(prm) * views, partials, loss, (hipStream_t)stream);
     return check_launch((hipStream_t)stream, prm->debug);
 }
 
@@ -480,7 +498,7 @@ static int composite_bwd_impl(const d3ga_raster_params *prm, const float *bg, co
     if (l1.image && (!(l1.target || l1.target_cell) || !l1.g_loss)) return D3GA_E_NULL;
     if (colors2 && (!bg2 || !dL_dpix2)) return D3GA_E_NULL;
     const int views = n_views_of(prm);
-    const int gx = tiles_x(prm->W), gy = tiles_y(prm->H) * views;
+    const int gx = grid_x(prm), gy = grid_y(prm) * views;
     const BinBuf bin = carve_bin(const_cast<void *>(binning), (int64_t)gx * gy, d_capacity);
     const GeomBuf g = carve_geom(const_cast<void *>(geom), (int64_t)prm->P * views);
     const ImgBuf im = carve_img(const_cast<void *>(img), prm->W, prm->H, (int64_t)gx * gy, views);

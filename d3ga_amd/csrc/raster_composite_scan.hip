@@ -121,13 +121,14 @@ struct BwdArgs {
     const float2 *xy; const float4 *conic_o; const float4 *rgb_invd; const float *bg; const float *final_T; const uint32_t *n_contrib;
     const float *dL_dpix; float *acc; const float *colors2; const float *bg2; const float *dL_dpix2; const uint2 *blk_list;
     const uint32_t *blk_count; L1Source l1; const float *dL_dinvd;
+    const int4 *win;         // windowed camera slot: the window table ({ox, oy, w, h} per view), else null
 };
 struct BwdDiag { unsigned long long install = 0, hit = 0, evict = 0, valid = 0, entries = 0, rowgroups = 0, trips = 0, groups = 0; };
 
 // One wavefront's share of one tile: its SEG = 4 / R blocks (`blk`: the block of THIS lane's segment, in the forward's numbering),
 // walked back to front in groups of 16 R entries, every record merged into the tile's cache `s_cache` (see the file header).
 // s_pix / s_dump: this wavefront's pixel records and staging area.
-template <bool DUAL, int S, bool INVD, int R>
+template <bool DUAL, int S, bool INVD, int R, bool WIN>
 __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, const uint32_t begin, const uint32_t end, const int blk,
                                               uint32_t *const s_cache, float *const s_pix, float *const s_dump, const int lane,
                                               BwdDiag &dg) {
@@ -143,11 +144,15 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
     constexpr int kAccStride = D3GA_ACC_STRIDE;
     const int bx = 2 * ((blk >> 2) & 1) + (blk & 1), by = 2 * (blk >> 3) + ((blk >> 1) & 1);      // the forward numbers a tile's blocks 4 * quadrant + (block within the quadrant)
     const int tyb = tile / A.gx, view = tyb / A.gyv;                                          // tile row of the batch -> (view, row of the view)
-    const int bx0 = (tile - tyb * A.gx) * kTile + 4 * bx, by0 = (tyb - view * A.gyv) * kTile + 4 * by;      // block origin in pixels (local to the view)
+    int4 wv = make_int4(0, 0, A.W, A.H);                         // WIN: {ox, oy, w, h} of the view (the grid starts at tile (ox / 16, oy / 16))
+    if constexpr (WIN) wv = A.win[view];
+    const int bx0 = (tile - tyb * A.gx) * kTile + 4 * bx + (WIN ? (wv.x & ~(kTile - 1)) : 0);
+    const int by0 = (tyb - view * A.gyv) * kTile + 4 * by + (WIN ? (wv.y & ~(kTile - 1)) : 0);      // block origin in pixels (local to the view)
     const int px = bx0 + (l16 & 3), py = by0 + (l16 >> 2);
-    const bool inside = px < A.W && py < A.H;
+    const bool inside = WIN ? (px >= wv.x && px < wv.x + A.W && py >= wv.y && py < wv.y + A.H) : (px < A.W && py < A.H);
+    const int ix = WIN ? px - wv.x : px, iy = WIN ? py - wv.y : py;      // the pixel in the W x H images
     const size_t hw = (size_t)A.H * A.W;
-    const size_t pid1 = hw * view + (size_t)py * A.W + px;       // one-plane images (final_T, n_contrib, inverse depth) of the view
+    const size_t pid1 = hw * view + (size_t)iy * A.W + ix;       // one-plane images (final_T, n_contrib, inverse depth) of the view
     const size_t pid = pid1 + 2 * hw * view;                     // three-plane images
     const float T_final = inside ? A.final_T[pid1] : 0.f;
     const uint32_t last = inside ? A.n_contrib[pid1] : 0u;
@@ -184,11 +189,12 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
     }
     const uint32_t blk_cap = end - begin;
     // (the forward writes A.blk_count only for quadrants that start inside the image)
-    const bool quad_in = bx0 - 4 * (bx & 1) < A.W && by0 - 4 * (by & 1) < A.H;
+    const int qx0 = bx0 - 4 * (bx & 1), qy0 = by0 - 4 * (by & 1);
+    const bool quad_in = WIN ? (qx0 < wv.x + A.W && qy0 < wv.y + A.H && qx0 + 8 > wv.x && qy0 + 8 > wv.y) : (qx0 < A.W && qy0 < A.H);
     const uint32_t cnt = quad_in ? A.blk_count[16 * (size_t)tile + blk] : 0u;
     const uint2 *const list = A.blk_list + 16 * (size_t)begin + (size_t)blk * blk_cap;
     const int ngroups = (int)((wave_max_u32(cnt) + (uint32_t)(LW - 1)) / (uint32_t)LW);
-    const float ddelx_dx = 0.5f * A.W, ddely_dy = 0.5f * A.H;
+    const float ddelx_dx = 0.5f * (WIN ? wv.z : A.W), ddely_dy = 0.5f * (WIN ? wv.w : A.H);      // d(pixel)/d(ndc) of the full raster
     const float bxr = (float)bx0, byr = (float)by0;
     const int per = D3GA_SCAN_ABL == 12 ? LW : (ngroups > 0 ? ((int)cnt + ngroups - 1) / ngroups : 0);      // rows paced to finish together (see above)
     auto list_entry = [&](int g) -> uint2 {
@@ -399,7 +405,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
 // wavefronts per tile.  2 / 4: 8 / 16 wavefronts per tile, a block's list runs over 2 / 4 rows (32 / 64 entries per group), a
 // wavefront takes 2 / 1 blocks -- the same pixel steps in total, but the tile's longest list is walked in half / a quarter of
 // the groups: the critical path of a heavy tile (18 groups of one wavefront at C3) shrinks with it.
-template <bool DUAL, int S, bool INVD = false, int R = 1, bool PVB = false>      // PVB: bg is (k,3), one row per view (d3ga.h: per_view_background)
+template <bool DUAL, int S, bool INVD = false, int R = 1, bool PVB = false, bool WIN = false>      // PVB: bg is (k,3), one row per view (d3ga.h: per_view_background); WIN: windowed camera slot
 __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_WAVES : 3) : D3GA_TILE_WAVES)) void composite_bwd_tile_kernel(   // (DUAL: 12-float pixel records -- the LDS of three workgroups per CU)
    
     int W, int H, int gx, int gy, int gyv, const uint32_t *__restrict__ tile_start, uint64_t dcap, const float2 *__restrict__ xy,
@@ -407,7 +413,8 @@ __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_W
     const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix,
     float *__restrict__ acc, const uint32_t *__restrict__ tile_order, const float *__restrict__ colors2,
     const float *__restrict__ bg2, const float *__restrict__ dL_dpix2, const uint2 *__restrict__ blk_list,
-    const uint32_t *__restrict__ blk_count, int assign, L1Source l1, const float *__restrict__ dL_dinvd, int split_cap, const uint32_t *__restrict__ split_cnt, int P) {
+    const uint32_t *__restrict__ blk_count, int assign, L1Source l1, const float *__restrict__ dL_dinvd, int split_cap, const uint32_t *__restrict__ split_cnt, int P,
+    const int4 *__restrict__ win) {
     static_assert((S & (S - 1)) == 0, "power of two");
     constexpr int NW = 4 * R;                        // wavefronts per tile (three, the third walking two sets of blocks: measured, slower -- DESIGN.md sec. 4)
     constexpr int SEG = 4 / R, LW = 16 * R;          // blocks per wavefront, lanes per block
@@ -444,10 +451,13 @@ __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_W
     __shared__ uint8_t s_perm[16];                          // assign 2: the tile's 16 blocks by descending list length
     if (R > 1 || half >= 0) assign = 2;                     // (the quadrant / interleaved assignments exist for R = 1 only)
     if (assign == 2 && threadIdx.x < 16) {
-        const int b = threadIdx.x, tx0 = (tile % gx) * kTile, ty0 = ((tile / gx) % gyv) * kTile;
+        int4 wv = make_int4(0, 0, W, H);
+        if constexpr (WIN) wv = win[(tile / gx) / gyv];
+        const int b = threadIdx.x, tx0 = (tile % gx) * kTile + (WIN ? (wv.x & ~(kTile - 1)) : 0), ty0 = ((tile / gx) % gyv) * kTile + (WIN ? (wv.y & ~(kTile - 1)) : 0);
         auto count_of = [&](int j) -> uint32_t {            // (the forward writes the counts of quadrants that start inside the image)
-            const int q = j >> 2;
-            return (tx0 + ((q & 1) << 3) < W && ty0 + ((q >> 1) << 3) < H) ? blk_count[16 * (size_t)tile + j] : 0u;
+            const int q = j >> 2, qx = tx0 + ((q & 1) << 3), qy = ty0 + ((q >> 1) << 3);
+            const bool in = WIN ? (qx < wv.x + W && qy < wv.y + H && qx + 8 > wv.x && qy + 8 > wv.y) : (qx < W && qy < H);
+            return in ? blk_count[16 * (size_t)tile + j] : 0u;
         };
         const uint32_t mine = count_of(b);
         int rank = 0;
@@ -490,12 +500,12 @@ __global__ __launch_bounds__(256 * R, (DUAL ? (D3GA_TILE_WAVES < 3 ? D3GA_TILE_W
             blk = 4 * ((bx >> 1) + 2 * (by >> 1)) + ((bx & 1) + 2 * (by & 1));
         }
         const float *const bgv = PVB ? bg + 3 * ((tile / gx) / gyv) : bg;      // the tile's view: uniform over the workgroup
-        const BwdArgs A = {W, H, gx, gyv, P, xy, conic_o, rgb_invd, bgv, final_T, n_contrib, dL_dpix, acc, colors2, bg2, dL_dpix2, blk_list, blk_count, l1, dL_dinvd};
+        const BwdArgs A = {W, H, gx, gyv, P, xy, conic_o, rgb_invd, bgv, final_T, n_contrib, dL_dpix, acc, colors2, bg2, dL_dpix2, blk_list, blk_count, l1, dL_dinvd, win};
         if (R == 1 && half >= 0) {
             blk = s_perm[2 * (2 * ((wave + (int)blockIdx.x) & 3) + (lane >> 5)) + half];
-            bwd_tile_wave<DUAL, S, INVD, (R == 1 ? 2 : R)>(A, tile, begin, end, blk, s_cache, s_pix, s_dump, lane, dg);
+            bwd_tile_wave<DUAL, S, INVD, (R == 1 ? 2 : R), WIN>(A, tile, begin, end, blk, s_cache, s_pix, s_dump, lane, dg);
         } else
-        bwd_tile_wave<DUAL, S, INVD, R>(A, tile, begin, end, blk, s_cache, s_pix, s_dump, lane, dg);
+        bwd_tile_wave<DUAL, S, INVD, R, WIN>(A, tile, begin, end, blk, s_cache, s_pix, s_dump, lane, dg);
     }
 
 #ifdef D3GA_DIAG_COUNTERS
@@ -568,13 +578,19 @@ int launch_composite_bwd_scan(const d3ga_raster_params *prm, int gx, int gy, con
     const dim3 tgrid(gx * gy + split_cap);
     const int S = composite_merge_slots();
     const bool pvb = n_views_of(prm) > 1 && prm->per_view_background;      // bg (k,3)
-#define D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, RV, PVBV)                                                                        \
-    hipLaunchKernelGGL((composite_bwd_tile_kernel<DUALV, SV, INVDV, RV, PVBV>), tgrid, dim3(256 * RV),                          \
+    const bool wnd = is_windowed(prm);
+    const int4 *wtab = wnd ? win_table((void *)bin.counters, (int64_t)gx * gy, d_capacity) : nullptr;
+#define D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, RV, PVBV, WINV)                                                                  \
+    hipLaunchKernelGGL((composite_bwd_tile_kernel<DUALV, SV, INVDV, RV, PVBV, WINV>), tgrid, dim3(256 * RV),                    \
                        0, s, prm->W, prm->H, gx, gy, gy / n_views_of(prm), bin.tile_start, \
                        (uint64_t)d_capacity, reinterpret_cast<const float2 *>(g.xyh), g.conic_o, g.rgb_invd, bg, im.final_T, im.n_contrib, dL_dpix, acc, order,   \
-                       colors2, bg2, dL_dpix2, (const uint2 *)im.blk_list, (const uint32_t *)im.blk_count, composite_tile_assign(), l1, dL_dinvd, split_cap, split_cnt, prm->P)
+                       colors2, bg2, dL_dpix2, (const uint2 *)im.blk_list, (const uint32_t *)im.blk_count, composite_tile_assign(), l1, dL_dinvd, split_cap, split_cnt, prm->P, wtab)
 #define D3GA_LAUNCH_TILE(DUALV, SV, INVDV)                                                                                    \
-    do { if (pvb) D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, true); else D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, false); } while (0)
+    do {                                                                                                                      \
+        if (wnd) { if (pvb) D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, true, true); else D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, false, true); } \
+        else if (pvb) D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, true, false);                                                   \
+        else D3GA_LAUNCH_TILE_R(DUALV, SV, INVDV, 1, false, false);                                                           \
+    } while (0)
     if (dL_dinvd) {                                          // inverse-depth gradient (branch dr_aa): single-image launches only
         if (colors2) return D3GA_E_CONFIG;
         if (S >= 512) D3GA_LAUNCH_TILE(false, 512, true); else D3GA_LAUNCH_TILE(false, 256, true);

@@ -196,6 +196,25 @@ __device__ __forceinline__ TileRect write_geom_records(const GeomBuf &geom, int 
     return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
 }
 
+// Windowed camera slot (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): the splat was projected on the view's full raster; its tile rectangle
+// is intersected with the window's tiles [x0, x0 + gx) x [y0, y0 + gy) and rebased to them.  Only integer tile indices move: every
+// float of the record is the full-raster one.  A rectangle that misses the window culls the Gaussian in this view (radius kept).
+__device__ __forceinline__ PreOut window_clip(PreOut o, int x0, int y0, int gx, int gy) {
+    Splat &sp = o.sp;
+    const int r0 = max(sp.rect[0], x0) - x0, r1 = max(sp.rect[1], y0) - y0;
+    const int r2 = min(sp.rect[2], x0 + gx) - x0, r3 = min(sp.rect[3], y0 + gy) - y0;
+    if (sp.visible && r2 > r0 && r3 > r1) { sp.rect[0] = r0; sp.rect[1] = r1; sp.rect[2] = r2; sp.rect[3] = r3; }
+    else { sp.visible = false; sp.rect[0] = sp.rect[1] = sp.rect[2] = sp.rect[3] = 0; }
+    return o;
+}
+// the window table of the binning buffer (one {ox, oy, w, h} per view) from the views' 9-float camera rows
+__global__ void window_table_kernel(const float *__restrict__ campos, int views, int4 *__restrict__ table) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= views) return;
+    const float *cp = campos + (size_t)D3GA_CAMERA_SLOT_WINDOWED_FLOATS * v;
+    table[v] = make_int4((int)cp[7], (int)cp[8], (int)cp[5], (int)cp[6]);
+}
+
 // tile histogram (counting-sort pass 1) of this block's Gaussians through its LDS window.  Every thread of the block must call it
 // (barriers inside); s_cnt: kWinTiles words that nobody else uses between the call's first and last barrier.
 __device__ __forceinline__ void tile_histogram(int *s_box, uint32_t *s_cnt, const TileRect &t, int gx, uint32_t *__restrict__ tile_count,
@@ -224,7 +243,8 @@ __device__ __forceinline__ void tile_histogram(int *s_box, uint32_t *s_cnt, cons
     }
 }
 
-template <bool WANT_J>      // WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
+// WIN: windowed camera slot (campos: 9 floats, d3ga.h): project with the view's raster size, histogram over the window's tiles
+template <bool WANT_J, bool WIN = false>      // WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
@@ -233,6 +253,12 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     uint32_t *__restrict__ tile_count, uint32_t *__restrict__ counters, int32_t *__restrict__ radii,
     int tile_row0 /* view-batched renders: this view's first tile row in the batch's grid (d3ga.h: n_views); else 0 */) {
     if (!(prm.tanfovx > 0.f)) { prm.tanfovx = campos[3]; prm.tanfovy = campos[4]; }     // camera slot: see d3ga.h
+    int wx0 = 0, wy0 = 0, wgx = 0, wgy = 0;                          // (WIN) the window's first tile and its grid
+    if constexpr (WIN) {
+        wgx = (prm.W + kTile - 1) / kTile + 1; wgy = (prm.H + kTile - 1) / kTile + 1;
+        wx0 = (int)campos[7] / kTile; wy0 = (int)campos[8] / kTile;
+        prm.W = (int)campos[5]; prm.H = (int)campos[6];
+    }
     // one dynamic LDS region, used first as the SH staging slabs and then (after a barrier) as the tile window
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_box[4];
@@ -275,12 +301,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
                                 : preprocess_one(prm, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, colors_precomp,
                                                  opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                                                  campos);
-        tr = write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, want_j, cj);
+        if constexpr (WIN) tr = write_geom_records(geom, i, window_clip(o, wx0, wy0, wgx, wgy), !cov3D_precomp, tile_row0, radii, want_j, cj);
+        else tr = write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, want_j, cj);
     }
 #ifdef D3GA_DIAG
     if (prm.debug & 0x100) return;                                              // diag: no histogram
 #endif
-    tile_histogram(s_box, s_cnt, tr, (prm.W + kTile - 1) / kTile, tile_count, counters);      // (barriers inside: the slabs are dead now)
+    tile_histogram(s_box, s_cnt, tr, WIN ? wgx : (prm.W + kTile - 1) / kTile, tile_count, counters);      // (barriers inside: the slabs are dead now)
 }
 
 // The same for KV views of ONE set of Gaussians in one pass (view-batched renders with shared geometry, d3ga.h: n_views): the
@@ -451,6 +478,7 @@ __global__ __launch_bounds__(kBlock) void recolor_kernel(d3ga_raster_params prm,
     dst.clamped[i] = mask;
 }
 
+template <bool WIN = false>      // WIN: windowed camera slot -- the view's raster size from campos[5], campos[6]
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ viewmatrix,
@@ -460,6 +488,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscales, float *__restrict__ dL_drots,
     const float *__restrict__ cov3D_precomp, int accum /* views > 0 of a batch: add to the gradients of inputs the views share (raster_pre_body.h) */) {
     if (!(prm.tanfovx > 0.f)) { prm.tanfovx = campos[3]; prm.tanfovy = campos[4]; }     // camera slot: see d3ga.h
+    if constexpr (WIN) { prm.W = (int)campos[5]; prm.H = (int)campos[6]; }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_sh = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -558,6 +587,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
 // and dL/dcolour are written per view at record v P + i of the group (a view that culled the Gaussian writes zeros), not summed.
 constexpr int kMaxGroup = 8;
 struct ViewCamsN { const float *vm[kMaxGroup], *pm[kMaxGroup], *cp[kMaxGroup]; };
+template <bool WIN = false>      // WIN: windowed camera slots -- every view's raster size from its camera row
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
     d3ga_raster_params prm, int kv, const float *__restrict__ means3D, bool sh_path, const float *__restrict__ scales,
     const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp, ViewCamsN cams, GeomBuf geom /* first view of the group */,
@@ -641,7 +671,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
             const float *vm = cams.vm[v], *pm = cams.pm[v], *cp = cams.cp[v];
             const float tfx = slot ? cp[3] : prm.tanfovx, tfy = slot ? cp[4] : prm.tanfovy;
             float gm_v[3] = {0.f, 0.f, 0.f}, g6_v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, aa = 1.0f;
-            cov2d_bwd(mean, c6, vm, prm.W, prm.H, tfx, tfy, a[3], a[4], a[5], g6_v, gm_v, prm.antialiasing != 0, a[6], act_opacity, &aa);
+            cov2d_bwd(mean, c6, vm, WIN ? (int)cp[5] : prm.W, WIN ? (int)cp[6] : prm.H, tfx, tfy, a[3], a[4], a[5], g6_v, gm_v, prm.antialiasing != 0,
+                      a[6], act_opacity, &aa);
             project_bwd(mean, pm, a[0], a[1], gm_v);
             const float z = vm[2] * mean.x + vm[6] * mean.y + vm[10] * mean.z + vm[14];
             const float gz = -a[10] / (z * z);
@@ -777,7 +808,7 @@ static int validate(const d3ga_raster_params *prm) {
     if (prm->P < 0 || prm->W <= 0 || prm->H <= 0 || prm->M < 0 || prm->M > 16) return D3GA_E_SIZE;
     if (prm->sh_degree < 0 || prm->sh_degree > 3) return D3GA_E_CONFIG;
     if (prm->n_views < 0) return D3GA_E_SIZE;
-    if (((prm->W + kTile - 1) / kTile) > 65535 || (int64_t)((prm->H + kTile - 1) / kTile) * n_views_of(prm) > 65535) return D3GA_E_SIZE;
+    if (grid_x(prm) > 65535 || (int64_t)grid_y(prm) * n_views_of(prm) > 65535) return D3GA_E_SIZE;
     if ((int64_t)prm->P * n_views_of(prm) >= (1ll << 31)) return D3GA_E_SIZE;
     return D3GA_OK;
 }
@@ -791,11 +822,13 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     if (!geom || !binning || !viewmatrix || !projmatrix || !campos) return D3GA_E_NULL;
     if (d_capacity < 0) return D3GA_E_SIZE;
     hipStream_t s = (hipStream_t)stream;
-    const int views = n_views_of(prm), gyv = tiles_y(prm->H);
-    const int64_t tiles = (int64_t)tiles_x(prm->W) * gyv * views;
+    const int views = n_views_of(prm), gyv = grid_y(prm);
+    const int64_t tiles = (int64_t)grid_x(prm) * gyv * views;
+    const bool wnd = is_windowed(prm);
     BinBuf bin = carve_bin(binning, tiles, d_capacity);
     // counters + tile_count are adjacent: one memset
     D3GA_HIP(zero_async(bin.counters, 256 + align256(4 * tiles), s));
+    if (wnd) hipLaunchKernelGGL(window_table_kernel, dim3((views + 63) / 64), dim3(64), 0, s, campos, views, win_table(binning, tiles, d_capacity));
     if (prm->P == 0) return D3GA_OK;          // empty scene: every per-Gaussian tensor is empty (NULL)
     if ((shs != nullptr) == (colors_precomp != nullptr)) return D3GA_E_CONFIG;
     const bool pva = views > 1 && prm->per_view_appearance;   // (k,P) opacities and (k,P,3) colours: precomputed colours only (d3ga.h)
@@ -809,7 +842,7 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? (kShHalfLdsBytes > win ? kShHalfLdsBytes : win) : win;
     // (the kernels' `staged` condition, on the host: with it and a backward to follow the forward leaves GeomBuf::dcol)
     const bool want_j = D3GA_PRE_DCOL && shs && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48 && !prm->forward_only;
-    const int cam_stride = prm->tanfovx > 0.f ? 3 : 5;       // camera slots carry the two tangents behind the position
+    const int cam_stride = prm->tanfovx > 0.f ? 3 : (wnd ? D3GA_CAMERA_SLOT_WINDOWED_FLOATS : 5);   // camera slots carry the two tangents behind the position
     // a batch of views writes view v's records at v P + i of the batch's buffers: grouped launches below when the SH row can be
     // shared, else one launch per view (a streaming kernel at the copy rate gains nothing from a taller grid)
     const size_t pv = (views > 1 && prm->per_view_geometry) ? (size_t)prm->P : 0;      // records between the views' geometry (0: shared)
@@ -819,7 +852,7 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     // k cameras of ONE set of Gaussians with staged SH colours: groups of up to four views per pass (preprocess_views_kernel: the
     // 12 M-byte coefficient row, the mean and the covariance are read once per group instead of once per view).  SH only, so never
     // with per-view appearance (refused above): the group kernel reads one opacity per Gaussian for all its views
-    const bool grouped = views > 1 && shs && !pva && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
+    const bool grouped = views > 1 && shs && !pva && !wnd && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
 #define D3GA_PRE_VIEWS(KVV)                                                                                                        \
     do {                                                                                                                           \
         ViewCams<KVV> vc;                                                                                                          \
@@ -849,7 +882,13 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
         const float *cv = cov3D_precomp ? cov3D_precomp + 6 * pv * v : nullptr;
         const float *ov = opacities + pa * v, *colv = colors_precomp ? colors_precomp + 3 * pa * v : nullptr;      // (per-view appearance)
         int32_t *rv = radii + (size_t)prm->P * v;
-        if (want_j)
+        if (wnd && want_j)
+            hipLaunchKernelGGL((preprocess_kernel<true, true>), grid, block, lds, s, *prm, mv, shs,
+                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
+        else if (wnd)
+            hipLaunchKernelGGL((preprocess_kernel<false, true>), grid, block, lds, s, *prm, mv, shs,
+                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
+        else if (want_j)
             hipLaunchKernelGGL(preprocess_kernel<true>, grid, block, lds, s, *prm, mv, shs,
                                colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
         else
@@ -863,7 +902,7 @@ extern "C" int d3ga_raster_recolor(const d3ga_raster_params *prm, const float *m
                                    const float *colors_precomp, const float *campos, const void *geom_src,
                                    void *geom_dst, d3ga_stream_t stream) {
     D3GA_TRY(validate(prm));
-    if (n_views_of(prm) > 1) return D3GA_E_CONFIG;
+    if (n_views_of(prm) > 1 || is_windowed(prm)) return D3GA_E_CONFIG;
     if (prm->P == 0) return D3GA_OK;
     if (!geom_src || !geom_dst || geom_src == geom_dst) return D3GA_E_NULL;
     if ((shs != nullptr) == (colors_precomp != nullptr)) return D3GA_E_CONFIG;
@@ -904,13 +943,19 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
     if (pva && shs) return D3GA_E_CONFIG;
     const GeomBuf g = carve_geom(const_cast<void *>(geom), (int64_t)prm->P * views);
     const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? kShLdsBytes : 0;
+    const bool win = is_windowed(prm);
     if (views == 1) {
-        hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D,
-                           shs, scales, rotations, viewmatrix, projmatrix, campos, g, acc, dL_dmeans3D, dL_dmeans2D,
-                           dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, cov3D_precomp, 0);
+        if (win)
+            hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D,
+                               shs, scales, rotations, viewmatrix, projmatrix, campos, g, acc, dL_dmeans3D, dL_dmeans2D,
+                               dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, cov3D_precomp, 0);
+        else
+            hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D,
+                               shs, scales, rotations, viewmatrix, projmatrix, campos, g, acc, dL_dmeans3D, dL_dmeans2D,
+                               dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, cov3D_precomp, 0);
         return check_launch(s, prm->debug);
     }
-    const int cam_stride = prm->tanfovx > 0.f ? 3 : 5;
+    const int cam_stride = prm->tanfovx > 0.f ? 3 : (win ? D3GA_CAMERA_SLOT_WINDOWED_FLOATS : 5);
     // k views that SHARE their geometry: one pass over the Gaussians walks the views (preprocess_bwd_views_kernel), up to eight per
     // launch -- when the SH gradient is wanted as the (P,M,3) block (not as the factors of the camera-sharded exchange) and, for SH
     // colours, the forward left its direction Jacobian
@@ -927,7 +972,7 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
                     vc.vm[q] = viewmatrix + 16 * (size_t)v; vc.pm[q] = projmatrix + 16 * (size_t)v; vc.cp[q] = campos + (size_t)cam_stride * v;
                 }
                 const size_t o = (size_t)prm->P * v0, og = pvl * v0, oa = pva ? o : 0;      // oa: the group's first per-view opacity / colour gradient
-                hipLaunchKernelGGL(preprocess_bwd_views_kernel, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), shs ? kShLdsBytes : 0, s, *prm, kv,
+                hipLaunchKernelGGL(win ? preprocess_bwd_views_kernel<true> : preprocess_bwd_views_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), shs ? kShLdsBytes : 0, s, *prm, kv,
                                    means3D + 3 * og, shs != nullptr, scales ? scales + 3 * og : nullptr, rotations ? rotations + 4 * og : nullptr,
                                    cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, vc, geom_view(g, prm->P, v0), acc + D3GA_ACC_STRIDE * o,
                                    dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity ? dL_dopacity + oa : nullptr, dL_dsh,
@@ -945,7 +990,7 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
     const size_t fr = prm->factor_rows > 0 ? (size_t)prm->factor_rows : (size_t)prm->P;      // rows between the views' SH factors
     for (int v = 0; v < views; ++v) {
         const size_t o = (size_t)prm->P * v, og = pv * v;
-        hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D + 3 * og,
+        hipLaunchKernelGGL(win ? preprocess_bwd_kernel<true> : preprocess_bwd_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D + 3 * og,
                            shs, scales ? scales + 3 * og : nullptr, rotations ? rotations + 4 * og : nullptr, viewmatrix + 16 * (size_t)v,
                            projmatrix + 16 * (size_t)v, campos + (size_t)cam_stride * v, geom_view(g, prm->P, v), acc + D3GA_ACC_STRIDE * o,
                            dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity, (float *)nullptr,

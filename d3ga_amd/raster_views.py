@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import RasterParams, check, dptr, require_cuda, stream_handle
-from .cameras import Camera
+from .cameras import Camera, crop_window
 from . import rasterizer as _R
 
 
@@ -23,16 +23,23 @@ class CameraBatch:
     """k cameras of one raster size in ONE device buffer: view matrices (k,16) | full projections (k,16) | centres + tangents
     (k,5).  The kernels read tan(FoV/2) per view from the buffer (the camera-slot convention of include/d3ga.h: the settings
     carry tanfovx = 0), so the cameras of a batch may differ in everything but the raster size, and a captured step is replayed
-    with other cameras after `set()` -- one asynchronous H2D copy."""
+    with other cameras after `set()` -- one asynchronous H2D copy.
 
-    def __init__(self, n_views, width, height, device="cuda"):
+    windowed=True: width x height is the CROP WINDOW every view pastes to (lib/batch.py:186-198, renderer.py:36-47), and the views
+    may differ in raster size and principal point: the centre rows grow to (k,9) with (w, h, ox, oy) behind the tangents and the
+    kernels rasterize each view's window directly (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED)."""
+
+    def __init__(self, n_views, width, height, device="cuda", windowed=False):
         self.n_views, self.image_width, self.image_height = int(n_views), int(width), int(height)
+        self.windowed = bool(windowed)
         k = self.n_views
-        self.buffer = torch.zeros(37 * k, dtype=torch.float32, device=torch.device(device))
+        c = 9 if self.windowed else 5
+        self._c = c
+        self.buffer = torch.zeros((32 + c) * k, dtype=torch.float32, device=torch.device(device))
         self.viewmatrices = self.buffer[:16 * k].view(k, 16)
         self.projmatrices = self.buffer[16 * k:32 * k].view(k, 16)
-        self.campos = self.buffer[32 * k:].view(k, 5)
-        self._host = torch.zeros(37 * k, dtype=torch.float32)
+        self.campos = self.buffer[32 * k:].view(k, c)
+        self._host = torch.zeros((32 + c) * k, dtype=torch.float32)
         if self.buffer.is_cuda:
             self._host = self._host.pin_memory()
         self._host_np = self._host.numpy()
@@ -46,15 +53,25 @@ class CameraBatch:
         if self._event is not None:
             self._event.synchronize()                 # the copy that last read the staging buffer has run
         h = self._host_np
+        rows = []
         for v, b in enumerate(batches):
-            if int(b["width"]) != self.image_width or int(b["height"]) != self.image_height:
+            if self.windowed:
+                w, hh, ox, oy, W, H = crop_window(b)
+                if (W, H) != (self.image_width, self.image_height):
+                    raise ValueError(f"CameraBatch is a {self.image_width}x{self.image_height} window; view {v}'s crop pastes to {W}x{H}")
+                rows.append((w, hh, ox, oy))
+            elif int(b["width"]) != self.image_width or int(b["height"]) != self.image_height:
                 raise ValueError(f"CameraBatch is {self.image_width}x{self.image_height}; view {v} is {b['width']}x{b['height']}")
+        c = self._c
+        for v, b in enumerate(batches):
             m = Camera.pack_host_cached(b)        # view (16) | projection (16) | full (16) | centre (3) | tan(FoVx/2), tan(FoVy/2)
             h[16 * v:16 * v + 16] = m[0:16]
             h[16 * k + 16 * v:16 * k + 16 * v + 16] = m[32:48]
-            o = 32 * k + 5 * v
+            o = 32 * k + c * v
             h[o:o + 3] = m[48:51]
             h[o + 3:o + 5] = m[51:53]
+            if self.windowed:
+                h[o + 5:o + 9] = rows[v]
         self.buffer.copy_(self._host, non_blocking=True)
         if self.buffer.is_cuda:
             self._event = torch.cuda.Event()
@@ -62,8 +79,11 @@ class CameraBatch:
         return self
 
 
-def _scratch_views(P, W, H, k, cap, dev, fwd_only):
+def _scratch_views(P, W, H, k, cap, dev, fwd_only, windowed=False):
     sizes = (ctypes.c_int64 * 3)()
+    if windowed:
+        check(_lib.lib().d3ga_raster_scratch_bytes_window(P, W, H, k, cap, int(fwd_only), sizes), "d3ga_raster_scratch_bytes_window")
+        return [torch.empty(int(n), dtype=torch.uint8, device=dev) for n in sizes]
     check(_lib.lib().d3ga_raster_scratch_bytes_views(P, W, H, k, cap, int(fwd_only), sizes), "d3ga_raster_scratch_bytes_views")
     return [torch.empty(int(n), dtype=torch.uint8, device=dev) for n in sizes]
 
@@ -83,6 +103,10 @@ class _RasterizeViews(torch.autograd.Function):
                 (scales is not None or rotations is not None) and cov3Ds_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         k, W, H = cams.n_views, cams.image_width, cams.image_height
+        windowed = getattr(cams, "windowed", False)
+        if windowed and grad_sync is not None:
+            raise ValueError("rasterize_gaussians_views: grad_sync (camera-sharded exchange) is not available with windowed cameras "
+                             "(CameraBatch(windowed=True)); render the windows without it")
         # a batch of FRAMES: every view brings its own geometry (k,P,.) -- the avatar deformed per pose -- and shares the appearance
         per_view = means3D.dim() == 3
         P = means3D.shape[-2]
@@ -106,7 +130,8 @@ class _RasterizeViews(torch.autograd.Function):
             colors2, bg2 = f32(colors2.detach()), f32(bg2)
             if tuple(colors2.shape) != (P, 3) or bg2.numel() != 3:
                 raise ValueError("rasterize_gaussians_views: colors2 is (P,3) and bg2 (3,), shared by the views")
-        prm = RasterParams(P=P, M=M, sh_degree=int(sh_degree), W=W, H=H, tanfovx=0.0, tanfovy=0.0,
+        marker = _lib.CAMERA_SLOT_WINDOWED if windowed else 0.0         # camera slots: tangents (and windows) from the device rows
+        prm = RasterParams(P=P, M=M, sh_degree=int(sh_degree), W=W, H=H, tanfovx=marker, tanfovy=marker,
                            scale_modifier=float(scale_modifier), antialiasing=int(bool(antialiasing)), prefiltered=0, debug=0,
                            opacity_activation=_R._ACTIVATIONS[opacity_activation], forward_only=int(fwd_only), n_views=k,
                            per_view_geometry=int(per_view), per_view_appearance=int(pva), per_view_background=int(pvb))
@@ -124,7 +149,7 @@ class _RasterizeViews(torch.autograd.Function):
         static = _R._policy["mode"] == "static"
         cap = _R._policy["static"] if static else max(k * _R._hwm.get(dev.index, 0), k * (4 * P + 1024))
         while True:
-            geom, binning, img = _scratch_views(P, W, H, k, cap, dev, fwd_only)
+            geom, binning, img = _scratch_views(P, W, H, k, cap, dev, fwd_only, windowed)
             tm = _R.stage_timer
             tm.stage("preprocess", lambda: check(L.d3ga_raster_preprocess(
                 pp, dptr(means3D), dptr(sh), dptr(colors_precomp), dptr(opacities), dptr(scales), dptr(rotations),
@@ -132,7 +157,7 @@ class _RasterizeViews(torch.autograd.Function):
                 cap, dptr(radii), st), "d3ga_raster_preprocess"))
             tm.stage("bin_sort", lambda: check(L.d3ga_raster_bin_sort(pp, dptr(geom), dptr(binning), cap, st), "d3ga_raster_bin_sort"))
             if tgt is not None and P > 0:
-                ws = torch.empty(4 * k * ((W + 15) // 16) * ((H + 15) // 16), dtype=torch.float32, device=dev)
+                ws = torch.empty(4 * k * ((W + 15) // 16 + windowed) * ((H + 15) // 16 + windowed), dtype=torch.float32, device=dev)
                 tm.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd_l1(
                     pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(colors), None, dptr(tgt), None, dptr(loss), dptr(ws), st),
                     "d3ga_raster_composite_fwd_l1"))

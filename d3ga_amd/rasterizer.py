@@ -170,17 +170,22 @@ _scratch_sizes = {}
 _prm_cache = {}          # parameter blocks by value (never mutated: the backward copies one when it needs another acc_self_clearing)
 
 
-def _scratch(P, W, H, cap, device, forward_only=False, binning=True):
+def _scratch(P, W, H, cap, device, forward_only=False, binning=True, windowed=False):
     """(geom, binning, img) byte tensors.  forward_only: the img buffer without the per-block lists of the backward
     (128 B per duplicate of capacity -- several hundred MB per render at a few million duplicates); binning=False: None
-    for the binning buffer (a geometry-cache hit shares the first pass's)."""
-    key = (P, W, H, cap, bool(forward_only))
+    for the binning buffer (a geometry-cache hit shares the first pass's).  windowed: a W x H window of a windowed camera slot
+    (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED -- the window's tile grid and table)."""
+    key = (P, W, H, cap, bool(forward_only), bool(windowed))
     sz = _scratch_sizes.get(key)
     if sz is None:                                   # (two ctypes calls per render otherwise: the sizes of a training loop never change)
         sizes = (ctypes.c_int64 * 3)()
         L = _lib.lib()
-        check(L.d3ga_raster_scratch_bytes(P, W, H, cap, sizes), "d3ga_raster_scratch_bytes")
-        img_bytes = int(L.d3ga_raster_img_bytes(W, H, cap, 1)) if forward_only else int(sizes[2])
+        if windowed:
+            check(L.d3ga_raster_scratch_bytes_window(P, W, H, 1, cap, int(bool(forward_only)), sizes), "d3ga_raster_scratch_bytes_window")
+            img_bytes = int(sizes[2])
+        else:
+            check(L.d3ga_raster_scratch_bytes(P, W, H, cap, sizes), "d3ga_raster_scratch_bytes")
+            img_bytes = int(L.d3ga_raster_img_bytes(W, H, cap, 1)) if forward_only else int(sizes[2])
         if len(_scratch_sizes) > 64:
             _scratch_sizes.clear()
         sz = _scratch_sizes[key] = (int(sizes[0]), int(sizes[1]), img_bytes)
@@ -275,7 +280,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         H, W = int(s.image_height), int(s.image_width)
         M = sh.shape[1] if sh is not None else 0
         tfx, tfy = float(s.tanfovx), float(s.tanfovy)
-        if not (tfx > 0.0 and tfy > 0.0):
+        # windowed camera slot (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): W x H is the crop window, campos carries (w, h, ox, oy)
+        windowed = tfx == _lib.CAMERA_SLOT_WINDOWED and tfy == _lib.CAMERA_SLOT_WINDOWED and campos.numel() >= 9
+        if not (tfx > 0.0 and tfy > 0.0) and not windowed:
             # tanfovx <= 0 is the in-band marker of a camera slot (cameras.CameraSlot): the kernels then read both tangents
             # from campos[3], campos[4].  Anything else non-positive (or NaN) would make them read past a 3-float campos.
             if not (tfx == 0.0 and tfy == 0.0 and campos.numel() >= 5):
@@ -311,7 +318,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         def composite_fwd_single(L, pp, geom, binning, cap, img, st):
             if l1_in_fwd:
-                ws = torch.empty(4 * ((W + 15) // 16) * ((H + 15) // 16), dtype=torch.float32, device=dev)
+                ws = torch.empty(4 * ((W + 15) // 16 + windowed) * ((H + 15) // 16 + windowed), dtype=torch.float32, device=dev)
                 check(L.d3ga_raster_composite_fwd_l1(pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(color),
                                                      dptr(invdepth), dptr(None if l1_cell is not None else l1_t), dptr(l1_cell),
                                                      dptr(loss), dptr(ws), st), "d3ga_raster_composite_fwd_l1")
@@ -326,7 +333,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         cap = _policy["static"] if static else max(_hwm.get(dev.index, 0), 4 * P + 1024)
         geo_inputs = (means3D, opacities, scales, rotations, cov3Ds_precomp, view, proj)
         color2 = torch.empty((3, H, W), dtype=torch.float32, device=dev) if dual else None
-        use_cache = _reuse["enabled"] and P > 0 and not dual and not torch.cuda.is_current_stream_capturing()
+        use_cache = _reuse["enabled"] and P > 0 and not dual and not windowed and not torch.cuda.is_current_stream_capturing()
         key = _geometry_key(prm, ("static", cap) if static else "auto", geo_inputs) if use_cache else None
         hit = _geom_cache.get(dev.index) if use_cache else None
         if hit is not None and hit["key"] == key:
@@ -341,7 +348,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if _capture_log is not None:
                 _capture_log.append((binning, cap))
         while hit is None or hit["key"] != key:
-            geom, binning, img = _scratch(P, W, H, cap, dev, fwd_only)
+            geom, binning, img = _scratch(P, W, H, cap, dev, fwd_only, windowed=windowed)
             if stage_timer.enabled or dual or l1_in_fwd:
                 st, pp = stream_handle(), ctypes.byref(prm)
                 stage_timer.stage("preprocess", lambda: check(L.d3ga_raster_preprocess(

@@ -3,7 +3,7 @@ solid_bg=True, fast=False, detach=[]) -> {"render": (3,H',W')}` (renderer.py:69-
 """
 import torch
 
-from .cameras import batch_to_camera
+from .cameras import CAMERA_SLOT_WINDOWED, batch_to_camera, crop_window, is_cropped, window_camera
 from .rasterizer import GaussianRasterizationSettings, rasterize_gaussians, rasterize_gaussians_l1, rasterize_gaussians_pair
 
 bg_colors = {"white": (1.0, 1.0, 1.0), "black": (0.0, 0.0, 0.0)}
@@ -34,27 +34,34 @@ def paste(img, crop):
     return img
 
 
-def render_pair(batch, pkg, bg_color, colors2, bg_color2, grad_sync=None):
+def render_pair(batch, pkg, bg_color, colors2, bg_color2, grad_sync=None, crop_window=False):
     """The two renders of the reference's training step (models/trainer.py:102-110: `render(frame, pkg, bg)` and
     `render(frame, pkg, colors_precomp=pkg["silhouette_rgb"], bg_color=zeros)`) from ONE pass over the same geometry:
     -> {"render": (3,H',W'), "render2": (3,H',W')}.  Same images and the same summed gradients as the two calls (colors2
-    is treated as constant, as the reference's silhouette colours are); use the two calls when `detach` differs."""
-    out = render(batch, pkg, bg_color, grad_sync=grad_sync, _pair=(colors2, bg_color2))
+    is treated as constant, as the reference's silhouette colours are); use the two calls when `detach` differs.  crop_window: as for
+    `render`."""
+    out = render(batch, pkg, bg_color, grad_sync=grad_sync, _pair=(colors2, bg_color2), crop_window=crop_window)
     return out
 
 
-def render_l1(batch, pkg, bg_color, target, grad_sync=None):
+def render_l1(batch, pkg, bg_color, target, grad_sync=None, crop_window=False):
     """`render(batch, pkg, bg_color)` and `l1_loss(render, target)` (utils/loss_utils.py:29, train.py:190) from one operator:
     -> {"render": (3,H',W'), "l1": scalar}.  Same image, same loss, same gradients as the two calls; the loss gradient is
     formed inside the compositing backward instead of travelling through a (3,H,W) gradient image.  `target`: a tensor of
     the render's shape or a `graph.TensorSlot`.  With an off-centre crop (lib/batch.py:186-198: the loss lives on the cropped
-    window, not on the raster) the two calls are made instead."""
-    crop = batch["crop"]
-    if int(crop[4]) != int(batch["width"]) or int(crop[5]) != int(batch["height"]):
+    window, not on the raster) the two calls are made instead -- unless crop_window=True (see `render`): the window is then rendered
+    directly and the loss stays fused (one operator)."""
+    windowed = crop_window or _windowed_slot(batch)
+    if is_cropped(batch) and not windowed:
         from .losses import l1_loss
         img = render(batch, pkg, bg_color, grad_sync=grad_sync)["render"]
         return {"render": img, "l1": l1_loss(img, target)}
-    return render(batch, pkg, bg_color, grad_sync=grad_sync, _l1=target)
+    return render(batch, pkg, bg_color, grad_sync=grad_sync, _l1=target, crop_window=crop_window)
+
+
+def _windowed_slot(batch):
+    slot = batch.get("camera_slot")
+    return slot is not None and getattr(slot, "windowed", False)
 
 
 def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=None, bg_color2=None, grad_sync=None):
@@ -69,8 +76,11 @@ def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=Non
     configuration, use_shs false: colour and opacity evaluated per frame) are stacked to (k,P,.) and rendered per view.  One package
     seen from k cameras may carry `rgb` (k,P,3) and `opacities` (k,P,1) itself (ColorField evaluated once per camera).  Every image
     equals `render(batch_v, pkg_v, bg_color_v)["render"]`, the gradients equal the sum over the k calls (d3ga_amd/raster_views.py).
-    The views share the raster size and must not be cropped (lib/batch.py:186-198: centred principal point).  cameras: a `raster_views.CameraBatch` to reuse (a captured step keeps one and
-    calls `cameras.set(batches)` before every replay); batches may then be None."""
+    Views with off-centre crops or different raster sizes (lib/batch.py:186-198: every camera's own padded raster) are rendered
+    through their crop windows (CameraBatch(windowed=True), include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): every image is then
+    `paste(render(batch_v, ...)["render"], crop_v)`, (k,3,H,W) with (W,H) = crop[4], crop[5], which must be the same for all views;
+    targets are (k,3,H,W) windows.  Centred views of one raster size take the full-raster path.  cameras: a `raster_views.CameraBatch`
+    to reuse (a captured step keeps one and calls `cameras.set(batches)` before every replay); batches may then be None."""
     from .raster_views import CameraBatch, rasterize_gaussians_views
     frames = pkg if isinstance(pkg, (list, tuple)) else None
     if frames is not None:
@@ -92,11 +102,16 @@ def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=Non
                    **look)
     means3D = pkg["means3D"]
     if cameras is None:
-        for b in batches:
-            c = b["crop"]
-            if int(c[4]) != int(b["width"]) or int(c[5]) != int(b["height"]):
-                raise ValueError("render_views: a view with an off-centre crop -- use render() per view")
-        cameras = CameraBatch(len(batches), int(batches[0]["width"]), int(batches[0]["height"]), device=means3D.device).set(batches)
+        sizes = {(int(b["width"]), int(b["height"])) for b in batches}
+        if len(sizes) == 1 and not any(is_cropped(b) for b in batches):
+            cameras = CameraBatch(len(batches), int(batches[0]["width"]), int(batches[0]["height"]), device=means3D.device).set(batches)
+        else:                        # cropped / mixed raster sizes: every view's crop window (all must paste to one W x H)
+            W, H = crop_window(batches[0])[4:]
+            for v, b in enumerate(batches):
+                if crop_window(b)[4:] != (W, H):
+                    raise ValueError(f"render_views: view {v}'s crop pastes to {crop_window(b)[4]}x{crop_window(b)[5]}, view 0's to {W}x{H} "
+                                     "-- the views of a batch share one pasted image size")
+            cameras = CameraBatch(len(batches), W, H, device=means3D.device, windowed=True).set(batches)
     opacities, act = pkg.get("opacities"), None
     if opacities is None and pkg.get("opacity_logits") is not None:
         opacities, act = pkg["opacity_logits"], "sigmoid"
@@ -111,24 +126,41 @@ def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=Non
 
 
 def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_bg=True, fast=False, detach=[],
-           grad_sync=None, _pair=None, _l1=None):
+           grad_sync=None, _pair=None, _l1=None, crop_window=False):
+    """crop_window (extension): with an off-centre crop (lib/batch.py:186-198) rasterize the pasted W x H window directly
+    (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED) instead of the padded w x h raster followed by `paste` -- the same image bit for
+    bit, the same radii, the same gradients up to the summation order of float atomics, without the padding pixels and the
+    paste's copies.  A windowed `cameras.CameraSlot` in the batch always renders its window."""
     means3D = pkg["means3D"]
     # a cameras.CameraSlot in the batch: the camera is read from its static device buffer (graph-capturable step that
     # follows the trainer's camera-per-step, d3ga_amd/graph.py)
-    cam = batch.get("camera_slot") or batch_to_camera(batch, device=means3D.device)
+    slot = batch.get("camera_slot")
     crop = batch["crop"]
+    windowed = (slot is not None and getattr(slot, "windowed", False)) or (crop_window and slot is None and is_cropped(batch))
+    if windowed and grad_sync is not None:
+        raise ValueError("render: grad_sync is not available with crop-window rendering")
+    if windowed and slot is None:
+        W, H = int(crop[4]), int(crop[5])
+        mats, row = window_camera(batch, device=means3D.device)
+        view, full, campos, tfx = mats[0:16].view(4, 4), mats[32:48].view(4, 4), row, CAMERA_SLOT_WINDOWED
+    else:
+        cam = slot or batch_to_camera(batch, device=means3D.device)
+        W, H = (slot.image_width, slot.image_height) if windowed else (int(batch["width"]), int(batch["height"]))
+        view, full, campos, tfx = cam.world_view_transform, cam.full_proj_transform, cam.camera_center, cam.tanfovx
+    if windowed:
+        crop = None                       # the rasterizer's output IS the window
 
     settings = GaussianRasterizationSettings(
-        image_height=int(batch["height"]),
-        image_width=int(batch["width"]),
-        tanfovx=cam.tanfovx,
-        tanfovy=cam.tanfovy,
+        image_height=H,
+        image_width=W,
+        tanfovx=tfx,
+        tanfovy=tfx if windowed else cam.tanfovy,
         bg=bg_color,
         scale_modifier=1.0,
-        viewmatrix=cam.world_view_transform,
-        projmatrix=cam.full_proj_transform,
+        viewmatrix=view,
+        projmatrix=full,
         sh_degree=pkg["sh_degree"] if "sh_degree" in pkg else 0,
-        campos=cam.camera_center,
+        campos=campos,
         prefiltered=False,
         debug=False,
         antialiasing=False,
@@ -165,6 +197,8 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
         img, _radii, _invd, img2 = rasterize_gaussians_pair(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                             cov3D_precomp, settings, _pair[0], _pair[1], grad_sync, act,
                                                             want_invdepth=False)
+        if crop is None:
+            return {"render": img, "render2": img2}
         return {"render": paste(img, crop), "render2": paste(img2, crop)}
     if _l1 is not None:
         img, _radii, _invd, loss = rasterize_gaussians_l1(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
@@ -179,4 +213,4 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
                                    grad_sync, act, want_invdepth=False)[0]     # only [0] of the rasterizer's outputs is used here (renderer.py:141)
     if measure_time:
         torch.cuda.synchronize()
-    return {"render": paste(rendered, crop)}
+    return {"render": rendered if crop is None else paste(rendered, crop)}

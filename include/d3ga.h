@@ -162,7 +162,8 @@ typedef struct d3ga_raster_params {
     int32_t W, H;        /* raster size (renderer.py:80-81) */
     float tanfovx, tanfovy; /* tan(FoV/2) (renderer.py:76-77).  tanfovx <= 0: CAMERA SLOT -- the kernels read both from device
                              * memory, campos[3] and campos[4] (campos is then 5 floats), so that a captured hipGraph can be
-                             * replayed with another camera by rewriting one device buffer (d3ga_amd/cameras.py:CameraSlot) */
+                             * replayed with another camera by rewriting one device buffer (d3ga_amd/cameras.py:CameraSlot).
+                             * tanfovx == D3GA_CAMERA_SLOT_WINDOWED: WINDOWED camera slot, see below. */
     float scale_modifier;
     int32_t antialiasing; /* branch dr_aa [UPSTREAM-RECALL]: opacity x sqrt(max(2.5e-5, det(cov2D) / det(cov2D + 0.3 I))); D3GA passes 0 (renderer.py:92) */
     int32_t prefiltered;  /* accepted, ignored (renderer.py:90) */
@@ -223,6 +224,25 @@ typedef struct d3ga_raster_params {
 } d3ga_raster_params;
 #define D3GA_OPACITY_SIGMOID 1
 
+/* Windowed camera slot (crop-window rasterization; lib/batch.py:186-198 of the reference renders every frame at a padded raster
+ * size w x h that centres the principal point, renderer.py:36-47 then pastes the W x H window back out of it).
+ * d3ga_raster_params::tanfovx == D3GA_CAMERA_SLOT_WINDOWED selects it.  campos then holds ONE ROW OF 9 FLOATS PER VIEW (device memory):
+ *     centre (3) | tan(FoVx/2) | tan(FoVy/2) | w | h | ox | oy          (w, h, ox, oy: exact float integers)
+ * (w, h) is the view's full raster size, (ox, oy) the window's offset in it (paste(): ox = 0 if left_w > right_w else w - W, oy
+ * likewise); d3ga_raster_params::W, ::H are the WINDOW size, shared by the views of a batch, and every output image is W x H: the
+ * pixel (x, y) of the full raster lands at ((y - oy) W + (x - ox)).  Every floating-point quantity stays in full-raster pixel
+ * coordinates -- projection with (w, h), the tile rectangle clamped to the raster's tiles -- so images, radii and the per-Gaussian
+ * records are bit-identical to a full-raster render followed by the paste; only tile indices and output addresses are shifted.
+ * Tile grid of a window: aligned to the raster's 16-pixel grid, first tile (ox / 16, oy / 16), a fixed tiles_x(W) + 1 by
+ * tiles_y(H) + 1 tiles per view (covers any offset; the tiles a view does not need stay empty); view v's tile (tx, ty) is tile
+ * (v gyw + ty) gxw + tx.  A Gaussian whose rectangle misses the window is culled in that view's records (its radius stays the
+ * full-raster one).  The binning buffer is then sized by d3ga_raster_scratch_bytes_window: behind the sections of
+ * d3ga_raster_binning_layout it holds the window table (one int32 x4 row per view: ox, oy, w, h) that d3ga_raster_preprocess writes
+ * from campos and the compositing kernels read.  Because the record lives in device memory, a captured graph is replayed with any
+ * camera whose crop pastes to W x H.  Not available windowed (D3GA_E_CONFIG): d3ga_raster_recolor. */
+#define D3GA_CAMERA_SLOT_WINDOWED (-1.0f)
+#define D3GA_CAMERA_SLOT_WINDOWED_FLOATS 9
+
 /* Byte sizes of the three caller-owned scratch buffers (the analogue of upstream's geomBuffer /
  * binningBuffer / imgBuffer).  d_capacity = capacity in (tile,Gaussian) duplicates of the binning lists.
  * sizes[0]=geom, sizes[1]=binning, sizes[2]=img.  Buffers must be 256-byte aligned. */
@@ -233,6 +253,13 @@ int64_t d3ga_raster_img_bytes(int32_t W, int32_t H, int64_t d_capacity, int32_t 
  * sizes[2] is the img buffer with (forward_only == 0) or without the per-block lists. */
 int d3ga_raster_scratch_bytes_views(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t d_capacity, int32_t forward_only,
                                     int64_t sizes[3]);
+
+/* The same for WINDOWED camera slots (see D3GA_CAMERA_SLOT_WINDOWED): W, H = the window size, the tile grid (tiles_x(W) + 1) x
+ * (tiles_y(H) + 1) per view, the binning buffer with the window table behind its sections. */
+int d3ga_raster_scratch_bytes_window(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t d_capacity, int32_t forward_only,
+                                     int64_t sizes[3]);
+/* offsets[0..5] as d3ga_raster_binning_layout for the window grid of a W x H window, offsets[6] the window table (n_views x int32 x4). */
+int d3ga_raster_binning_layout_window(int32_t W, int32_t H, int32_t n_views, int64_t d_capacity, int64_t offsets[7]);
 
 /* Byte offsets of the sections of the binning buffer, for inspection/tests:
  * offsets[0] counters (8 x u32), [1] tile_count (tiles x u32), [2] tile_start (tiles+1 x u32, exclusive prefix),
