@@ -37,8 +37,28 @@ class RasterParams(ctypes.Structure):
                 ("factor_rows", ctypes.c_int32), ("per_view_appearance", ctypes.c_int32), ("per_view_background", ctypes.c_int32)]
 
 
+BODY_MAX_JOINTS = 64     # D3GA_BODY_MAX_JOINTS (include/d3ga.h)
+BODY_MAX_SHAPE = 32      # D3GA_BODY_MAX_SHAPE: shape + expression coefficients
+BODY_LD_ALIGN = 2048     # D3GA_BODY_LD_ALIGN: row stride alignment of the blend directions, in floats
+
+
+def body_saved_floats(J):
+    """D3GA_BODY_SAVED_FLOATS(J): floats per frame of the body model forward's `saved` buffer."""
+    return 27 * J + 16
+
+
+class BodyModel(ctypes.Structure):
+    """struct d3ga_body_model (include/d3ga.h): sizes and device pointers of a prepared SMPL / SMPL-X model."""
+    _fields_ = [("V", ctypes.c_int32), ("J", ctypes.c_int32), ("n_shape", ctypes.c_int32), ("n_expr", ctypes.c_int32),
+                ("n_hand_pca", ctypes.c_int32), ("ld", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("v_template", "dirs", "w_ptr", "w_joint", "w_val", "wt_ptr", "wt_vert", "wt_val",
+                                               "J0", "Jdirs", "parents", "level_ptr", "level_joint", "child_ptr", "child_joint",
+                                               "hand_comps", "hand_mean")]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _prm = ctypes.POINTER(RasterParams)
+_bm = ctypes.POINTER(BodyModel)
 
 # name -> (argtypes, restype); the trailing _vp of every launch entry is the hipStream_t
 _SIGNATURES = {
@@ -111,6 +131,9 @@ _SIGNATURES = {
     "d3ga_ssim_bwd": ([ctypes.c_int32] * 3 + [_vp] * 7 + [_vp], _i),
     "d3ga_ssim_l1_fwd": ([ctypes.c_int32] * 3 + [_vp] * 7 + [_vp], _i),
     "d3ga_ssim_l1_bwd": ([ctypes.c_int32] * 3 + [_vp] * 8 + [_vp], _i),
+    "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),
+    "d3ga_body_model_fwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 10 + [_vp, _i64, _vp], _i),
+    "d3ga_body_model_bwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 12 + [_vp, _i64, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

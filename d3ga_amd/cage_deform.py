@@ -403,19 +403,6 @@ def batch_rodrigues(rot_vecs, epsilon=1e-8):
     return eye + s * K + (1.0 - c) * torch.bmm(K, K)
 
 
-class SMPLlayer(torch.nn.Module):
-    """Import-compatible placeholder for `tetra_sampler.body_model.SMPLlayer` (lib/smplman.py:9,68-74).
-
-    The SMPL-X body model needs the licensed SMPL-X asset files (`config.data.smplx_model`, the joint regressor) and is
-    OUT OF SCOPE here: the import succeeds so that the reference's modules load unchanged, constructing
-    the layer fails with an error that says what is missing.  Everything downstream of the body model -- the per-vertex
-    blend `Smplman.deform` (lib/smplman.py:155-171) -- is `d3ga_amd.cage_deform.lbs_cage` and takes the joint transforms
-    any SMPL-X implementation produces."""
-
-    def __init__(self, model_path=None, model_type="smplx", gender="neutral", use_joints=True, regressor_path=None, **kw):
-        super().__init__()
-        raise NotImplementedError(
-            "tetra_sampler.body_model.SMPLlayer is not provided by d3ga_amd: it requires the licensed SMPL-X model files "
-            f"(model_path={model_path!r}, regressor_path={regressor_path!r}) and the un-vendored tetra-sampler package "
-            "(github.com/Zielon/sampler).  Install that package for the body model; d3ga_amd replaces the deform / "
-            "rasterize path only (lbs_cage takes the joint transforms A and blend offsets any SMPL-X layer returns).")
+# `tetra_sampler.body_model.SMPLlayer` (lib/smplman.py:9,68-74): the SMPL-X body model on the HIP kernels of
+# csrc/body_model.hip.  Kept importable from here for callers of the earlier placeholder.
+from .body_model import SMPLlayer  # noqa: E402,F401

@@ -230,3 +230,84 @@ def make_scene(wl, seed=17):
         "joint_mats": t(A), "joint_pos": t(joint_pos), "skin_idx": t(skin_idx), "skin_w": t(skin_w),
         "delta_node": t((rng.normal(size=canon.shape) * 0.002).astype(np.float32)),
     }
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Synthetic SMPL-X / SMPL-shaped model files (the real ones are licensed): the arrays and shapes of the published model
+# definition filled with seeded random values -- a tree with parents[i] < i, bones of ~0.1, vertices scattered about the
+# joints, up to 4 skinning joints per vertex, a J_regressor whose rows are convex combinations of 20 vertices.
+# ---------------------------------------------------------------------------------------------------------------------
+SMPLX_SIZES = {"smplx": (10475, 55), "smpl": (6890, 24)}
+
+
+def smpl_model_data(kind="smplx", seed=0, V=None, chain=False, n_shapedirs=None, max_depth=15):
+    """A dict of numpy arrays with the keys and shapes of an SMPL-X (`kind="smplx"`: J = 55, posedirs (V,3,486),
+    shapedirs (V,3,400), hand PCA) or SMPL (J = 24, shapedirs (V,3,10)) model file.  `chain`: a 55-deep single chain."""
+    rng = np.random.default_rng(seed)
+    V0, J = SMPLX_SIZES[kind]
+    V = V0 if V is None else V
+    S = n_shapedirs or (400 if kind == "smplx" else 10)
+    parents = np.zeros(J, np.int64)
+    depth = np.zeros(J, np.int64)
+    for i in range(1, J):
+        if chain:
+            p = i - 1
+        else:
+            cand = [k for k in range(i) if depth[k] < max_depth - 1]
+            p = int(cand[max(0, len(cand) - 1 - int(rng.integers(0, 6)))])
+        parents[i] = p
+        depth[i] = depth[p] + 1
+    bone = 0.12 if not chain else 0.04
+    jpos = np.zeros((J, 3))
+    for i in range(1, J):
+        d = rng.normal(size=3)
+        jpos[i] = jpos[parents[i]] + d / np.linalg.norm(d) * bone * rng.uniform(0.5, 1.5)
+    prim = rng.integers(0, J, size=V)
+    vt = jpos[prim] + rng.normal(size=(V, 3)) * 0.04
+    W = np.zeros((V, J))
+    for v in range(V):
+        j = prim[v]
+        near = [j] + ([int(parents[j])] if parents[j] >= 0 else []) + [int(x) for x in rng.integers(0, J, size=2)]
+        k = int(rng.integers(1, 5))
+        sel = list(dict.fromkeys(near))[:k]
+        w = rng.uniform(0.2, 1.0, size=len(sel))
+        W[v, sel] += w / w.sum()
+    Jreg = np.zeros((J, V))
+    for j in range(J):
+        pool = np.nonzero(prim == j)[0]
+        if len(pool) < 20:
+            pool = np.concatenate([pool, rng.integers(0, V, size=20 - len(pool))])
+        idx = rng.choice(pool, size=20, replace=False) if len(np.unique(pool)) >= 20 else rng.integers(0, V, size=20)
+        w = rng.uniform(0.1, 1.0, size=20)
+        np.add.at(Jreg[j], idx, w / w.sum())
+    kintree = np.stack([parents, np.arange(J)]).astype(np.int64)
+    kintree[0, 0] = 4294967295                     # the published files store -1 as uint32
+    data = {
+        "v_template": vt,
+        "shapedirs": rng.normal(size=(V, 3, S)) * 0.01,
+        "posedirs": (rng.normal(size=(V, 3, 9 * (J - 1))) * 0.002).astype(np.float32),
+        "J_regressor": Jreg,
+        "weights": W,
+        "kintree_table": kintree,
+        "f": rng.integers(0, V, size=(2 * V, 3)).astype(np.int64),
+    }
+    if kind == "smplx":
+        for side in ("l", "r"):
+            data["hands_components" + side] = rng.normal(size=(45, 45)) * 0.3
+            data["hands_mean" + side] = rng.normal(size=45) * 0.1
+    return data
+
+
+def write_smpl_model(path, data, sparse_regressor=False):
+    """Write model data as `.pkl` (latin-1 readable pickle; J_regressor as scipy.sparse.csc_matrix if asked) or `.npz`."""
+    import pickle
+    if path.endswith(".npz"):
+        np.savez(path, **data)
+        return path
+    d = dict(data)
+    if sparse_regressor:
+        import scipy.sparse
+        d["J_regressor"] = scipy.sparse.csc_matrix(d["J_regressor"])
+    with open(path, "wb") as f:
+        pickle.dump(d, f, protocol=2)
+    return path

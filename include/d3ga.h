@@ -151,6 +151,65 @@ int d3ga_fem_energy_bwd(int T, int V, const float *tetpoints, const int32_t *tet
                         const float *g_energy, float *g_tetpoints, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * B1  SMPL / SMPL-X body model (added without an ABI number change: new entry points only, no existing layout moves).
+ * Replaces the un-vendored `tetra_sampler.body_model.SMPLlayer` as built at
+ * lib/smplman.py:68-74 and called at lib/smplman.py:175 (`geom, T, A, bs = lbs_module(poses=, shapes=, Rh=, Th=,
+ * expression=)`).  The model is a set of device tensors prepared once on the host (d3ga_amd/body_model.py):
+ *   NS = n_shape + n_expr blend coefficients [beta; psi], NR = NS + 9 (J - 1) rows of blend directions.
+ *   dirs (NR, ld): rows 0..NS the shape / expression directions, rows NS + 9 (j - 1) + 3 a + c the pose direction of
+ *       (R_j - I)[a][c], each row the 3V offsets x0 y0 z0 x1 ..., zero beyond 3V; ld a multiple of D3GA_BODY_LD_ALIGN.
+ *   skin weights twice: CSR by vertex (w_ptr (V+1), w_joint, w_val) and by joint (wt_ptr (J+1), wt_vert ascending,
+ *       wt_val), every nonzero of the dense (V,J) matrix.
+ *   J0 (J,3) = J_regressor v_template, Jdirs (NS,J,3) = J_regressor . shape / expression directions.
+ *   parents (J), parents[0] = -1; the kinematic tree by level (level_ptr (n_levels + 1), level_joint (J): a joint's parent sits
+ *       in an earlier level) and by children (child_ptr (J+1), child_joint (J-1)).
+ *   hand_comps (2, n_hand_pca, 45) left then right, hand_mean (2,45): the compact SMPL-X pose layout only.
+ * Pose layouts (pose_width): 3J axis-angle rows in joint order, or for n_hand_pca > 0 and J = 55 the compact
+ *   [body 66 | left-hand PCA n | right-hand PCA n | jaw, left eye, right eye 9], hands = PCA . comps + mean.
+ * R_j = Rodrigues(theta_j) with t = |theta_j + 1e-8|; forward kinematics G_j = G_parent [R_j | J_j - J_parent];
+ *   A_j = [RG_j | tG_j - RG_j J_j] (not including Rh, Th); bs = dirs^T [beta; psi; pf] (= v_posed - v_template);
+ *   T_v = sum_j w_vj A_j; verts = R(Rh) T_v [v_template + bs; 1] + Th.
+ * fwd: poses (B, pose_width), shapes (B, n_shape), expr (B, n_expr) | NULL (zeros), Rh (B,3) | NULL, Th (B,3) | NULL
+ *   -> verts (B,V,3), T (B,V,4,4), A (B,J,4,4), bs (B,V,3), saved (B, D3GA_BODY_SAVED_FLOATS(J)): what the backward reads.
+ * bwd: saved, T and bs of the forward, upstream gradients g_verts (B,V,3), g_T (B,V,4,4), g_A (B,J,4,4), g_bs (B,V,3), each
+ *   NULL = zero -> g_poses (B, pose_width), g_shapes (B, n_shape), g_expr (B, n_expr), g_Rh (B,3), g_Th (B,3), each NULL =
+ *   not written.  The bottom rows of T and A are constants: their gradients are ignored.  Every reduction goes through
+ *   partial slabs summed in a fixed order (no atomics): two calls give bitwise-equal gradients.
+ * scratch: caller-owned device memory of at least d3ga_body_model_scratch_bytes (host query) for the pass; not kept
+ *   between calls.  No host synchronisation: the calls are capturable in a graph.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_BODY_MAX_JOINTS 64
+#define D3GA_BODY_MAX_SHAPE 32          /* n_shape + n_expr */
+#define D3GA_BODY_LD_ALIGN 2048         /* floats */
+#define D3GA_BODY_SAVED_FLOATS(J) (27 * (J) + 16)
+typedef struct d3ga_body_model {
+    int32_t V, J;               /* vertices, joints */
+    int32_t n_shape, n_expr;    /* shape and expression coefficients */
+    int32_t n_hand_pca;         /* hand PCA components of the compact SMPL-X pose layout, 0: none */
+    int32_t ld;                 /* row stride of dirs in floats */
+    int32_t n_levels;           /* levels of the kinematic tree */
+    int32_t reserved;
+    const float *v_template;    /* (V,3) */
+    const float *dirs;          /* (NR, ld) */
+    const int32_t *w_ptr, *w_joint;
+    const float *w_val;
+    const int32_t *wt_ptr, *wt_vert;
+    const float *wt_val;
+    const float *J0;            /* (J,3) */
+    const float *Jdirs;         /* (NS,J,3) */
+    const int32_t *parents, *level_ptr, *level_joint, *child_ptr, *child_joint;
+    const float *hand_comps, *hand_mean;
+} d3ga_body_model;
+int d3ga_body_model_scratch_bytes(const d3ga_body_model *model, int32_t B, int64_t *fwd_bytes, int64_t *bwd_bytes);
+int d3ga_body_model_fwd(const d3ga_body_model *model, int32_t B, int32_t pose_width, const float *poses, const float *shapes,
+                        const float *expr, const float *Rh, const float *Th, float *verts, float *T, float *A, float *bs,
+                        float *saved, void *scratch, int64_t scratch_bytes, d3ga_stream_t stream);
+int d3ga_body_model_bwd(const d3ga_body_model *model, int32_t B, int32_t pose_width, const float *saved, const float *T,
+                        const float *bs, const float *g_verts, const float *g_T, const float *g_A, const float *g_bs,
+                        float *g_poses, float *g_shapes, float *g_expr, float *g_Rh, float *g_Th, void *scratch,
+                        int64_t scratch_bytes, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * R1-R6  Tile rasterizer.  Replaces the un-vendored package `diff_gaussian_rasterization`
  * (graphdeco-inria, branch dr_aa; /root/reference/.gitmodules:9-12) as called from renderer.py:79-141:
  * _C.rasterize_gaussians / _C.rasterize_gaussians_backward / _C.mark_visible.
