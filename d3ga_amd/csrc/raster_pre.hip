@@ -25,19 +25,7 @@ constexpr int kShRow = 52;
 constexpr int kShSlab = 64 * kShRow;            // floats per wavefront
 constexpr size_t kShLdsBytes = (size_t)(kBlock / 64) * kShSlab * sizeof(float);   // 53,248 B per block
 
-__device__ __forceinline__ bool sh_staged(int M) { return M > 0 && (3 * M) % 4 == 0 && 3 * M <= 48; }
-#ifndef D3GA_PRE_DCOL        // 1: the forward leaves GeomBuf::dcol for the backward (round 5); 0: the backward reads the coefficients again (A/B build)
-#define D3GA_PRE_DCOL 1
-#endif
-#ifndef D3GA_DCOL_PLANAR     // 1 (default): GeomBuf::dcol as nine planes of P floats -- every store / load instruction is one contiguous run of a
-                             // wavefront (preprocess 57 -> 54.5 us against 36-byte records, same-box A/B); 0: records (A/B build)
-#define D3GA_DCOL_PLANAR 1
-#endif
-#if D3GA_DCOL_PLANAR
-#define D3GA_DCOL_AT(base, i, k, P) ((base)[(size_t)(k) * (size_t)(P) + (size_t)(i)])       /* P: the planes' stride (GeomBuf::dcol_stride) */
-#else
-#define D3GA_DCOL_AT(base, i, k, P) ((base)[9 * (size_t)(i) + (k)])
-#endif
+__host__ __device__ __forceinline__ bool sh_staged(int M) { return M > 0 && (3 * M) % 4 == 0 && 3 * M <= 48; }
 
 // global (rows x 3M floats, contiguous) -> LDS slab; `rows` valid rows of this wavefront (<= 64)
 __device__ __forceinline__ void sh_slab_load(float *slab, const float *__restrict__ src, int rows, int M3, int lane) {
@@ -86,30 +74,25 @@ __device__ __forceinline__ void sh_rows48_store(const float *slab, float *__rest
     }
 }
 
-// forward staging (see preprocess_kernel): kShPassRows of a wavefront's 64 rows at a time
-#ifndef D3GA_SH_PASS_ROWS
-#define D3GA_SH_PASS_ROWS 32
-#endif
-constexpr int kShPassRows = D3GA_SH_PASS_ROWS;                  // 32: two passes (default), 16: four (measured, slower: below)
-constexpr int kShPasses = 64 / kShPassRows;
+// forward staging (see preprocess_kernel): 32 of a wavefront's 64 rows at a time, in two passes
+constexpr int kShPassRows = 32;
 constexpr int kShHalfSlab = kShPassRows * kShRow;
-constexpr size_t kShHalfLdsBytes = (size_t)(kBlock / 64) * kShHalfSlab * sizeof(float);      // 26,624 B per block (32 rows)
+constexpr size_t kShHalfLdsBytes = (size_t)(kBlock / 64) * kShHalfSlab * sizeof(float);      // 26,624 B per block
 
-// sum_k Y_k(dir_i) * coeff_k of this thread's Gaussian, with the (P,M,3) block read through wavefront-private LDS.
-// SH colour in PASSES over a part of the wavefront's rows (full 192-byte rows, so every byte is fetched once): the slab of
-// a wavefront is kShPassRows x 52 floats -- 13 KiB for all 64 rows (12 resident wavefronts per CU), 6.5 KiB for 32 (20: the
-// default).  Round 4 measured 16 rows per pass (3.3 KiB: the tile window's 16 KiB is then the block's LDS, 28 wavefronts per
-// CU, the launch's 1954 workgroups in 1.09 instead of 1.53 rounds): with all four quarters in flight the registers hold the
-// kernel at 20 wavefronts anyway (88 VGPRs); with two in flight (68 VGPRs, 28 wavefronts) preprocess takes 61-65 us against
-// 55.6 (eager stage events, same box) -- the second memory round trip per wavefront and a quarter of the lanes per
-// accumulate pass cost more than the occupancy returns.  Only wavefront-private LDS is touched: no workgroup barrier,
-// program order + wave_barrier suffice.  Every thread of the block must call it.
+// sum_k Y_k(dir_i) * coeff_k of this thread's Gaussian, with the (P,M,3) block read through wavefront-private LDS: into acc, or
+// (WANT_J) into cj.a0..a2 with J = d(colour)/d(unit direction) (sh_accumulate_jacobian), from the same staged row.
+// SH colour in two PASSES over half of the wavefront's rows each (full 192-byte rows, so every byte is fetched once): the slab
+// of a wavefront is 32 x 52 floats, 6.5 KiB (20 resident wavefronts per CU; 64 rows would be 13 KiB and 12).  Round 4
+// measured 16 rows per pass (3.3 KiB: the tile window's 16 KiB is then the block's LDS, 28 wavefronts per CU, the launch's
+// 1954 workgroups in 1.09 instead of 1.53 rounds): with all four quarters in flight the registers hold the kernel at 20
+// wavefronts anyway (88 VGPRs); with two in flight (68 VGPRs, 28 wavefronts) preprocess takes 61-65 us against 55.6 (eager
+// stage events, same box) -- the second memory round trip per wavefront and a quarter of the lanes per accumulate pass cost
+// more than the occupancy returns (docs/LOG.md).  Only wavefront-private LDS is touched: no workgroup barrier, program order +
+// wave_barrier suffice.  Every thread of the block must call it.
 template <bool WANT_J>
 __device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, const float *__restrict__ means3D,
                                                  const float *__restrict__ shs, const float *__restrict__ campos,
                                                  float *s_sh, float acc[3], ShColJ &cj) {
-    constexpr bool want_j = WANT_J;
-    // WANT_J: also J = d(colour)/d(unit direction) of this Gaussian (sh_accumulate_jacobian), from the same staged row
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * kBlock + tid;
     const int M3 = 3 * prm.M;
@@ -119,50 +102,34 @@ __device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, 
     const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
     float B[16];
     float dx = 0.f, dy = 0.f, dz = 1.f;
-    if (want_j && i < prm.P) sh_view_dir(means3D, i, campos, dx, dy, dz);
+    if (WANT_J && i < prm.P) sh_view_dir(means3D, i, campos, dx, dy, dz);
+    auto eval = [&](const float *row) __attribute__((always_inline)) {
+        if (WANT_J) cj = sh_accumulate_jacobian(B, dx, dy, dz, row, nb, cj);
+        else sh_accumulate(B, row, 0, 16, nb, acc);
+    };
     if (M3 == 48 && rows == 64) {                              // wave-uniform: a full wavefront of full rows
+        // both halves' loads are issued up front (the second half waits in registers while the first is evaluated)
         const float *src = shs + (size_t)48 * row0;
-        auto pass = [&](const ShRegs<kShPassRows> &h, int p) {
-            __builtin_amdgcn_wave_barrier();
-            sh_rows48_to_slab<kShPassRows>(slab, h, lane);
-            __builtin_amdgcn_wave_barrier();
-            if (lane / kShPassRows == p) {
-                if (want_j) cj = sh_accumulate_jacobian(B, dx, dy, dz, slab + (lane % kShPassRows) * kShRow, nb, cj);
-                else sh_accumulate(B, slab + (lane % kShPassRows) * kShRow, 0, 16, nb, acc);
-            }
-        };
-        if constexpr (kShPasses == 2) {
-            // both halves' loads are issued up front (the second half waits in registers while the first is evaluated)
-            const ShRegs<kShPassRows> h0 = sh_rows48_load<kShPassRows>(src, lane);
-            const ShRegs<kShPassRows> h1 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows, lane);
-            sh_view_basis(prm, means3D, i, campos, B);
-            pass(h0, 0);
-            pass(h1, 1);
-        } else {
-            static_assert(kShPasses == 2 || kShPasses == 4, "two or four passes");
-            // two quarters' loads in flight at a time: quarter p + 2 is requested when quarter p has been evaluated
-            const ShRegs<kShPassRows> h0 = sh_rows48_load<kShPassRows>(src, lane);
-            const ShRegs<kShPassRows> h1 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows, lane);
-            sh_view_basis(prm, means3D, i, campos, B);
-            pass(h0, 0);
-            const ShRegs<kShPassRows> h2 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows * 2, lane);
-            pass(h1, 1);
-            const ShRegs<kShPassRows> h3 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows * 3, lane);
-            pass(h2, 2);
-            pass(h3, 3);
-        }
+        const ShRegs<kShPassRows> h0 = sh_rows48_load<kShPassRows>(src, lane);
+        const ShRegs<kShPassRows> h1 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows, lane);
+        sh_view_basis(prm, means3D, i, campos, B);
+        __builtin_amdgcn_wave_barrier();
+        sh_rows48_to_slab<kShPassRows>(slab, h0, lane);
+        __builtin_amdgcn_wave_barrier();
+        if (lane / kShPassRows == 0) eval(slab + (lane % kShPassRows) * kShRow);
+        __builtin_amdgcn_wave_barrier();
+        sh_rows48_to_slab<kShPassRows>(slab, h1, lane);
+        __builtin_amdgcn_wave_barrier();
+        if (lane / kShPassRows == 1) eval(slab + (lane % kShPassRows) * kShRow);
         return;
     }
     if (i < prm.P) sh_view_basis(prm, means3D, i, campos, B);
-    for (int h = 0; h < kShPasses; ++h) {
+    for (int h = 0; h < 2; ++h) {
         const int r = min(kShPassRows, rows - kShPassRows * h);
         __builtin_amdgcn_wave_barrier();
         if (r > 0) sh_slab_load(slab, shs + (size_t)M3 * (row0 + kShPassRows * h), r, M3, lane);
         __builtin_amdgcn_wave_barrier();
-        if (i < prm.P && lane / kShPassRows == h) {
-            if (want_j) cj = sh_accumulate_jacobian(B, dx, dy, dz, slab + (lane % kShPassRows) * kShRow, nb, cj);
-            else sh_accumulate(B, slab + (lane % kShPassRows) * kShRow, 0, 16, nb, acc);
-        }
+        if (i < prm.P && lane / kShPassRows == h) eval(slab + (lane % kShPassRows) * kShRow);
     }
 }
 
@@ -188,11 +155,7 @@ __device__ __forceinline__ TileRect write_geom_records(const GeomBuf &geom, int 
     }
     geom.rgb_invd[i] = make_float4(o.rgb[0], o.rgb[1], o.rgb[2], sp.visible ? 1.0f / sp.depth : 0.f);
     geom.clamped[i] = o.clampmask;
-    if (want_j) {
-        const float jv[9] = {cj.j0, cj.j1, cj.j2, cj.j3, cj.j4, cj.j5, cj.j6, cj.j7, cj.j8};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) D3GA_DCOL_AT(geom.dcol, i, k, geom.dcol_stride) = jv[k];
-    }
+    if (want_j) dcol_store(geom.dcol, geom.dcol_stride, i, cj);
     return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
 }
 
@@ -208,11 +171,11 @@ __device__ __forceinline__ PreOut window_clip(PreOut o, int x0, int y0, int gx, 
     return o;
 }
 // the window table of the binning buffer (one {ox, oy, w, h} per view) from the views' 9-float camera rows
-__global__ void window_table_kernel(const float *__restrict__ campos, int views, int4 *__restrict__ table) {
+__global__ void window_table_kernel(d3ga_raster_params prm, const float *__restrict__ campos, int views, int4 *__restrict__ table) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= views) return;
-    const float *cp = campos + (size_t)D3GA_CAMERA_SLOT_WINDOWED_FLOATS * v;
-    table[v] = make_int4((int)cp[7], (int)cp[8], (int)cp[5], (int)cp[6]);
+    const ViewCam c = view_cam(prm, nullptr, nullptr, campos + (size_t)D3GA_CAMERA_SLOT_WINDOWED_FLOATS * v, true);
+    table[v] = make_int4(c.ox, c.oy, c.W, c.H);
 }
 
 // tile histogram (counting-sort pass 1) of this block's Gaussians through its LDS window.  Every thread of the block must call it
@@ -243,8 +206,28 @@ __device__ __forceinline__ void tile_histogram(int *s_box, uint32_t *s_cnt, cons
     }
 }
 
+// The per-view tail of both forward kernels: R1 of Gaussian i in view `cam` from what the kernel has in registers (staged: the SH
+// colour sum in cj.a0..a2; pre: the covariance row and raw opacity), then the view's records.  WIN: the rectangle is clipped to the
+// window's gx x gy tiles.
+template <bool WIN>
+__device__ __forceinline__ TileRect preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D,
+                                                    const float *sh_row, bool staged, const ShColJ &cj, bool pre, const float (&pc6)[6],
+                                                    float pop, const float *colors_precomp, const float *opacities, const float *scales,
+                                                    const float *rotations, const float *cov3D_precomp, const GeomBuf &geom,
+                                                    int tile_row0, int32_t *radii, bool want_j, int gx, int gy) {
+    PreLoaded pl;
+    pl.has_sh = staged; pl.has_c6 = pre;
+    pl.sh[0] = cj.a0; pl.sh[1] = cj.a1; pl.sh[2] = cj.a2;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pl.c6[k] = pc6[k];
+    pl.op = pop;
+    PreOut o = preprocess_one(prm, cam, i, means3D, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
+    if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
+    return write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, want_j, cj);
+}
+
 // WIN: windowed camera slot (campos: 9 floats, d3ga.h): project with the view's raster size, histogram over the window's tiles
-template <bool WANT_J, bool WIN = false>      // WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
+template <bool WANT_J, bool WIN>      // WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
@@ -252,13 +235,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const float *__restrict__ projmatrix, const float *__restrict__ campos, GeomBuf geom,
     uint32_t *__restrict__ tile_count, uint32_t *__restrict__ counters, int32_t *__restrict__ radii,
     int tile_row0 /* view-batched renders: this view's first tile row in the batch's grid (d3ga.h: n_views); else 0 */) {
-    if (!(prm.tanfovx > 0.f)) { prm.tanfovx = campos[3]; prm.tanfovy = campos[4]; }     // camera slot: see d3ga.h
-    int wx0 = 0, wy0 = 0, wgx = 0, wgy = 0;                          // (WIN) the window's first tile and its grid
-    if constexpr (WIN) {
-        wgx = (prm.W + kTile - 1) / kTile + 1; wgy = (prm.H + kTile - 1) / kTile + 1;
-        wx0 = (int)campos[7] / kTile; wy0 = (int)campos[8] / kTile;
-        prm.W = (int)campos[5]; prm.H = (int)campos[6];
-    }
+    const ViewCam cam = view_cam(prm, viewmatrix, projmatrix, campos, WIN);
+    const int gx = (prm.W + kTile - 1) / kTile + (WIN ? 1 : 0), gy = (prm.H + kTile - 1) / kTile + 1;   // (WIN) the window's grid
     // one dynamic LDS region, used first as the SH staging slabs and then (after a barrier) as the tile window
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_box[4];
@@ -268,7 +246,6 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const int i = blockIdx.x * kBlock + tid;
     const int M3 = 3 * prm.M;
     const bool staged = shs != nullptr && sh_staged(prm.M);
-    float acc[3] = {0.f, 0.f, 0.f};
     // covariance row and opacity: in flight while the SH rows are staged
     float pc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pop = 0.f;
     const bool pre = staged && cov3D_precomp != nullptr;
@@ -278,36 +255,22 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
         pop = opacities[i];
     }
     ShColJ cj = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    constexpr bool want_j = WANT_J;                                 // (the launcher: staged && !forward_only)
+    float acc[3] = {0.f, 0.f, 0.f};
     if (staged) {
         staged_sh_colour<WANT_J>(prm, means3D, shs, campos, s_sh, acc, cj);
-        if (want_j) { acc[0] = cj.a0; acc[1] = cj.a1; acc[2] = cj.a2; }
+        if (!WANT_J) { cj.a0 = acc[0]; cj.a1 = acc[1]; cj.a2 = acc[2]; }
         __syncthreads();                                            // the region becomes the tile window below
     }
     TileRect tr = {false, 0, 0, 0, 0};
-#ifdef D3GA_DIAG
-    if (prm.debug & 0x200) { if (acc[0] == 12345.f) radii[0] = 1; return; }     // diag: SH staging only
-#endif
     if (i < prm.P) {
         // two call sites so that each inlined copy sees ONE address space (registers vs global_load, never flat)
-        PreLoaded pl;
-        pl.has_sh = staged; pl.has_c6 = pre;
-        pl.sh[0] = acc[0]; pl.sh[1] = acc[1]; pl.sh[2] = acc[2];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) pl.c6[k] = pc6[k];
-        pl.op = pop;
-        const PreOut o = staged ? preprocess_one(prm, i, means3D, nullptr, colors_precomp, opacities, scales, rotations,
-                                                 cov3D_precomp, viewmatrix, projmatrix, campos, pl)
-                                : preprocess_one(prm, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, colors_precomp,
-                                                 opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                                                 campos);
-        if constexpr (WIN) tr = write_geom_records(geom, i, window_clip(o, wx0, wy0, wgx, wgy), !cov3D_precomp, tile_row0, radii, want_j, cj);
-        else tr = write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, want_j, cj);
+        tr = staged ? preprocess_view<WIN>(prm, cam, i, means3D, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
+                                           rotations, cov3D_precomp, geom, tile_row0, radii, WANT_J, gx, gy)
+                    : preprocess_view<WIN>(prm, cam, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
+                                           colors_precomp, opacities, scales, rotations, cov3D_precomp, geom, tile_row0, radii,
+                                           WANT_J, gx, gy);
     }
-#ifdef D3GA_DIAG
-    if (prm.debug & 0x100) return;                                              // diag: no histogram
-#endif
-    tile_histogram(s_box, s_cnt, tr, WIN ? wgx : (prm.W + kTile - 1) / kTile, tile_count, counters);      // (barriers inside: the slabs are dead now)
+    tile_histogram(s_box, s_cnt, tr, gx, tile_count, counters);      // (barriers inside: the slabs are dead now)
 }
 
 // The same for KV views of ONE set of Gaussians in one pass (view-batched renders with shared geometry, d3ga.h: n_views): the
@@ -315,8 +278,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
 // colour (and its direction Jacobian) is formed from the staged row with that view's direction, the projection runs, the records go
 // to the view's section of the batch's buffers and the view's histogram pass follows.  Per view the arithmetic is that of
 // preprocess_kernel (same inlined functions, same order): bit-identical records.  views: KV cameras starting at `view0`.
-template <int KV>
-struct ViewCams { const float *vm[KV], *pm[KV], *cp[KV]; };
+// Unlike staged_sh_colour, the basis is formed inside the passes: the registers cannot hold KV of them.
 template <bool WANT_J, int KV>
 __device__ __forceinline__ void staged_sh_colour_views(const d3ga_raster_params &prm, const float *__restrict__ means3D, size_t pv,
                                                        const float *__restrict__ shs, const ViewCams<KV> &cams, float *s_sh,
@@ -347,7 +309,6 @@ __device__ __forceinline__ void staged_sh_colour_views(const d3ga_raster_params 
         }
     };
     if (M3 == 48 && rows == 64) {                              // wave-uniform: a full wavefront of full rows
-        static_assert(kShPasses == 2, "two passes");
         const float *src = shs + (size_t)48 * row0;
         const ShRegs<kShPassRows> h0 = sh_rows48_load<kShPassRows>(src, lane);
         const ShRegs<kShPassRows> h1 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows, lane);
@@ -361,7 +322,7 @@ __device__ __forceinline__ void staged_sh_colour_views(const d3ga_raster_params 
         if (lane / kShPassRows == 1) eval(slab + (lane % kShPassRows) * kShRow);
         return;
     }
-    for (int h = 0; h < kShPasses; ++h) {
+    for (int h = 0; h < 2; ++h) {
         const int r = min(kShPassRows, rows - kShPassRows * h);
         __builtin_amdgcn_wave_barrier();
         if (r > 0) sh_slab_load(slab, shs + (size_t)M3 * (row0 + kShPassRows * h), r, M3, lane);
@@ -383,7 +344,6 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(smem);
     const int tid = threadIdx.x;
     const int i = blockIdx.x * kBlock + tid;
-    const bool slot = !(prm.tanfovx > 0.f);                     // camera slots: the tangents ride behind every view's position
     // shared by the views: covariance row and opacity (in flight while the SH rows are staged)
     float pc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pop = 0.f;
     const bool pre = cov3D_precomp != nullptr && pv == 0;
@@ -402,19 +362,11 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
         __syncthreads();                                        // the LDS region changes hands: slabs -> window, window -> window
         TileRect tr = {false, 0, 0, 0, 0};
         if (i < prm.P) {
-            d3ga_raster_params pvw = prm;
-            if (slot) { pvw.tanfovx = cams.cp[v][3]; pvw.tanfovy = cams.cp[v][4]; }
-            PreLoaded pl;
-            pl.has_sh = true; pl.has_c6 = pre;
-            pl.sh[0] = cj[v].a0; pl.sh[1] = cj[v].a1; pl.sh[2] = cj[v].a2;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) pl.c6[k] = pc6[k];
-            pl.op = pop;
             const size_t og = pv * v;
-            const PreOut o = preprocess_one(pvw, i, means3D + 3 * og, nullptr, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
-                                            rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr,
-                                            cams.vm[v], cams.pm[v], cams.cp[v], pl);
-            tr = write_geom_records(geom_view(geom, prm.P, v), i, o, !cov3D_precomp, tile_row0 + v * gyv, radii + (size_t)prm.P * v, WANT_J, cj[v]);
+            tr = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, means3D + 3 * og, nullptr, true,
+                                        cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
+                                        rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr,
+                                        geom_view(geom, prm.P, v), tile_row0 + v * gyv, radii + (size_t)prm.P * v, WANT_J, gx, 0);
         }
         tile_histogram(s_box, s_cnt, tr, gx, tile_count, counters);
     }
@@ -434,19 +386,16 @@ __global__ __launch_bounds__(kBlock) void recolor_kernel(d3ga_raster_params prm,
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const int M3 = 3 * prm.M;
     const bool staged = shs != nullptr && sh_staged(prm.M);
-    float acc[3] = {0.f, 0.f, 0.f};
     ShColJ cj = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    constexpr bool want_j = WANT_J;
+    float acc[3] = {0.f, 0.f, 0.f};
     if (staged) staged_sh_colour<WANT_J>(prm, means3D, shs, campos, s_sh, acc, cj);
     if (i >= prm.P) return;
-    if (want_j) {
+    if (WANT_J) {
         acc[0] = cj.a0; acc[1] = cj.a1; acc[2] = cj.a2;
-        const float jv[9] = {cj.j0, cj.j1, cj.j2, cj.j3, cj.j4, cj.j5, cj.j6, cj.j7, cj.j8};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) D3GA_DCOL_AT(dst.dcol, i, k, dst.dcol_stride) = jv[k];
+        dcol_store(dst.dcol, dst.dcol_stride, i, cj);
     }
     const uint2 rc = src.rect[i];
-    const bool visible = ((rc.y & 0xffffu) > (rc.x & 0xffffu)) && ((rc.y >> 16) > (rc.x >> 16));
+    const bool visible = rect_visible(rc.x, rc.y);
     const float depth = src.depth[i];
     dst.depth[i] = depth;
     dst.conic_o[i] = src.conic_o[i];
@@ -478,7 +427,13 @@ __global__ __launch_bounds__(kBlock) void recolor_kernel(d3ga_raster_params prm,
     dst.clamped[i] = mask;
 }
 
-template <bool WIN = false>      // WIN: windowed camera slot -- the view's raster size from campos[5], campos[6]
+// the records of a view's backward as the per-view bodies read them (raster_pre_body.h)
+__device__ __forceinline__ ViewRecs view_recs(const GeomBuf &g, const float *acc) {
+    return ViewRecs{reinterpret_cast<const uint32_t *>(g.rect), acc, g.clamped, reinterpret_cast<const float *>(g.conic_o), g.dcol,
+                    g.dcol_stride};
+}
+
+template <bool WIN>      // WIN: windowed camera slot -- the view's raster size from its camera row
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ viewmatrix,
@@ -487,8 +442,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors,
     float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscales, float *__restrict__ dL_drots,
     const float *__restrict__ cov3D_precomp, int accum /* views > 0 of a batch: add to the gradients of inputs the views share (raster_pre_body.h) */) {
-    if (!(prm.tanfovx > 0.f)) { prm.tanfovx = campos[3]; prm.tanfovy = campos[4]; }     // camera slot: see d3ga.h
-    if constexpr (WIN) { prm.W = (int)campos[5]; prm.H = (int)campos[6]; }
+    const ViewCam cam = view_cam(prm, viewmatrix, projmatrix, campos, WIN);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_sh = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -502,26 +456,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     // This Gaussian's records first, unconditionally (an invisible one has an all-zero accumulator row and a valid
     // covariance row): they are in flight together with the SH rows instead of two dependent round trips behind them.
     uint2 rc = make_uint2(0u, 0u);
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0;
-    float a[12], c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    AccRec ar;                                                  // (set for i < P only, as a[] was: zero-initialising it changes the packed float code)
+    float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     uint8_t clampmask = 0;
     float act_opacity = 0.f;
     if (i < prm.P) {
         rc = geom.rect[i];
-        const float4 *ap = reinterpret_cast<const float4 *>(acc + D3GA_ACC_STRIDE * (size_t)i);
-        a0 = ap[0]; a1 = ap[1]; a2 = ap[2];
-        if (prm.acc_self_clearing) {
-            // the caller keeps this buffer for the next backward: leave the record as we found the untouched ones, all zero
-            // (only records the compositing backward wrote are written back: 48 of their 64 bytes)
-            const uint32_t any = (__float_as_uint(a0.x) | __float_as_uint(a0.y) | __float_as_uint(a0.z) | __float_as_uint(a0.w)) |
-                                 (__float_as_uint(a1.x) | __float_as_uint(a1.y) | __float_as_uint(a1.z) | __float_as_uint(a1.w)) |
-                                 (__float_as_uint(a2.x) | __float_as_uint(a2.y) | __float_as_uint(a2.z) | __float_as_uint(a2.w));
-            if (any) {
-                float4 *wp = const_cast<float4 *>(ap);
-                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                wp[0] = z; wp[1] = z; wp[2] = z;
-            }
-        }
+        ar = acc_load(acc, i, prm.acc_self_clearing);
 #pragma unroll
         for (int k = 0; k < 6; ++k) c6[k] = (cov3D_precomp ? cov3D_precomp : geom.cov3D)[6 * (size_t)i + k];   // (the forward kept no copy of a precomputed one)
         clampmask = geom.clamped[i];
@@ -530,26 +471,19 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     // Round 5: the forward left d(colour)/d(direction) of every Gaussian (geom.dcol, 36 bytes) when it staged the coefficients and
     // a backward was to follow: the coefficients themselves (192 bytes per Gaussian) are then not read here at all -- the slab
     // only collects the gradient rows for the coalesced store.
-    const bool have_j = D3GA_PRE_DCOL && staged && !prm.forward_only;
+    const bool have_j = staged && !prm.forward_only;
     ShColJ jd = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (have_j && i < prm.P) {
-        const float *d = geom.dcol;
-        jd.j0 = D3GA_DCOL_AT(d, i, 0, geom.dcol_stride); jd.j1 = D3GA_DCOL_AT(d, i, 1, geom.dcol_stride); jd.j2 = D3GA_DCOL_AT(d, i, 2, geom.dcol_stride);
-        jd.j3 = D3GA_DCOL_AT(d, i, 3, geom.dcol_stride); jd.j4 = D3GA_DCOL_AT(d, i, 4, geom.dcol_stride); jd.j5 = D3GA_DCOL_AT(d, i, 5, geom.dcol_stride);
-        jd.j6 = D3GA_DCOL_AT(d, i, 6, geom.dcol_stride); jd.j7 = D3GA_DCOL_AT(d, i, 7, geom.dcol_stride); jd.j8 = D3GA_DCOL_AT(d, i, 8, geom.dcol_stride);
-    }
+    if (have_j && i < prm.P) jd = dcol_load(geom.dcol, geom.dcol_stride, i);
     if (staged && !have_j) {
         if (full48) sh_rows48_to_slab<64>(slab, sh_rows48_load<64>(shs + (size_t)48 * row0, lane), lane);
         else if (rows > 0) sh_slab_load(slab, shs + (size_t)M3 * row0, rows, M3, lane);
         __builtin_amdgcn_wave_barrier();          // the slab is private to the wavefront: program order suffices
     }
     if (i < prm.P) {
-        const bool visible = ((rc.y & 0xffffu) > (rc.x & 0xffffu)) && ((rc.y >> 16) > (rc.x >> 16));
-        a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w; a[4] = a1.x; a[5] = a1.y; a[6] = a1.z; a[7] = a1.w;
-        a[8] = a2.x; a[9] = a2.y; a[10] = a2.z; a[11] = a2.w;
+        const bool visible = rect_visible(rc.x, rc.y);
         if (!visible) {
 #pragma unroll
-            for (int k = 0; k < 12; ++k) a[k] = 0.f;
+            for (int k = 0; k < 12; ++k) ar.a[k] = 0.f;
 #pragma unroll
             for (int k = 0; k < 6; ++k) c6[k] = 0.f;
             act_opacity = 0.f;
@@ -557,16 +491,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
         // two call sites so that each inlined copy sees ONE address space (LDS row vs global row, never flat);
         // staged: the gradient row overwrites the coefficient row in place
         if (staged)
-            preprocess_bwd_one(prm, i, visible, means3D, slab + lane * kShRow, scales, rotations, viewmatrix, projmatrix,
-                               campos, c6, clampmask, a, dL_dmeans3D, dL_dmeans2D, dL_dopacity,
-                               dL_dsh ? slab + lane * kShRow : nullptr, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots,
-                               act_opacity, have_j, jd, accum);
+            preprocess_bwd_one(prm, cam, i, visible, means3D, slab + lane * kShRow, scales, rotations, c6, clampmask, ar.a, dL_dmeans3D,
+                               dL_dmeans2D, dL_dopacity, dL_dsh ? slab + lane * kShRow : nullptr, dL_dcolors, dL_dcov3D, dL_dscales,
+                               dL_drots, act_opacity, have_j, jd, accum);
         else
-            preprocess_bwd_one(prm, i, visible, means3D, shs ? shs + (size_t)M3 * i : nullptr, scales, rotations,
-                               viewmatrix, projmatrix, campos, c6, clampmask, a, dL_dmeans3D, dL_dmeans2D,
-                               dL_dopacity, dL_dsh ? dL_dsh + (size_t)M3 * i : nullptr, dL_dcolors, dL_dcov3D,
-                               dL_dscales, dL_drots,
-                               act_opacity, false, ShColJ(), accum);
+            preprocess_bwd_one(prm, cam, i, visible, means3D, shs ? shs + (size_t)M3 * i : nullptr, scales, rotations, c6, clampmask,
+                               ar.a, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh ? dL_dsh + (size_t)M3 * i : nullptr, dL_dcolors,
+                               dL_dcov3D, dL_dscales, dL_drots, act_opacity, false, ShColJ(), accum);
     }
     if (staged && dL_dsh) {
         __builtin_amdgcn_wave_barrier();          // the slab is private to the wavefront: program order suffices
@@ -576,21 +507,18 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
 }
 
 // R6 for the views of a batch that share their geometry (d3ga.h: n_views without per_view_geometry), ONE pass: thread i walks the kv
-// views of Gaussian i -- per view its accumulator record, rectangle, clamp mask, stored opacity and d(colour)/d(direction) --, sums
-// the gradients of the shared inputs in registers and writes every output ONCE: no read-modify-write of dL/dmeans3D / dL/dcov /
-// dL/dopacity per view, no (P,3) factors through memory, the (P,M,3) SH row formed here (sum_v Y(dir_v) (x) g_v, as
-// sh_grad_from_views_kernel forms it) instead of by a pass of its own.  Same per-view arithmetic as preprocess_bwd_one (cov2d_bwd,
-// project_bwd, the direction term from the forward's Jacobian), views added in ascending order like the per-view launches add them.
-// SH colours need the forward's dcol planes (staged coefficients, forward_only == 0): the launcher falls back to per-view launches
-// otherwise, and for the factored SH output of the camera-sharded exchange.  accum: a later group of a batch of more than kMaxGroup
-// views -- every output is added to, except the per-view ones.  pva (d3ga.h: per_view_appearance, precomputed colours): dL/dopacity
-// and dL/dcolour are written per view at record v P + i of the group (a view that culled the Gaussian writes zeros), not summed.
+// views of Gaussian i (preprocess_bwd_views_one), sums the gradients of the shared inputs in registers and writes every output ONCE:
+// no read-modify-write of dL/dmeans3D / dL/dcov / dL/dopacity per view, no (P,3) factors through memory, the (P,M,3) SH row formed
+// there (sum_v Y(dir_v) (x) g_v, as sh_grad_from_views_kernel forms it) instead of by a pass of its own.  SH colours need the
+// forward's dcol planes (staged coefficients, forward_only == 0): the launcher falls back to per-view launches otherwise, and for the
+// factored SH output of the camera-sharded exchange.  accum: a later group of a batch of more than kMaxGroup views -- every output is
+// added to, except the per-view ones.  pva (d3ga.h: per_view_appearance, precomputed colours): dL/dopacity and dL/dcolour are
+// written per view at record v P + i of the group, not summed.
 constexpr int kMaxGroup = 8;
-struct ViewCamsN { const float *vm[kMaxGroup], *pm[kMaxGroup], *cp[kMaxGroup]; };
-template <bool WIN = false>      // WIN: windowed camera slots -- every view's raster size from its camera row
+template <bool WIN>      // WIN: windowed camera slots -- every view's raster size from its camera row
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
     d3ga_raster_params prm, int kv, const float *__restrict__ means3D, bool sh_path, const float *__restrict__ scales,
-    const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp, ViewCamsN cams, GeomBuf geom /* first view of the group */,
+    const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp, ViewCams<kMaxGroup> cams, GeomBuf geom /* first view of the group */,
     const float *__restrict__ acc /* first view of the group */, float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D /* first view | null */,
     float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors, float *__restrict__ dL_dcov3D,
     float *__restrict__ dL_dscales, float *__restrict__ dL_drots, bool accum,
@@ -604,123 +532,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_views_kernel(
     const int row0 = blockIdx.x * kBlock + wave * 64;
     const int rows = min(64, prm.P - row0);
     float *slab = s_sh + wave * kShSlab;
-    const bool slot = !(prm.tanfovx > 0.f);
-    const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
-    if (i < prm.P) {
-        V3 mean = ld3(means3D, i);
-        float c6[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) c6[k] = (cov3D_precomp ? cov3D_precomp : geom.cov3D)[6 * (size_t)i + k];   // (from scale / rotation: view 0's record -- the same in every view of shared geometry)
-        float gmean[3] = {0.f, 0.f, 0.f}, g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gop = 0.f, gcol[3] = {0.f, 0.f, 0.f};
-        auto put = [&](float *p, float v, bool add) { *p = add ? *p + v : v; };
-        auto geometry_out = [&](size_t og, const float (&gm)[3], const float (&g)[6], bool vis, bool add) {     // og: record offset of the geometry gradients
-            for (int k = 0; k < 3; ++k) put(dL_dmeans3D + 3 * (og + i) + k, gm[k], add);
-            if (dL_dcov3D)
-                for (int k = 0; k < 6; ++k) put(dL_dcov3D + 6 * (og + i) + k, g[k], add);
-            if (dL_dscales && dL_drots) {
-                float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
-                if (vis) {
-                    const float sc[3] = {scales[3 * (og + i)], scales[3 * (og + i) + 1], scales[3 * (og + i) + 2]};
-                    const float q[4] = {rotations[4 * (og + i)], rotations[4 * (og + i) + 1], rotations[4 * (og + i) + 2], rotations[4 * (og + i) + 3]};
-                    cov3d_from_scale_rot_bwd(sc, prm.scale_modifier, q, g, gs, gq);      // (linear in g: a sum over views goes through once)
-                }
-                for (int k = 0; k < 3; ++k) put(dL_dscales + 3 * (og + i) + k, gs[k], add);
-                for (int k = 0; k < 4; ++k) put(dL_drots + 4 * (og + i) + k, gq[k], add);
-            }
-        };
-        const float zero3[3] = {0.f, 0.f, 0.f}, zero6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float out[48];
-#pragma unroll
-        for (int k = 0; k < 48; ++k) out[k] = 0.f;
-        for (int v = 0; v < kv; ++v) {
-            const size_t j = (size_t)prm.P * v + i;                          // this view's record
-            const uint2 rc = geom.rect[j];
-            const float4 *ap = reinterpret_cast<const float4 *>(acc + D3GA_ACC_STRIDE * j);
-            const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2];
-            if (prm.acc_self_clearing) {
-                const uint32_t any = (__float_as_uint(a0.x) | __float_as_uint(a0.y) | __float_as_uint(a0.z) | __float_as_uint(a0.w)) |
-                                     (__float_as_uint(a1.x) | __float_as_uint(a1.y) | __float_as_uint(a1.z) | __float_as_uint(a1.w)) |
-                                     (__float_as_uint(a2.x) | __float_as_uint(a2.y) | __float_as_uint(a2.z) | __float_as_uint(a2.w));
-                if (any) {
-                    float4 *wp = const_cast<float4 *>(ap);
-                    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                    wp[0] = z; wp[1] = z; wp[2] = z;
-                }
-            }
-            const bool visible = ((rc.y & 0xffffu) > (rc.x & 0xffffu)) && ((rc.y >> 16) > (rc.x >> 16));
-            if (dL_dmeans2D) {                                                // screen-space: per view
-                float *m2 = dL_dmeans2D + 3 * j;
-                m2[0] = visible ? a0.x : 0.f; m2[1] = visible ? a0.y : 0.f; m2[2] = 0.f;
-            }
-            if (!visible) {
-                if (pv) geometry_out(pv * v, zero3, zero6, false, false);      // a batch of frames: every view's geometry gradients are written
-                if (pva) {                                                     // ... and per-view appearance every view's opacity / colour gradients
-                    if (dL_dopacity) dL_dopacity[j] = 0.f;
-                    if (dL_dcolors) { dL_dcolors[3 * j] = 0.f; dL_dcolors[3 * j + 1] = 0.f; dL_dcolors[3 * j + 2] = 0.f; }
-                }
-                continue;
-            }
-            if (pv) {                                                        // this view's own geometry
-                mean = ld3(means3D + 3 * pv * v, i);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) c6[k] = (cov3D_precomp ? cov3D_precomp + 6 * pv * v : geom.cov3D + 6 * (size_t)prm.P * v)[6 * (size_t)i + k];
-            }
-            const uint8_t clampmask = geom.clamped[j];
-            const float act_opacity = geom.conic_o[j].w;
-            const float a[12] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
-            const float *vm = cams.vm[v], *pm = cams.pm[v], *cp = cams.cp[v];
-            const float tfx = slot ? cp[3] : prm.tanfovx, tfy = slot ? cp[4] : prm.tanfovy;
-            float gm_v[3] = {0.f, 0.f, 0.f}, g6_v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, aa = 1.0f;
-            cov2d_bwd(mean, c6, vm, WIN ? (int)cp[5] : prm.W, WIN ? (int)cp[6] : prm.H, tfx, tfy, a[3], a[4], a[5], g6_v, gm_v, prm.antialiasing != 0,
-                      a[6], act_opacity, &aa);
-            project_bwd(mean, pm, a[0], a[1], gm_v);
-            const float z = vm[2] * mean.x + vm[6] * mean.y + vm[10] * mean.z + vm[14];
-            const float gz = -a[10] / (z * z);
-            gm_v[0] += vm[2] * gz; gm_v[1] += vm[6] * gz; gm_v[2] += vm[10] * gz;
-            if (sh_path) {
-                const float gr[3] = {(clampmask & 1) ? 0.f : a[7], (clampmask & 2) ? 0.f : a[8], (clampmask & 4) ? 0.f : a[9]};
-                const V3 d0 = mean - v3(cp[0], cp[1], cp[2]);
-                const float inv = 1.0f / sqrtf(dot(d0, d0));
-                float B[16];
-                sh_basis(prm.sh_degree, d0.x * inv, d0.y * inv, d0.z * inv, B);
-                const float *d = geom.dcol;
-                const float j0 = D3GA_DCOL_AT(d, j, 0, geom.dcol_stride), j1 = D3GA_DCOL_AT(d, j, 1, geom.dcol_stride), j2 = D3GA_DCOL_AT(d, j, 2, geom.dcol_stride);
-                const float j3 = D3GA_DCOL_AT(d, j, 3, geom.dcol_stride), j4 = D3GA_DCOL_AT(d, j, 4, geom.dcol_stride), j5 = D3GA_DCOL_AT(d, j, 5, geom.dcol_stride);
-                const float j6 = D3GA_DCOL_AT(d, j, 6, geom.dcol_stride), j7 = D3GA_DCOL_AT(d, j, 7, geom.dcol_stride), j8 = D3GA_DCOL_AT(d, j, 8, geom.dcol_stride);
-                const V3 gd = v3(j0 * gr[0] + j1 * gr[1] + j2 * gr[2], j3 * gr[0] + j4 * gr[1] + j5 * gr[2], j6 * gr[0] + j7 * gr[1] + j8 * gr[2]);
-                const V3 gm = normalize_bwd(d0, gd);
-                gm_v[0] += gm.x; gm_v[1] += gm.y; gm_v[2] += gm.z;
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (k < nb) { out[3 * k] += B[k] * gr[0]; out[3 * k + 1] += B[k] * gr[1]; out[3 * k + 2] += B[k] * gr[2]; }
-            } else if (pva) {
-                if (dL_dcolors) { dL_dcolors[3 * j] = a[7]; dL_dcolors[3 * j + 1] = a[8]; dL_dcolors[3 * j + 2] = a[9]; }
-            } else {
-                gcol[0] += a[7]; gcol[1] += a[8]; gcol[2] += a[9];
-            }
-            {
-                const float op = act_opacity / aa, g_op = a[6] * aa;
-                const float g = prm.opacity_activation == D3GA_OPACITY_SIGMOID ? g_op * op * (1.0f - op) : g_op;
-                if (!pva) gop += g;
-                else if (dL_dopacity) dL_dopacity[j] = g;
-            }
-            if (pv) geometry_out(pv * v, gm_v, g6_v, true, false);
-            else {
-                gmean[0] += gm_v[0]; gmean[1] += gm_v[1]; gmean[2] += gm_v[2];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) g6[k] += g6_v[k];
-            }
-        }
-        if (!pv) geometry_out(0, gmean, g6, true, accum);
-        if (dL_dopacity && !pva) put(dL_dopacity + i, gop, accum);
-        if (!sh_path && !pva && dL_dcolors) { put(dL_dcolors + 3 * (size_t)i, gcol[0], accum); put(dL_dcolors + 3 * (size_t)i + 1, gcol[1], accum); put(dL_dcolors + 3 * (size_t)i + 2, gcol[2], accum); }
-        if (sh_path && dL_dsh) {
-            float *row = slab + lane * kShRow;
-#pragma unroll
-            for (int k = 0; k < 48; ++k)
-                if (k < M3) row[k] = out[k];
-        }
-    }
+    if (i < prm.P)
+        preprocess_bwd_views_one(prm, i, kv, WIN, cams, view_recs(geom, acc), means3D, cov3D_precomp ? cov3D_precomp : geom.cov3D,
+                                 scales, rotations, sh_path, pv, pva, accum, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dcolors,
+                                 dL_dcov3D, dL_dscales, dL_drots, sh_path && dL_dsh ? slab + lane * kShRow : nullptr);
     if (sh_path && dL_dsh) {
         __builtin_amdgcn_wave_barrier();          // the slab is private to the wavefront: program order suffices
         if (accum) {                              // a later group of a large batch: add to what the earlier groups wrote
@@ -813,6 +628,30 @@ static int validate(const d3ga_raster_params *prm) {
     return D3GA_OK;
 }
 
+// The launchers' shared rules.  staged: the kernels move the SH rows through the LDS slabs; leaves_dcol: the forward then leaves
+// GeomBuf::dcol for a backward to follow, and the backward reads it instead of the coefficients.
+static bool staged(const d3ga_raster_params *prm, const float *shs) { return shs != nullptr && sh_staged(prm->M); }
+static bool leaves_dcol(const d3ga_raster_params *prm, const float *shs) { return staged(prm, shs) && !prm->forward_only; }
+// dynamic LDS of a launch: the SH slabs if staged, at least `floor` bytes (the forward's tile window)
+static size_t lds_bytes(bool staged, size_t slabs, size_t floor = 0) { return staged && slabs > floor ? slabs : floor; }
+// floats per camera row (d3ga.h: camera slots carry the two tangents behind the position, windowed ones also the raster and window)
+static int cam_stride(const d3ga_raster_params *prm) {
+    return prm->tanfovx > 0.f ? 3 : (is_windowed(prm) ? D3GA_CAMERA_SLOT_WINDOWED_FLOATS : 5);
+}
+// the cameras of views [v0, v0 + kv) (slots past kv repeat view v0)
+template <int K>
+static ViewCams<K> view_cams(const float *vm, const float *pm, const float *cp, int stride, int v0, int kv) {
+    ViewCams<K> c;
+    for (int q = 0; q < K; ++q) {
+        const int v = v0 + (q < kv ? q : 0);
+        c.vm[q] = vm + 16 * (size_t)v; c.pm[q] = pm + 16 * (size_t)v; c.cp[q] = cp + (size_t)stride * v;
+    }
+    return c;
+}
+// a per-record array of a batch at record r (n floats per record), or null
+template <class T>
+static T *at(T *p, size_t n, size_t r) { return p ? p + n * r : nullptr; }
+
 extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float *means3D, const float *shs,
                                       const float *colors_precomp, const float *opacities, const float *scales,
                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
@@ -828,7 +667,7 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     BinBuf bin = carve_bin(binning, tiles, d_capacity);
     // counters + tile_count are adjacent: one memset
     D3GA_HIP(zero_async(bin.counters, 256 + align256(4 * tiles), s));
-    if (wnd) hipLaunchKernelGGL(window_table_kernel, dim3((views + 63) / 64), dim3(64), 0, s, campos, views, win_table(binning, tiles, d_capacity));
+    if (wnd) hipLaunchKernelGGL(window_table_kernel, dim3((views + 63) / 64), dim3(64), 0, s, *prm, campos, views, win_table(binning, tiles, d_capacity));
     if (prm->P == 0) return D3GA_OK;          // empty scene: every per-Gaussian tensor is empty (NULL)
     if ((shs != nullptr) == (colors_precomp != nullptr)) return D3GA_E_CONFIG;
     const bool pva = views > 1 && prm->per_view_appearance;   // (k,P) opacities and (k,P,3) colours: precomputed colours only (d3ga.h)
@@ -838,11 +677,9 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     if (shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M) return D3GA_E_CONFIG;
     if (!means3D || !opacities || !radii) return D3GA_E_NULL;
     const GeomBuf g = carve_geom(geom, (int64_t)prm->P * views);
-    const size_t win = (size_t)kWinTiles * 4;
-    const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? (kShHalfLdsBytes > win ? kShHalfLdsBytes : win) : win;
-    // (the kernels' `staged` condition, on the host: with it and a backward to follow the forward leaves GeomBuf::dcol)
-    const bool want_j = D3GA_PRE_DCOL && shs && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48 && !prm->forward_only;
-    const int cam_stride = prm->tanfovx > 0.f ? 3 : (wnd ? D3GA_CAMERA_SLOT_WINDOWED_FLOATS : 5);   // camera slots carry the two tangents behind the position
+    const size_t lds = lds_bytes(staged(prm, shs), kShHalfLdsBytes, (size_t)kWinTiles * 4);
+    const bool want_j = leaves_dcol(prm, shs);
+    const int cs = cam_stride(prm);
     // a batch of views writes view v's records at v P + i of the batch's buffers: grouped launches below when the SH row can be
     // shared, else one launch per view (a streaming kernel at the copy rate gains nothing from a taller grid)
     const size_t pv = (views > 1 && prm->per_view_geometry) ? (size_t)prm->P : 0;      // records between the views' geometry (0: shared)
@@ -852,48 +689,30 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     // k cameras of ONE set of Gaussians with staged SH colours: groups of up to four views per pass (preprocess_views_kernel: the
     // 12 M-byte coefficient row, the mean and the covariance are read once per group instead of once per view).  SH only, so never
     // with per-view appearance (refused above): the group kernel reads one opacity per Gaussian for all its views
-    const bool grouped = views > 1 && shs && !pva && !wnd && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
-#define D3GA_PRE_VIEWS(KVV)                                                                                                        \
-    do {                                                                                                                           \
-        ViewCams<KVV> vc;                                                                                                          \
-        for (int q = 0; q < KVV; ++q) {                                                                                            \
-            vc.vm[q] = viewmatrix + 16 * (size_t)(v0 + q); vc.pm[q] = projmatrix + 16 * (size_t)(v0 + q);                          \
-            vc.cp[q] = campos + (size_t)cam_stride * (v0 + q);                                                                     \
-        }                                                                                                                          \
-        if (want_j) hipLaunchKernelGGL((preprocess_views_kernel<true, KVV>), grid, block, lds, s, *prm, means3D + 3 * pv * v0, shs, colors_precomp,  \
-                                       opacities, scales ? scales + 3 * pv * v0 : nullptr, rotations ? rotations + 4 * pv * v0 : nullptr, cov3D_precomp ? cov3D_precomp + 6 * pv * v0 : nullptr, vc, geom_view(g, prm->P, v0), bin.tile_count,  \
-                                       bin.counters, radii + (size_t)prm->P * v0, v0 * gyv, gyv, pv);                              \
-        else hipLaunchKernelGGL((preprocess_views_kernel<false, KVV>), grid, block, lds, s, *prm, means3D + 3 * pv * v0, shs, colors_precomp,    \
-                                opacities, scales ? scales + 3 * pv * v0 : nullptr, rotations ? rotations + 4 * pv * v0 : nullptr, cov3D_precomp ? cov3D_precomp + 6 * pv * v0 : nullptr, vc, geom_view(g, prm->P, v0), bin.tile_count,         \
-                                bin.counters, radii + (size_t)prm->P * v0, v0 * gyv, gyv, pv);                                     \
-        v0 += KVV;                                                                                                                 \
-    } while (0)
+    const bool grouped = views > 1 && !pva && !wnd && staged(prm, shs);
+    auto launch_group = [&](auto kv) {        // views [v0, v0 + KV)
+        constexpr int KV = decltype(kv)::value;
+        const size_t og = pv * v0;
+        hipLaunchKernelGGL((want_j ? preprocess_views_kernel<true, KV> : preprocess_views_kernel<false, KV>), grid, block, lds, s, *prm,
+                           at(means3D, 3, og), shs, colors_precomp, opacities, at(scales, 3, og), at(rotations, 4, og),
+                           at(cov3D_precomp, 6, og), view_cams<KV>(viewmatrix, projmatrix, campos, cs, v0, KV), geom_view(g, prm->P, v0),
+                           bin.tile_count, bin.counters, radii + (size_t)prm->P * v0, v0 * gyv, gyv, pv);
+        v0 += KV;
+    };
     while (grouped && views - v0 >= 2) {
         const int left = views - v0;
-        if (left >= 4 && left != 5) D3GA_PRE_VIEWS(4);          // (5 = 3 + 2: no single view left over)
-        else if (left == 3 || left == 5) D3GA_PRE_VIEWS(3);
-        else D3GA_PRE_VIEWS(2);
+        if (left >= 4 && left != 5) launch_group(std::integral_constant<int, 4>());     // (5 = 3 + 2: no single view left over)
+        else if (left == 3 || left == 5) launch_group(std::integral_constant<int, 3>());
+        else launch_group(std::integral_constant<int, 2>());
     }
-#undef D3GA_PRE_VIEWS
+    const auto kernel = want_j ? (wnd ? preprocess_kernel<true, true> : preprocess_kernel<true, false>)
+                               : (wnd ? preprocess_kernel<false, true> : preprocess_kernel<false, false>);
     for (int v = v0; v < views; ++v) {
-        const GeomBuf gv = geom_view(g, prm->P, v);
-        const float *vm = viewmatrix + 16 * (size_t)v, *pm = projmatrix + 16 * (size_t)v, *cp = campos + (size_t)cam_stride * v;
-        const float *mv = means3D + 3 * pv * v, *sv = scales ? scales + 3 * pv * v : nullptr, *rq = rotations ? rotations + 4 * pv * v : nullptr;
-        const float *cv = cov3D_precomp ? cov3D_precomp + 6 * pv * v : nullptr;
-        const float *ov = opacities + pa * v, *colv = colors_precomp ? colors_precomp + 3 * pa * v : nullptr;      // (per-view appearance)
-        int32_t *rv = radii + (size_t)prm->P * v;
-        if (wnd && want_j)
-            hipLaunchKernelGGL((preprocess_kernel<true, true>), grid, block, lds, s, *prm, mv, shs,
-                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
-        else if (wnd)
-            hipLaunchKernelGGL((preprocess_kernel<false, true>), grid, block, lds, s, *prm, mv, shs,
-                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
-        else if (want_j)
-            hipLaunchKernelGGL(preprocess_kernel<true>, grid, block, lds, s, *prm, mv, shs,
-                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
-        else
-            hipLaunchKernelGGL(preprocess_kernel<false>, grid, block, lds, s, *prm, mv, shs,
-                               colv, ov, sv, rq, cv, vm, pm, cp, gv, bin.tile_count, bin.counters, rv, v * gyv);
+        const ViewCams<1> c = view_cams<1>(viewmatrix, projmatrix, campos, cs, v, 1);
+        const size_t og = pv * v, oa = pa * v;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, *prm, at(means3D, 3, og), shs, at(colors_precomp, 3, oa), opacities + oa,
+                           at(scales, 3, og), at(rotations, 4, og), at(cov3D_precomp, 6, og), c.vm[0], c.pm[0], c.cp[0],
+                           geom_view(g, prm->P, v), bin.tile_count, bin.counters, radii + (size_t)prm->P * v, v * gyv);
     }
     return check_launch(s, prm->debug & 0xff);
 }
@@ -910,14 +729,8 @@ extern "C" int d3ga_raster_recolor(const d3ga_raster_params *prm, const float *m
     if (shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
     const GeomBuf src = carve_geom(const_cast<void *>(geom_src), prm->P), dst = carve_geom(geom_dst, prm->P);
-    const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? kShHalfLdsBytes : 0;
-    const bool want_j = D3GA_PRE_DCOL && shs && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48 && !prm->forward_only;
-    if (want_j)
-        hipLaunchKernelGGL(recolor_kernel<true>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D, shs,
-                           colors_precomp, campos, src, dst);
-    else
-        hipLaunchKernelGGL(recolor_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D, shs,
-                           colors_precomp, campos, src, dst);
+    hipLaunchKernelGGL(leaves_dcol(prm, shs) ? recolor_kernel<true> : recolor_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock),
+                       dim3(kBlock), lds_bytes(staged(prm, shs), kShHalfLdsBytes), s, *prm, means3D, shs, colors_precomp, campos, src, dst);
     return check_launch(s, prm->debug & 0xff);
 }
 
@@ -942,67 +755,49 @@ extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const f
     const bool pva = views > 1 && prm->per_view_appearance;      // per-view opacity / colour gradients: precomputed colours only (d3ga.h)
     if (pva && shs) return D3GA_E_CONFIG;
     const GeomBuf g = carve_geom(const_cast<void *>(geom), (int64_t)prm->P * views);
-    const size_t lds = (shs && prm->M > 0 && (3 * prm->M) % 4 == 0) ? kShLdsBytes : 0;
+    const size_t lds = lds_bytes(staged(prm, shs), kShLdsBytes);
     const bool win = is_windowed(prm);
+    const int cs = cam_stride(prm);
+    const dim3 grid((prm->P + kBlock - 1) / kBlock), block(kBlock);
+    const size_t pv = prm->per_view_geometry ? (size_t)prm->P : 0;      // a batch of frames: every view has its own geometry and geometry gradients
+    // one view of the batch on ITS records (preprocess_bwd_kernel)
+    auto launch_view = [&](int v, float *dsh, float *dcol, int accum) {
+        const ViewCams<1> c = view_cams<1>(viewmatrix, projmatrix, campos, cs, v, 1);
+        const size_t o = (size_t)prm->P * v, og = pv * v;
+        hipLaunchKernelGGL(win ? preprocess_bwd_kernel<true> : preprocess_bwd_kernel<false>, grid, block, lds, s, *prm, at(means3D, 3, og),
+                           shs, at(scales, 3, og), at(rotations, 4, og), c.vm[0], c.pm[0], c.cp[0], geom_view(g, prm->P, v),
+                           acc + D3GA_ACC_STRIDE * o, dL_dmeans3D + 3 * og, at(dL_dmeans2D, 3, o), dL_dopacity, dsh, dcol,
+                           at(dL_dcov3D, 6, og), at(dL_dscales, 3, og), at(dL_drots, 4, og), at(cov3D_precomp, 6, og), accum);
+    };
     if (views == 1) {
-        if (win)
-            hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D,
-                               shs, scales, rotations, viewmatrix, projmatrix, campos, g, acc, dL_dmeans3D, dL_dmeans2D,
-                               dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, cov3D_precomp, 0);
-        else
-            hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D,
-                               shs, scales, rotations, viewmatrix, projmatrix, campos, g, acc, dL_dmeans3D, dL_dmeans2D,
-                               dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, cov3D_precomp, 0);
+        launch_view(0, dL_dsh, dL_dcolors, 0);
         return check_launch(s, prm->debug);
     }
-    const int cam_stride = prm->tanfovx > 0.f ? 3 : (win ? D3GA_CAMERA_SLOT_WINDOWED_FLOATS : 5);
-    // k views that SHARE their geometry: one pass over the Gaussians walks the views (preprocess_bwd_views_kernel), up to eight per
-    // launch -- when the SH gradient is wanted as the (P,M,3) block (not as the factors of the camera-sharded exchange) and, for SH
-    // colours, the forward left its direction Jacobian
-    {
-        const bool staged_sh = shs && prm->M > 0 && (3 * prm->M) % 4 == 0 && 3 * prm->M <= 48;
-        const bool looped = shs ? (dL_dsh != nullptr && staged_sh && D3GA_PRE_DCOL && !prm->forward_only) : true;
-        const size_t pvl = prm->per_view_geometry ? (size_t)prm->P : 0;
-        if (looped) {
-            for (int v0 = 0; v0 < views; v0 += kMaxGroup) {
-                const int kv = views - v0 < kMaxGroup ? views - v0 : kMaxGroup;
-                ViewCamsN vc;
-                for (int q = 0; q < kMaxGroup; ++q) {
-                    const int v = v0 + (q < kv ? q : 0);
-                    vc.vm[q] = viewmatrix + 16 * (size_t)v; vc.pm[q] = projmatrix + 16 * (size_t)v; vc.cp[q] = campos + (size_t)cam_stride * v;
-                }
-                const size_t o = (size_t)prm->P * v0, og = pvl * v0, oa = pva ? o : 0;      // oa: the group's first per-view opacity / colour gradient
-                hipLaunchKernelGGL(win ? preprocess_bwd_views_kernel<true> : preprocess_bwd_views_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), shs ? kShLdsBytes : 0, s, *prm, kv,
-                                   means3D + 3 * og, shs != nullptr, scales ? scales + 3 * og : nullptr, rotations ? rotations + 4 * og : nullptr,
-                                   cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, vc, geom_view(g, prm->P, v0), acc + D3GA_ACC_STRIDE * o,
-                                   dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity ? dL_dopacity + oa : nullptr, dL_dsh,
-                                   dL_dcolors ? dL_dcolors + 3 * oa : nullptr, dL_dcov3D ? dL_dcov3D + 6 * og : nullptr,
-                                   dL_dscales ? dL_dscales + 3 * og : nullptr, dL_drots ? dL_drots + 4 * og : nullptr, v0 > 0, pvl, pva);
-            }
-            return check_launch(s, prm->debug);
+    // k views: one pass over the Gaussians walks the views (preprocess_bwd_views_kernel), up to eight per launch -- when the SH
+    // gradient is wanted as the (P,M,3) block (not as the factors of the camera-sharded exchange) and, for SH colours, the forward
+    // left its direction Jacobian
+    if (shs ? (dL_dsh != nullptr && leaves_dcol(prm, shs)) : true) {
+        for (int v0 = 0; v0 < views; v0 += kMaxGroup) {
+            const int kv = views - v0 < kMaxGroup ? views - v0 : kMaxGroup;
+            const size_t o = (size_t)prm->P * v0, og = pv * v0, oa = pva ? o : 0;      // oa: the group's first per-view opacity / colour gradient
+            hipLaunchKernelGGL(win ? preprocess_bwd_views_kernel<true> : preprocess_bwd_views_kernel<false>, grid, block, lds, s, *prm, kv,
+                               at(means3D, 3, og), shs != nullptr, at(scales, 3, og), at(rotations, 4, og), at(cov3D_precomp, 6, og),
+                               view_cams<kMaxGroup>(viewmatrix, projmatrix, campos, cs, v0, kv), geom_view(g, prm->P, v0),
+                               acc + D3GA_ACC_STRIDE * o, dL_dmeans3D + 3 * og, at(dL_dmeans2D, 3, o), at(dL_dopacity, 1, oa), dL_dsh,
+                               at(dL_dcolors, 3, oa), at(dL_dcov3D, 6, og), at(dL_dscales, 3, og), at(dL_drots, 4, og), v0 > 0, pv, pva);
         }
+        return check_launch(s, prm->debug);
     }
     // otherwise: one launch per view on ITS records; view 0 writes the gradients of the view-independent
     if (pva) return D3GA_E_CONFIG;                                 // (SH colours only come here: per-view appearance is refused above)
     if (shs && !dL_dcolors) return D3GA_E_NULL;
-    const size_t pv = prm->per_view_geometry ? (size_t)prm->P : 0;      // a batch of frames: every view has its own geometry and geometry gradients
     if (prm->factor_rows != 0 && prm->factor_rows < prm->P) return D3GA_E_SIZE;
     const size_t fr = prm->factor_rows > 0 ? (size_t)prm->factor_rows : (size_t)prm->P;      // rows between the views' SH factors
-    for (int v = 0; v < views; ++v) {
-        const size_t o = (size_t)prm->P * v, og = pv * v;
-        hipLaunchKernelGGL(win ? preprocess_bwd_kernel<true> : preprocess_bwd_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm, means3D + 3 * og,
-                           shs, scales ? scales + 3 * og : nullptr, rotations ? rotations + 4 * og : nullptr, viewmatrix + 16 * (size_t)v,
-                           projmatrix + 16 * (size_t)v, campos + (size_t)cam_stride * v, geom_view(g, prm->P, v), acc + D3GA_ACC_STRIDE * o,
-                           dL_dmeans3D + 3 * og, dL_dmeans2D ? dL_dmeans2D + 3 * o : nullptr, dL_dopacity, (float *)nullptr,
-                           shs ? dL_dcolors + 3 * fr * v : dL_dcolors, dL_dcov3D ? dL_dcov3D + 6 * og : nullptr,
-                           dL_dscales ? dL_dscales + 3 * og : nullptr, dL_drots ? dL_drots + 4 * og : nullptr,
-                           cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, v > 0 ? (pv ? 1 : 3) : 0);
-    }
+    for (int v = 0; v < views; ++v) launch_view(v, nullptr, shs ? dL_dcolors + 3 * fr * v : dL_dcolors, v > 0 ? (pv ? 1 : 3) : 0);
     D3GA_TRY(check_launch(s, prm->debug));
     if (shs && dL_dsh) {
-        const size_t lds2 = ((3 * prm->M) % 4 == 0) ? kShLdsBytes : 0;
-        hipLaunchKernelGGL(sh_grad_from_views_kernel, dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds2, s, prm->P, prm->M, prm->sh_degree,
-                           views, means3D, (int64_t)(3 * pv), dL_dcolors, (int64_t)(3 * fr), campos, (int64_t)cam_stride, 1.0f, dL_dsh);
+        hipLaunchKernelGGL(sh_grad_from_views_kernel, grid, block, lds_bytes(sh_staged(prm->M), kShLdsBytes), s, prm->P, prm->M,
+                           prm->sh_degree, views, means3D, (int64_t)(3 * pv), dL_dcolors, (int64_t)(3 * fr), campos, (int64_t)cs, 1.0f, dL_dsh);
         return check_launch(s, prm->debug);
     }
     return D3GA_OK;
@@ -1016,8 +811,7 @@ extern "C" int d3ga_sh_grad_from_views(int32_t P, int32_t M, int32_t sh_degree, 
     if (P == 0) return D3GA_OK;
     if (!means3D || !dL_dsh || (n_views > 0 && (!g_views || !campos_views))) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
-    const size_t lds = ((3 * M) % 4 == 0) ? kShLdsBytes : 0;
-    hipLaunchKernelGGL(sh_grad_from_views_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, P, M, sh_degree,
+    hipLaunchKernelGGL(sh_grad_from_views_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), lds_bytes(sh_staged(M), kShLdsBytes), s, P, M, sh_degree,
                        n_views, means3D, (int64_t)0, g_views, g_stride, campos_views, campos_stride, scale, dL_dsh);
     return check_launch(s, 0);
 }

@@ -78,7 +78,56 @@ D3GA_HD void sh_accumulate(const float B[16], const float *part, int k0, int k1,
     }
 }
 
-// R1 for Gaussian i.  Exactly one of (sh_row|sh_acc|colors_precomp), ((scales,rotations)|cov3D_precomp) is non-null.
+// One view's camera.  The only code that reads the camera-slot convention (d3ga.h): tanfovx <= 0 puts the two tangents behind
+// the position (campos[3], campos[4]); a WINDOWED slot (9 floats) adds the full raster's size (campos[5], campos[6]), which the
+// view projects with, and the window's origin in it (campos[7], campos[8]).
+struct ViewCam {
+    const float *vm, *pm, *cp;      // view matrix, projection matrix, camera row
+    float tanfovx, tanfovy;
+    int W, H;                       // the raster the view projects on
+    int ox, oy;                     // (windowed) the window's first pixel in that raster
+};
+D3GA_HD ViewCam view_cam(const d3ga_raster_params &prm, const float *vm, const float *pm, const float *cp, bool win) {
+    ViewCam c = {vm, pm, cp, prm.tanfovx, prm.tanfovy, prm.W, prm.H, 0, 0};
+    if (!(prm.tanfovx > 0.f)) { c.tanfovx = cp[3]; c.tanfovy = cp[4]; }
+    if (win) { c.W = (int)cp[5]; c.H = (int)cp[6]; c.ox = (int)cp[7]; c.oy = (int)cp[8]; }
+    return c;
+}
+// the cameras of up to K views of a batch, by value (kernel arguments)
+template <int K>
+struct ViewCams { const float *vm[K], *pm[K], *cp[K]; };
+
+// Records the preprocess forward leaves and the compositing backward accumulates (d3ga_internal.h: GeomBuf; d3ga.h: acc),
+// as plain pointers.  A culled Gaussian keeps an EMPTY tile rectangle (x = minx | miny << 16, y = maxx | maxy << 16).
+D3GA_HD bool rect_visible(uint32_t lo, uint32_t hi) { return ((hi & 0xffffu) > (lo & 0xffffu)) && ((hi >> 16) > (lo >> 16)); }
+// accumulator record j (D3GA_ACC_STRIDE floats, 64-byte aligned).  self_clearing (d3ga_raster_params::acc_self_clearing): the
+// caller keeps the buffer for the next backward -- leave the record as the untouched ones are, all zero (only records the
+// compositing backward wrote are written back: 48 of their 64 bytes)
+struct AccRec { float a[12]; };
+D3GA_HD AccRec acc_load(const float *acc, size_t j, bool self_clearing) {
+    float *p = (float *)__builtin_assume_aligned(const_cast<float *>(acc) + D3GA_ACC_STRIDE * j, 64);
+    AccRec r;
+    uint32_t any = 0;
+    for (int k = 0; k < 12; ++k) { r.a[k] = p[k]; any |= __builtin_bit_cast(uint32_t, r.a[k]); }
+    if (self_clearing && any)
+        for (int k = 0; k < 12; ++k) p[k] = 0.f;
+    return r;
+}
+// d(SH colour)/d(unit view direction) of record j: nine planes of `stride` floats (GeomBuf::dcol)
+D3GA_HD ShColJ dcol_load(const float *dcol, int64_t stride, size_t j) {
+    ShColJ c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    c.j0 = dcol[j]; c.j1 = dcol[stride + j]; c.j2 = dcol[2 * stride + j];
+    c.j3 = dcol[3 * stride + j]; c.j4 = dcol[4 * stride + j]; c.j5 = dcol[5 * stride + j];
+    c.j6 = dcol[6 * stride + j]; c.j7 = dcol[7 * stride + j]; c.j8 = dcol[8 * stride + j];
+    return c;
+}
+D3GA_HD void dcol_store(float *dcol, int64_t stride, size_t j, const ShColJ &c) {
+    dcol[j] = c.j0; dcol[stride + j] = c.j1; dcol[2 * stride + j] = c.j2;
+    dcol[3 * stride + j] = c.j3; dcol[4 * stride + j] = c.j4; dcol[5 * stride + j] = c.j5;
+    dcol[6 * stride + j] = c.j6; dcol[7 * stride + j] = c.j7; dcol[8 * stride + j] = c.j8;
+}
+
+// R1 for Gaussian i in the view `cam`.  Exactly one of (sh_row|sh_acc|colors_precomp), ((scales,rotations)|cov3D_precomp) is non-null.
 // sh_row points at THIS Gaussian's 3*M SH floats (in global memory or in an LDS staging row); alternatively pl.sh
 // holds the already evaluated sum_k Y_k(dir) * coeff_k (see sh_view_basis / sh_accumulate).
 // pl.c6 / pl.op: this Gaussian's covariance row and raw opacity if the caller has loaded them already (the kernel issues
@@ -92,10 +141,9 @@ struct PreLoaded {
     float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float op = 0.f;                        // raw opacity (with has_c6)
 };
-D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, int i, const float *means3D, const float *sh_row,
+D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D, const float *sh_row,
                               const float *colors_precomp, const float *opacities, const float *scales,
-                              const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
-                              const float *projmatrix, const float *campos, const PreLoaded pl = PreLoaded()) {
+                              const float *rotations, const float *cov3D_precomp, const PreLoaded pl = PreLoaded()) {
     PreOut o;
     const V3 mean = ld3(means3D, i);
     const float raw_opacity = pl.has_c6 ? pl.op : opacities[i];
@@ -109,7 +157,7 @@ D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, int i, const float 
                             rotations[4 * (size_t)i + 3]};
         cov3d_from_scale_rot(s, prm.scale_modifier, q, o.c6);
     }
-    o.sp = project_gaussian(mean, o.c6, viewmatrix, projmatrix, prm.W, prm.H, prm.tanfovx, prm.tanfovy, prm.antialiasing != 0);
+    o.sp = project_gaussian(mean, o.c6, cam.vm, cam.pm, cam.W, cam.H, cam.tanfovx, cam.tanfovy, prm.antialiasing != 0);
     o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.f;
     o.clampmask = 0;
     o.opacity = 0.f;
@@ -132,7 +180,7 @@ D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, int i, const float 
             acc[0] = pl.sh[0]; acc[1] = pl.sh[1]; acc[2] = pl.sh[2];
         } else {
             float B[16];
-            sh_view_basis(prm, means3D, i, campos, B);
+            sh_view_basis(prm, means3D, i, cam.cp, B);
             sh_accumulate(B, sh_row, 0, 16, (prm.sh_degree + 1) * (prm.sh_degree + 1), acc);
         }
         for (int c = 0; c < 3; ++c) {
@@ -144,77 +192,112 @@ D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, int i, const float 
     return o;
 }
 
-// R6 for Gaussian i.  a[12] = accumulated screen-space gradients (layout: d3ga.h, d3ga_raster_composite_bwd);
-// all-zero and visible=false for culled Gaussians.  Output pointers may be null where not applicable.
-// sh_row / dsh_row point at THIS Gaussian's 3*M floats (global memory or an LDS staging row; they may alias).
-D3GA_HD void preprocess_bwd_one(const d3ga_raster_params &prm, int i, bool visible, const float *means3D,
+// The same with the camera as the params give it (tangents and raster size already those of this view: the host check).
+D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, int i, const float *means3D, const float *sh_row,
+                              const float *colors_precomp, const float *opacities, const float *scales,
+                              const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                              const float *projmatrix, const float *campos, const PreLoaded pl = PreLoaded()) {
+    const ViewCam cam = {viewmatrix, projmatrix, campos, prm.tanfovx, prm.tanfovy, prm.W, prm.H, 0, 0};
+    return preprocess_one(prm, cam, i, means3D, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
+}
+
+// R6 of ONE Gaussian in ONE view: the gradients its screen-space accumulator record a[12] (layout: d3ga.h,
+// d3ga_raster_composite_bwd) sends to its mean and covariance, to its opacity (gop) and -- SH colours (sh) -- the clamp-masked
+// dL/dcolour gr and the view direction's SH basis B (the view's SH gradient row is B (x) gr).  Zero for a culled Gaussian, but
+// for gop.  The direction term of the mean's gradient comes from the forward's d(colour)/d(direction) jd (have_j) or from the
+// coefficient row sh_row.  c6: the covariance the forward projected; act_opacity: the opacity it stored (conic_o.w).
+// dsh_row (may be null, may alias sh_row): the view's SH gradient row B (x) gr is also written there, in the same walk over the
+// coefficients -- with the row written after the walk, the compiler hoists all 48 coefficient loads and the single-view
+// backward needs 22 more VGPRs (one occupancy step).
+struct BwdView { float gmean[3], g6[6], gr[3], B[16], gop; };
+D3GA_HD BwdView preprocess_bwd_view(const d3ga_raster_params &prm, const ViewCam &cam, bool visible, V3 mean, const float *c6,
+                                    const float *a, uint8_t clampmask, float act_opacity, bool sh, bool have_j, ShColJ jd,
+                                    const float *sh_row, float *dsh_row = nullptr) {
+    BwdView r;       // (the sums below in local arrays: accumulated in the struct, the single-view backward needs 12 more VGPRs)
+    float gmean[3] = {0.f, 0.f, 0.f}, g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    r.gr[0] = r.gr[1] = r.gr[2] = 0.f;
+    float aa = 1.0f;
+    if (visible) {
+        cov2d_bwd(mean, c6, cam.vm, cam.W, cam.H, cam.tanfovx, cam.tanfovy, a[3], a[4], a[5], g6, gmean,
+                  prm.antialiasing != 0, a[6], act_opacity, &aa);
+        project_bwd(mean, cam.pm, a[0], a[1], gmean);
+        // inverse depth (branch dr_aa): a[10] = dL/d(1/z) of this Gaussian, z its view-space depth; d(1/z)/dmean = -view_z / z^2
+        const float *vm = cam.vm;
+        const float z = vm[2] * mean.x + vm[6] * mean.y + vm[10] * mean.z + vm[14];
+        const float gz = -a[10] / (z * z);
+        gmean[0] += vm[2] * gz; gmean[1] += vm[6] * gz; gmean[2] += vm[10] * gz;
+    }
+    if (sh && visible) {
+        r.gr[0] = (clampmask & 1) ? 0.f : a[7]; r.gr[1] = (clampmask & 2) ? 0.f : a[8]; r.gr[2] = (clampmask & 4) ? 0.f : a[9];
+        const float *gr = r.gr;
+        float B[16];
+        const V3 d0 = mean - v3(cam.cp[0], cam.cp[1], cam.cp[2]);
+        const float inv = 1.0f / sqrtf(dot(d0, d0));
+        const float x = d0.x * inv, y = d0.y * inv, z = d0.z * inv;
+        sh_basis(prm.sh_degree, x, y, z, B);
+        const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1), nbM = prm.M;
+        float *out = dsh_row;
+        V3 gd = v3(0.f, 0.f, 0.f);
+        if (have_j) {                        // dL/d(dir) = J . (clamp-masked dL/dcolour): the coefficients are not read
+            gd = v3(jd.j0 * gr[0] + jd.j1 * gr[1] + jd.j2 * gr[2], jd.j3 * gr[0] + jd.j4 * gr[1] + jd.j5 * gr[2],
+                    jd.j6 * gr[0] + jd.j7 * gr[1] + jd.j8 * gr[2]);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                if (k < nb) { if (out) { out[3 * k] = B[k] * gr[0]; out[3 * k + 1] = B[k] * gr[1]; out[3 * k + 2] = B[k] * gr[2]; } }
+                else if (k < nbM && out) { out[3 * k] = 0.f; out[3 * k + 1] = 0.f; out[3 * k + 2] = 0.f; }
+            }
+        } else {
+            float Bx[16], By[16], Bz[16];
+            sh_basis_grad(prm.sh_degree, x, y, z, Bx, By, Bz);
+            const float *sh = sh_row;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {   // fixed trip count: keeps the basis arrays in registers
+                if (k < nb) {
+                    const float s0 = sh[3 * k], s1 = sh[3 * k + 1], s2 = sh[3 * k + 2];
+                    if (out) { out[3 * k] = B[k] * gr[0]; out[3 * k + 1] = B[k] * gr[1]; out[3 * k + 2] = B[k] * gr[2]; }
+                    const float w = s0 * gr[0] + s1 * gr[1] + s2 * gr[2];
+                    gd.x += Bx[k] * w; gd.y += By[k] * w; gd.z += Bz[k] * w;
+                } else if (k < nbM && out) {
+                    out[3 * k] = 0.f; out[3 * k + 1] = 0.f; out[3 * k + 2] = 0.f;
+                }
+            }
+        }
+        const V3 gm = normalize_bwd(d0, gd);
+        gmean[0] += gm.x; gmean[1] += gm.y; gmean[2] += gm.z;
+        for (int k = 0; k < 16; ++k) r.B[k] = B[k];
+    }
+    // sigmoid' = s (1 - s); antialiasing: the stored opacity is opacity x aa and a[6] is the gradient w.r.t. that product
+    const float op = act_opacity / aa, g_op = a[6] * aa;
+    for (int k = 0; k < 3; ++k) r.gmean[k] = gmean[k];
+    for (int k = 0; k < 6; ++k) r.g6[k] = g6[k];
+    r.gop = prm.opacity_activation == D3GA_OPACITY_SIGMOID ? g_op * op * (1.0f - op) : g_op;
+    return r;
+}
+
+// R6 for Gaussian i in one view.  a[12] = its accumulator record; all-zero and visible=false for culled Gaussians.  Output
+// pointers may be null where not applicable.  sh_row / dsh_row point at THIS Gaussian's 3*M floats (global memory or an LDS
+// staging row; they may alias).  have_j: jd = the forward's d(colour)/d(direction) of this Gaussian (then sh_row is not read).
+// accum: views > 0 of a batch (d3ga.h n_views): gradients of inputs the views SHARE are added to what the outputs hold -- bit 0:
+// opacity and a precomputed colour, bit 1: the geometry (mean, covariance | scale, rotation).
+D3GA_HD void preprocess_bwd_one(const d3ga_raster_params &prm, const ViewCam &cam, int i, bool visible, const float *means3D,
                                 const float *sh_row, const float *scales, const float *rotations,
-                                const float *viewmatrix, const float *projmatrix, const float *campos,
                                 const float *c6, uint8_t clampmask, const float *a, float *dL_dmeans3D,
                                 float *dL_dmeans2D, float *dL_dopacity, float *dsh_row, float *dL_dcolors,
                                 float *dL_dcov3D, float *dL_dscales, float *dL_drots, float act_opacity = 0.f,
-                                bool have_j = false, ShColJ jd = ShColJ(),      // have_j: jd.j0..j8 = the forward's d(colour)/d(direction) of this Gaussian (then sh_row is not read)
-                                int accum = 0) {      // views > 0 of a batch (d3ga.h n_views): gradients of inputs the views SHARE are added to what the outputs hold -- bit 0: opacity and a precomputed colour, bit 1: the geometry (mean, covariance | scale, rotation)
-    float gmean[3] = {0.f, 0.f, 0.f};
-    float g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const V3 mean = ld3(means3D, i);
-    const int nbM = prm.M;
-    float aa = 1.0f;
-    if (visible) {
-        cov2d_bwd(mean, c6, viewmatrix, prm.W, prm.H, prm.tanfovx, prm.tanfovy, a[3], a[4], a[5], g6, gmean,
-                  prm.antialiasing != 0, a[6], act_opacity, &aa);
-        project_bwd(mean, projmatrix, a[0], a[1], gmean);
-        // inverse depth (branch dr_aa): a[10] = dL/d(1/z) of this Gaussian, z its view-space depth; d(1/z)/dmean = -view_z / z^2
-        const float z = viewmatrix[2] * mean.x + viewmatrix[6] * mean.y + viewmatrix[10] * mean.z + viewmatrix[14];
-        const float gz = -a[10] / (z * z);
-        gmean[0] += viewmatrix[2] * gz; gmean[1] += viewmatrix[6] * gz; gmean[2] += viewmatrix[10] * gz;
-    }
+                                bool have_j = false, ShColJ jd = ShColJ(), int accum = 0) {
     // SH colour path (sh_row != null).  dsh_row == null selects the FACTORED output used by the view-sharded gradient
     // exchange (d3ga_sh_grad_from_views): the clamp-masked dL/dcolour is written to dL_dcolors instead of the rank-1
     // (basis x dL/dcolour) SH block; the view-direction term of dL/dmean is computed either way.
+    const BwdView r = preprocess_bwd_view(prm, cam, visible, ld3(means3D, i), c6, a, clampmask, act_opacity, sh_row != nullptr,
+                                          have_j, jd, sh_row, dsh_row);
     if (sh_row) {
         float *out = dsh_row;
         if (visible) {
-            const float gr[3] = {(clampmask & 1) ? 0.f : a[7], (clampmask & 2) ? 0.f : a[8],
-                                 (clampmask & 4) ? 0.f : a[9]};
-            const V3 d0 = mean - v3(campos[0], campos[1], campos[2]);
-            const float inv = 1.0f / sqrtf(dot(d0, d0));
-            const float x = d0.x * inv, y = d0.y * inv, z = d0.z * inv;
-            float B[16];
-            sh_basis(prm.sh_degree, x, y, z, B);
-            const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
-            V3 gd = v3(0.f, 0.f, 0.f);
-            if (have_j) {                    // dL/d(dir) = J . (clamp-masked dL/dcolour): the coefficients are not read
-                gd = v3(jd.j0 * gr[0] + jd.j1 * gr[1] + jd.j2 * gr[2], jd.j3 * gr[0] + jd.j4 * gr[1] + jd.j5 * gr[2],
-                        jd.j6 * gr[0] + jd.j7 * gr[1] + jd.j8 * gr[2]);
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    if (k < nb) { if (out) { out[3 * k] = B[k] * gr[0]; out[3 * k + 1] = B[k] * gr[1]; out[3 * k + 2] = B[k] * gr[2]; } }
-                    else if (k < nbM && out) { out[3 * k] = 0.f; out[3 * k + 1] = 0.f; out[3 * k + 2] = 0.f; }
-                }
-            } else {
-                float Bx[16], By[16], Bz[16];
-                sh_basis_grad(prm.sh_degree, x, y, z, Bx, By, Bz);
-                const float *sh = sh_row;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {   // fixed trip count: keeps the basis arrays in registers
-                    if (k < nb) {
-                        const float s0 = sh[3 * k], s1 = sh[3 * k + 1], s2 = sh[3 * k + 2];
-                        if (out) { out[3 * k] = B[k] * gr[0]; out[3 * k + 1] = B[k] * gr[1]; out[3 * k + 2] = B[k] * gr[2]; }
-                        const float w = s0 * gr[0] + s1 * gr[1] + s2 * gr[2];
-                        gd.x += Bx[k] * w; gd.y += By[k] * w; gd.z += Bz[k] * w;
-                    } else if (k < nbM && out) {
-                        out[3 * k] = 0.f; out[3 * k + 1] = 0.f; out[3 * k + 2] = 0.f;
-                    }
-                }
-            }
-            const V3 gm = normalize_bwd(d0, gd);
-            gmean[0] += gm.x; gmean[1] += gm.y; gmean[2] += gm.z;
             if (dL_dcolors) {
-                dL_dcolors[3 * (size_t)i] = gr[0]; dL_dcolors[3 * (size_t)i + 1] = gr[1]; dL_dcolors[3 * (size_t)i + 2] = gr[2];
+                dL_dcolors[3 * (size_t)i] = r.gr[0]; dL_dcolors[3 * (size_t)i + 1] = r.gr[1]; dL_dcolors[3 * (size_t)i + 2] = r.gr[2];
             }
         } else {
-            if (out) for (int k = 0; k < 3 * nbM; ++k) out[k] = 0.f;
+            if (out) for (int k = 0; k < 3 * prm.M; ++k) out[k] = 0.f;
             if (dL_dcolors) {
                 dL_dcolors[3 * (size_t)i] = 0.f; dL_dcolors[3 * (size_t)i + 1] = 0.f; dL_dcolors[3 * (size_t)i + 2] = 0.f;
             }
@@ -225,20 +308,14 @@ D3GA_HD void preprocess_bwd_one(const d3ga_raster_params &prm, int i, bool visib
     }
     {
         float *o = dL_dmeans3D + 3 * (size_t)i;
-        o[0] = (accum & 2) ? o[0] + (gmean[0]) : (gmean[0]); o[1] = (accum & 2) ? o[1] + (gmean[1]) : (gmean[1]); o[2] = (accum & 2) ? o[2] + (gmean[2]) : (gmean[2]);
+        o[0] = (accum & 2) ? o[0] + (r.gmean[0]) : (r.gmean[0]); o[1] = (accum & 2) ? o[1] + (r.gmean[1]) : (r.gmean[1]); o[2] = (accum & 2) ? o[2] + (r.gmean[2]) : (r.gmean[2]);
     }
     if (dL_dmeans2D) {                       // screen-space: per view
         dL_dmeans2D[3 * (size_t)i] = a[0]; dL_dmeans2D[3 * (size_t)i + 1] = a[1]; dL_dmeans2D[3 * (size_t)i + 2] = 0.f;
     }
-    // act_opacity: the activated opacity the forward stored (conic_o.w); sigmoid' = s (1 - s)
-    // (antialiasing: the stored opacity is opacity x aa; a[6] is the gradient w.r.t. that product)
-    if (dL_dopacity) {
-        const float op = act_opacity / aa, g_op = a[6] * aa;
-        const float g = prm.opacity_activation == D3GA_OPACITY_SIGMOID ? g_op * op * (1.0f - op) : g_op;
-        dL_dopacity[i] = (accum & 1) ? dL_dopacity[i] + g : g;
-    }
+    if (dL_dopacity) dL_dopacity[i] = (accum & 1) ? dL_dopacity[i] + r.gop : r.gop;
     if (dL_dcov3D) {
-        for (int k = 0; k < 6; ++k) dL_dcov3D[6 * (size_t)i + k] = (accum & 2) ? dL_dcov3D[6 * (size_t)i + k] + (g6[k]) : (g6[k]);
+        for (int k = 0; k < 6; ++k) dL_dcov3D[6 * (size_t)i + k] = (accum & 2) ? dL_dcov3D[6 * (size_t)i + k] + (r.g6[k]) : (r.g6[k]);
     }
     if (dL_dscales && dL_drots) {
         float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
@@ -246,10 +323,125 @@ D3GA_HD void preprocess_bwd_one(const d3ga_raster_params &prm, int i, bool visib
             const float s[3] = {scales[3 * (size_t)i], scales[3 * (size_t)i + 1], scales[3 * (size_t)i + 2]};
             const float q[4] = {rotations[4 * (size_t)i], rotations[4 * (size_t)i + 1], rotations[4 * (size_t)i + 2],
                                 rotations[4 * (size_t)i + 3]};
-            cov3d_from_scale_rot_bwd(s, prm.scale_modifier, q, g6, gs, gq);
+            cov3d_from_scale_rot_bwd(s, prm.scale_modifier, q, r.g6, gs, gq);
         }
         for (int k = 0; k < 3; ++k) dL_dscales[3 * (size_t)i + k] = (accum & 2) ? dL_dscales[3 * (size_t)i + k] + (gs[k]) : (gs[k]);
         for (int k = 0; k < 4; ++k) dL_drots[4 * (size_t)i + k] = (accum & 2) ? dL_drots[4 * (size_t)i + k] + (gq[k]) : (gq[k]);
+    }
+}
+
+// The same with the camera as the params give it (see preprocess_one).
+D3GA_HD void preprocess_bwd_one(const d3ga_raster_params &prm, int i, bool visible, const float *means3D,
+                                const float *sh_row, const float *scales, const float *rotations,
+                                const float *viewmatrix, const float *projmatrix, const float *campos,
+                                const float *c6, uint8_t clampmask, const float *a, float *dL_dmeans3D,
+                                float *dL_dmeans2D, float *dL_dopacity, float *dsh_row, float *dL_dcolors,
+                                float *dL_dcov3D, float *dL_dscales, float *dL_drots, float act_opacity = 0.f,
+                                bool have_j = false, ShColJ jd = ShColJ(), int accum = 0) {
+    const ViewCam cam = {viewmatrix, projmatrix, campos, prm.tanfovx, prm.tanfovy, prm.W, prm.H, 0, 0};
+    preprocess_bwd_one(prm, cam, i, visible, means3D, sh_row, scales, rotations, c6, clampmask, a, dL_dmeans3D, dL_dmeans2D,
+                       dL_dopacity, dsh_row, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, act_opacity, have_j, jd, accum);
+}
+
+// The records a batch's backward reads per view (GeomBuf of the batch's first view, acc of that view): record j = v P + i.
+struct ViewRecs {
+    const uint32_t *rect;        // 2 words per record
+    const float *acc;            // D3GA_ACC_STRIDE floats per record
+    const uint8_t *clamped;
+    const float *conic_o;        // 4 floats per record: the stored opacity is [3]
+    const float *dcol;           // SH colours: the forward's d(colour)/d(direction), nine planes of dcol_stride floats
+    int64_t dcol_stride;
+};
+// R6 of Gaussian i over the kv views of a batch that share their geometry (d3ga.h: n_views), in ONE walk: per view its records and
+// preprocess_bwd_view, the gradients of the shared inputs summed in registers, views added in ascending order (so: the same sums as kv
+// calls of preprocess_bwd_one with `accum`), every output written ONCE.  The SH gradient row, sum_v B_v (x) gr_v, goes to dsh_row
+// (null: not wanted); SH colours need the forward's dcol.  cov6: the covariance rows the forward projected.  pv: records between
+// the views' geometry AND geometry gradients -- 0: shared (summed), P: a batch of frames (written per view).  pva: per-view
+// appearance -- dL/dopacity and dL/dcolour are written per view at record j (zeros where the view culled the Gaussian), not summed.
+// accum: add to every output that is not per view (a later group of a large batch).
+template <int K>
+D3GA_HD void preprocess_bwd_views_one(const d3ga_raster_params &prm, int i, int kv, bool win, const ViewCams<K> &cams,
+                                      const ViewRecs &rec, const float *means3D, const float *cov6, const float *scales,
+                                      const float *rotations, bool sh_path, size_t pv, bool pva, bool accum,
+                                      float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity, float *dL_dcolors,
+                                      float *dL_dcov3D, float *dL_dscales, float *dL_drots, float *dsh_row) {
+    V3 mean = ld3(means3D, i);
+    float c6[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c6[k] = cov6[6 * (size_t)i + k];   // (from scale / rotation: view 0's record -- the same in every view of shared geometry)
+    float gmean[3] = {0.f, 0.f, 0.f}, g6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gop = 0.f, gcol[3] = {0.f, 0.f, 0.f};
+    auto put = [&](float *p, float v, bool add) { *p = add ? *p + v : v; };
+    auto geometry_out = [&](size_t og, const float (&gm)[3], const float (&g)[6], bool vis, bool add) {     // og: record offset of the geometry gradients
+        for (int k = 0; k < 3; ++k) put(dL_dmeans3D + 3 * (og + i) + k, gm[k], add);
+        if (dL_dcov3D)
+            for (int k = 0; k < 6; ++k) put(dL_dcov3D + 6 * (og + i) + k, g[k], add);
+        if (dL_dscales && dL_drots) {
+            float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
+            if (vis) {
+                const float sc[3] = {scales[3 * (og + i)], scales[3 * (og + i) + 1], scales[3 * (og + i) + 2]};
+                const float q[4] = {rotations[4 * (og + i)], rotations[4 * (og + i) + 1], rotations[4 * (og + i) + 2], rotations[4 * (og + i) + 3]};
+                cov3d_from_scale_rot_bwd(sc, prm.scale_modifier, q, g, gs, gq);      // (linear in g: a sum over views goes through once)
+            }
+            for (int k = 0; k < 3; ++k) put(dL_dscales + 3 * (og + i) + k, gs[k], add);
+            for (int k = 0; k < 4; ++k) put(dL_drots + 4 * (og + i) + k, gq[k], add);
+        }
+    };
+    const float zero3[3] = {0.f, 0.f, 0.f}, zero6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
+    float out[48];
+#pragma unroll
+    for (int k = 0; k < 48; ++k) out[k] = 0.f;
+    for (int v = 0; v < kv; ++v) {
+        const size_t j = (size_t)prm.P * v + i;                          // this view's record
+        const uint32_t r0 = rec.rect[2 * j], r1 = rec.rect[2 * j + 1];
+        const AccRec ar = acc_load(rec.acc, j, prm.acc_self_clearing);
+        const float *a = ar.a;
+        const bool visible = rect_visible(r0, r1);
+        if (dL_dmeans2D) {                                                // screen-space: per view
+            float *m2 = dL_dmeans2D + 3 * j;
+            m2[0] = visible ? a[0] : 0.f; m2[1] = visible ? a[1] : 0.f; m2[2] = 0.f;
+        }
+        if (!visible) {
+            if (pv) geometry_out(pv * v, zero3, zero6, false, false);      // a batch of frames: every view's geometry gradients are written
+            if (pva) {                                                     // ... and per-view appearance every view's opacity / colour gradients
+                if (dL_dopacity) dL_dopacity[j] = 0.f;
+                if (dL_dcolors) { dL_dcolors[3 * j] = 0.f; dL_dcolors[3 * j + 1] = 0.f; dL_dcolors[3 * j + 2] = 0.f; }
+            }
+            continue;
+        }
+        if (pv) {                                                        // this view's own geometry
+            mean = ld3(means3D + 3 * pv * v, i);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c6[k] = cov6[6 * (pv * v + i) + k];
+        }
+        const ViewCam cam = view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], win);
+        const BwdView r = preprocess_bwd_view(prm, cam, true, mean, c6, a, rec.clamped[j], rec.conic_o[4 * j + 3], sh_path, true,
+                                              sh_path ? dcol_load(rec.dcol, rec.dcol_stride, j) : ShColJ(), nullptr);
+        if (sh_path) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < nb) { out[3 * k] += r.B[k] * r.gr[0]; out[3 * k + 1] += r.B[k] * r.gr[1]; out[3 * k + 2] += r.B[k] * r.gr[2]; }
+        } else if (pva) {
+            if (dL_dcolors) { dL_dcolors[3 * j] = a[7]; dL_dcolors[3 * j + 1] = a[8]; dL_dcolors[3 * j + 2] = a[9]; }
+        } else {
+            gcol[0] += a[7]; gcol[1] += a[8]; gcol[2] += a[9];
+        }
+        if (!pva) gop += r.gop;
+        else if (dL_dopacity) dL_dopacity[j] = r.gop;
+        if (pv) geometry_out(pv * v, r.gmean, r.g6, true, false);
+        else {
+            gmean[0] += r.gmean[0]; gmean[1] += r.gmean[1]; gmean[2] += r.gmean[2];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) g6[k] += r.g6[k];
+        }
+    }
+    if (!pv) geometry_out(0, gmean, g6, true, accum);
+    if (dL_dopacity && !pva) put(dL_dopacity + i, gop, accum);
+    if (!sh_path && !pva && dL_dcolors) { put(dL_dcolors + 3 * (size_t)i, gcol[0], accum); put(dL_dcolors + 3 * (size_t)i + 1, gcol[1], accum); put(dL_dcolors + 3 * (size_t)i + 2, gcol[2], accum); }
+    if (sh_path && dsh_row) {
+#pragma unroll
+        for (int k = 0; k < 48; ++k)
+            if (k < 3 * prm.M) dsh_row[k] = out[k];
     }
 }
 

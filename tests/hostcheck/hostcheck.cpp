@@ -130,4 +130,46 @@ void hc_preprocess_bwd(const d3ga_raster_params *prm, const float *means3D, cons
     }
 }
 
+// the view-batched backward's per-Gaussian walk (preprocess_bwd_views_one) over kv <= 8 views: records j = v P + i as the
+// forward leaves them -- rect (kv P, 2) packed tile rectangles, acc (kv P, 16), clamped (kv P), conic_o (kv P, 4), dcol (9, kv P)
+// planes (SH colours) --, cameras every 16 / cam_stride floats, dL_dsh (P, M, 3) or null
+void hc_preprocess_bwd_views(const d3ga_raster_params *prm, int kv, const float *means3D, const float *cov6, const float *scales,
+                             const float *rots, const float *view, const float *proj, const float *campos, int cam_stride,
+                             const uint32_t *rect, const float *acc, const uint8_t *clamped, const float *conic_o, const float *dcol,
+                             int sh_path, int64_t pv, int pva, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity,
+                             float *dL_dsh, float *dL_dcolors, float *dL_dcov3D, float *dL_dscales, float *dL_drots) {
+    ViewCams<8> cams;
+    for (int v = 0; v < 8; ++v) {
+        const int w = v < kv ? v : 0;
+        cams.vm[v] = view + 16 * w; cams.pm[v] = proj + 16 * w; cams.cp[v] = campos + cam_stride * w;
+    }
+    const ViewRecs rec = {rect, acc, clamped, conic_o, dcol, (int64_t)prm->P * kv};
+    for (int i = 0; i < prm->P; ++i)
+        preprocess_bwd_views_one(*prm, i, kv, false, cams, rec, means3D, cov6, scales, rots, sh_path != 0, (size_t)pv, pva != 0, false,
+                                 dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots,
+                                 dL_dsh ? dL_dsh + (size_t)3 * prm->M * i : nullptr);
+}
+
+// one view of a batch through the single-view backward (preprocess_bwd_one) on the same records as hc_preprocess_bwd_views:
+// record j = v P + i; `accum` as the per-view launches pass it; dcol: take d(colour)/d(direction) from the planes
+void hc_preprocess_bwd_view(const d3ga_raster_params *prm, int kv, int v, const float *means3D, const float *cov6, const float *scales,
+                            const float *rots, const float *view, const float *proj, const float *campos, const uint32_t *rect,
+                            const float *acc, const uint8_t *clamped, const float *conic_o, const float *dcol, const float *shs,
+                            float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh, float *dL_dcolors,
+                            float *dL_dcov3D, float *dL_dscales, float *dL_drots, int accum) {
+    const ViewCam cam = view_cam(*prm, view, proj, campos, false);
+    const float zeros[12] = {0};
+    const int64_t stride = (int64_t)prm->P * kv;
+    for (int i = 0; i < prm->P; ++i) {
+        const size_t j = (size_t)prm->P * v + i;
+        const bool vis = rect_visible(rect[2 * j], rect[2 * j + 1]);
+        float c6[6];
+        for (int k = 0; k < 6; ++k) c6[k] = vis ? cov6[6 * (size_t)i + k] : 0.f;
+        preprocess_bwd_one(*prm, cam, i, vis, means3D, shs ? shs + (size_t)3 * prm->M * i : nullptr, scales, rots, c6, clamped[j],
+                           vis ? acc + D3GA_ACC_STRIDE * j : zeros, dL_dmeans3D, dL_dmeans2D, dL_dopacity,
+                           dL_dsh ? dL_dsh + (size_t)3 * prm->M * i : nullptr, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots,
+                           vis ? conic_o[4 * j + 3] : 0.f, dcol != nullptr, dcol ? dcol_load(dcol, stride, j) : ShColJ(), accum);
+    }
+}
+
 }  // extern "C"

@@ -227,3 +227,88 @@ def test_preprocess_backward_with_clamped_sh_and_frustum_edge(hostcheck):
     prm = _prm(inp, 16, 2)
     prm.tanfovx *= 0.25                    # narrow guard band: many Gaussians are clamped in x
     _bwd_case(hostcheck, inp, prm, use_sh=True, from_sr=False, seed=4)
+
+
+def _views_records(hostcheck, prm, views, rng, means, cov=None, scales=None, rots=None, shs=None, colors=None):
+    """Forward records of k views (record j = v P + i) as preprocess leaves them, plus seeded accumulator and dcol planes."""
+    P, k = prm.P, len(views)
+    rect, clamped, conic_o, cov3D = (np.zeros((k * P, 2), np.uint32), np.zeros(k * P, np.uint8), np.zeros((k * P, 4), np.float32),
+                                     np.zeros((k * P, 6), np.float32))
+    for v, inp in enumerate(views):
+        sl = slice(v * P, (v + 1) * P)
+        o = _run_pre(hostcheck, dict(inp, means3D=torch.from_numpy(means[v])), prm, shs=shs, colors=colors, cov=cov[v] if cov is not None else None,
+                     scales=scales[v] if scales is not None else None, rots=rots[v] if rots is not None else None)
+        r = o["rect"].astype(np.uint32)
+        rect[sl] = np.stack([r[:, 0] | (r[:, 1] << 16), r[:, 2] | (r[:, 3] << 16)], 1)
+        clamped[sl], conic_o[sl], cov3D[sl] = o["clamped"], o["conic_o"], o["cov3D"]
+    rect[rng.random(k * P) < 0.3] = 0                  # culled in that view (an empty rectangle), visible in others
+    acc = rng.normal(size=(k * P, 16)).astype(np.float32)
+    acc[:, [2, 11, 12, 13, 14, 15]] = 0
+    dcol = rng.normal(size=(9, k * P)).astype(np.float32)
+    return rect, acc, clamped, conic_o, cov3D, dcol
+
+
+def test_preprocess_backward_views_body_matches_single_view(hostcheck):
+    """The view-batched backward's per-Gaussian walk against k calls of the single-view backward, views added in ascending
+    order as the per-view launches add them.  Both form the same sums in the same order (no contraction on the host): every
+    gradient is bit-identical, except (scale, rotation), which the walk maps ONCE from the summed covariance gradient while the
+    single-view calls map every view's and add -- a linear map applied before or after a float sum, so those two differ by
+    rounding only: within 1e-5 of the largest element."""
+    f = ctypes.c_float
+    cases = [dict(k=3, sh=True), dict(k=4, sh=False, sr=True), dict(k=2, sh=False, frames=True, sr=True),
+             dict(k=3, sh=False, pva=True), dict(k=5, sh=True, frames=True)]
+    for n, c in enumerate(cases):
+        k, sh, sr, frames, pva = c["k"], c["sh"], c.get("sr", False), c.get("frames", False), c.get("pva", False)
+        views = [scene_inputs("T1", scale_mult=2.0, azimuth=0.4 + 0.9 * v) for v in range(k)]
+        inp = views[0]
+        prm = _prm(inp, 16 if sh else 0, 3 if sh else 0, mod=1.1)
+        prm.n_views, prm.per_view_geometry, prm.per_view_appearance = k, int(frames), int(pva)
+        P, rng = prm.P, np.random.default_rng(20 + n)
+        kg = k if frames else 1                                    # geometry records (a batch of frames: one per view)
+        means = np.stack([_np(inp["means3D"]) + (0.02 * v * rng.normal(size=(P, 3)).astype(np.float32) if frames else 0)
+                          for v in range(k)]).astype(np.float32)
+        q = _np(torch.nn.functional.normalize(inp["scene"]["rotation"]))
+        scales = np.stack([_np(inp["scales"])] * k) if sr else None
+        rots = np.stack([q] * k) if sr else None
+        cov = None if sr else np.stack([_np(inp["cov6"])] * k)
+        shs = _np(inp["shs"]) if sh else None
+        rect, acc, clamped, conic_o, cov3D, dcol = _views_records(hostcheck, prm, views, rng, means, cov=cov, scales=scales, rots=rots,
+                                                                  shs=shs, colors=None if sh else _np(inp["rgb"]))
+        vis = (rect[:, 1] & 0xffff) > (rect[:, 0] & 0xffff)
+        assert vis.any() and not vis.all() and (vis.reshape(k, P).any(0) & ~vis.reshape(k, P).all(0)).any()   # culled in some views only
+        cov6 = np.ascontiguousarray((cov.reshape(-1, 6) if cov is not None else cov3D)[: kg * P])
+        view = np.stack([_np(x["view"]) for x in views]); proj = np.stack([_np(x["proj"]) for x in views])
+        campos = np.stack([_np(x["campos"]) for x in views])
+        na = k if pva else 1                                       # appearance gradient records
+        def outs():
+            return dict(m3=np.zeros((kg * P, 3), np.float32), m2=np.zeros((k * P, 3), np.float32), op=np.zeros(na * P, np.float32),
+                        sh=np.zeros((P, 16, 3), np.float32) if sh else None, col=None if sh else np.zeros((na * P, 3), np.float32),
+                        cov=None if sr else np.zeros((kg * P, 6), np.float32),
+                        sc=np.zeros((kg * P, 3), np.float32) if sr else None, ro=np.zeros((kg * P, 4), np.float32) if sr else None)
+        a = outs()
+        hostcheck.hc_preprocess_bwd_views(ctypes.byref(prm), k, ptr(means), ptr(cov6), ptr(scales), ptr(rots), ptr(view), ptr(proj),
+                                          ptr(campos), 3, ptr(rect), ptr(acc), ptr(clamped), ptr(conic_o), ptr(dcol), int(sh),
+                                          ctypes.c_int64(P if frames else 0), int(pva), ptr(a["m3"]), ptr(a["m2"]), ptr(a["op"]),
+                                          ptr(a["sh"]), ptr(a["col"]), ptr(a["cov"]), ptr(a["sc"]), ptr(a["ro"]))
+        b = outs()
+        sh_sum = np.zeros((P, 16, 3), np.float32)
+        for v in range(k):
+            g, ap = (v if frames else 0) * P, (v if pva else 0) * P      # geometry / appearance record offsets
+            row = np.zeros((P, 16, 3), np.float32) if sh else None
+            def o(x, n, off):
+                return None if x is None else ptr(x[off:]) if n == 1 else x[off:].ctypes.data_as(ctypes.c_void_p)
+            accum = 0 if v == 0 else (0 if pva else 1) | (0 if frames else 2)
+            hostcheck.hc_preprocess_bwd_view(ctypes.byref(prm), k, v, ptr(means[v]), ptr(cov6[g:]), ptr(scales[v] if sr else None),
+                                             ptr(rots[v] if sr else None), ptr(view[v]), ptr(proj[v]), ptr(campos[v]), ptr(rect), ptr(acc),
+                                             ptr(clamped), ptr(conic_o), ptr(dcol) if sh else None, ptr(shs), o(b["m3"], 3, g),
+                                             o(b["m2"], 3, v * P), o(b["op"], 1, ap), ptr(row), o(b["col"], 3, ap), o(b["cov"], 6, g),
+                                             o(b["sc"], 3, g), o(b["ro"], 4, g), accum)
+            if sh:
+                sh_sum += row
+        b["sh"] = sh_sum if sh else None
+        for key in ("m3", "m2", "op", "sh", "col", "cov"):
+            if a[key] is not None:
+                np.testing.assert_array_equal(a[key], b[key], err_msg=f"case {c}: {key}")
+        if sr:
+            for key in ("sc", "ro"):
+                assert rel_err(a[key], b[key]) < 1e-5, (c, key, rel_err(a[key], b[key]))
