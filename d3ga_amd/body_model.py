@@ -19,7 +19,8 @@ Pose vectors, (B, NUM_POSES) or the full (B, 3J):
              [body 0:66 | left-hand PCA 66:72 | right-hand PCA 72:78 | jaw, left eye, right eye 78:87]
            hand = PCA coefficients . hands_components[:6] (+ hands_mean unless use_flat_mean);
            the full 165 is the joint order [body 66 | jaw, leye, reye 9 | left hand 45 | right hand 45]
-           (datasets/actorshq_dataset.py:59).
+           (datasets/actorshq_dataset.py:59).  num_pca_comps is 0..45; with 45 the compact width is 165 as well, and a
+           165-wide pose is then read as the full layout (a 3J-wide pose always is).
 
 Per frame: R_j = Rodrigues(theta_j) (t = |theta_j + 1e-8|), pose feature pf = (R_j - I), j >= 1, row-major;
 bs = shapedirs [beta; psi] + posedirs pf (= v_posed - v_template); rest joints J = J_regressor (v_template + shapedirs
@@ -126,19 +127,23 @@ def prepare(data, model_type="smplx", num_pca_comps=6, use_pca=True, use_flat_me
     miss = [k for k in need if k not in data]
     if miss:
         raise ValueError(f"SMPL model data lacks {miss}")
+    if not 0 <= num_pca_comps <= 45:
+        raise ValueError(f"num_pca_comps={num_pca_comps}: the hand PCA has 45 components per hand (0..45)")
+    parents = np.asarray(data["kintree_table"]).astype(np.int64)[0].copy()
+    parents[0] = -1
+    J = len(parents)
+    if J > _lib.BODY_MAX_JOINTS:
+        raise ValueError(f"{J} joints: the kernels take at most {_lib.BODY_MAX_JOINTS}")
+    if J < 2:
+        raise ValueError(f"{J} joint: the kernels take at least 2 (a rigid body is the global Rh / Th of any model)")
     vt = _dense(data["v_template"])
     V = vt.shape[0]
     sd = _dense(data["shapedirs"]).reshape(V, 3, -1)
     pd = _dense(data["posedirs"]).reshape(V, 3, -1)
     Jreg = _dense(data["J_regressor"])
     W = _dense(data["weights"])
-    parents = np.asarray(data["kintree_table"]).astype(np.int64)[0].copy()
-    parents[0] = -1
-    J = len(parents)
     if Jreg.shape != (J, V) or W.shape != (V, J) or pd.shape[2] != 9 * (J - 1):
         raise ValueError(f"inconsistent SMPL model: V={V}, J={J}, J_regressor {Jreg.shape}, weights {W.shape}, posedirs {pd.shape}")
-    if J > _lib.BODY_MAX_JOINTS:
-        raise ValueError(f"{J} joints: the kernels take at most {_lib.BODY_MAX_JOINTS}")
     S = sd.shape[2]
     if model_type == "smplx":
         if S == 400:
@@ -219,7 +224,10 @@ class SMPLlayer(torch.nn.Module):
         self.register_buffer("weights", torch.from_numpy(m["weights"]))
         self.register_buffer("J_regressor", torch.from_numpy(m["J_regressor"]))
         for k in _KERNEL_BUFFERS:
-            self.register_buffer("bm_" + k, torch.from_numpy(np.ascontiguousarray(m[k])) if k in m else None, persistent=False)
+            a = m.get(k)
+            if a is not None and a.size == 0:       # no skin weight at all: an empty tensor's device pointer is NULL, which
+                a = np.zeros(1, a.dtype)            # the C ABI refuses; the empty CSR ranges never read this element
+            self.register_buffer("bm_" + k, None if a is None else torch.from_numpy(np.ascontiguousarray(a)), persistent=False)
         self._struct = None
         self._struct_key = None
         self._kp_regressor = None
@@ -229,6 +237,11 @@ class SMPLlayer(torch.nn.Module):
         """struct d3ga_body_model over the current device buffers (rebuilt when the module moves)."""
         key = tuple(t.data_ptr() if t is not None else 0 for t in [self.v_template] + [getattr(self, "bm_" + k) for k in _KERNEL_BUFFERS])
         if key != self._struct_key:
+            bufs = [("v_template", self.v_template)] + [("bm_" + k, getattr(self, "bm_" + k)) for k in _KERNEL_BUFFERS]
+            bad = [f"{k} {t.dtype}" for k, t in bufs if t is not None and t.dtype not in (torch.float32, torch.int32)]
+            if bad:
+                raise TypeError(f"SMPLlayer: the kernels read float32 model buffers, these are not: {', '.join(bad)}.  "
+                                "Keep the layer in float32 (no .double() / .half()); the inputs may be of any float dtype.")
             s = _lib.BodyModel(V=self.V, J=self.J, n_shape=self.n_shape, n_expr=self.n_expr, n_hand_pca=self.n_hand_pca,
                                ld=self.ld, n_levels=self.n_levels, reserved=0)
             s.v_template = self.v_template.data_ptr()
@@ -259,6 +272,7 @@ class SMPLlayer(torch.nn.Module):
     def forward(self, poses, shapes, Rh=None, Th=None, expression=None, return_verts=True, **kw):
         if poses.dim() != 2 or poses.shape[1] not in (self.NUM_POSES, 3 * self.J):
             raise ValueError(f"SMPLlayer: poses must be (B,{self.NUM_POSES}) or (B,{3 * self.J}), got {tuple(poses.shape)}")
+        self.model_struct()                   # refuses buffers that are not float32 before anything is launched
         B = poses.shape[0]
         shapes = self._coef(shapes, self.n_shape, B, "shapes")
         if shapes is None:

@@ -74,8 +74,9 @@ __device__ __forceinline__ void block_sum(float (&v)[N], float *red /* W * N */,
 
 __device__ __forceinline__ int n_coef(const d3ga_body_model &m) { return m.n_shape + m.n_expr; }
 __device__ __forceinline__ int n_rows(const d3ga_body_model &m) { return n_coef(m) + 9 * (m.J - 1); }
+// A 3J-wide pose is the full layout even when 75 + 2 n_hand_pca is 3J too (45 components): it is always accepted as is.
 __device__ __forceinline__ bool compact_layout(const d3ga_body_model &m, int pw) {
-    return m.n_hand_pca > 0 && pw == 75 + 2 * m.n_hand_pca;
+    return m.n_hand_pca > 0 && pw == 75 + 2 * m.n_hand_pca && pw != 3 * m.J;
 }
 
 // The kinematic tree and the joint shape directions in LDS: the level loops then wait on no global load.
@@ -581,9 +582,9 @@ __global__ __launch_bounds__(kBlock) void pose_bwd_kernel(d3ga_body_model m, int
 
 static int body_check(const d3ga_body_model *m, int B, int pw) {
     if (!m) return D3GA_E_NULL;
-    if (B < 0 || m->V <= 0 || m->J <= 0 || m->J > D3GA_BODY_MAX_JOINTS || m->n_shape < 0 || m->n_expr < 0 ||
-        m->n_shape + m->n_expr > D3GA_BODY_MAX_SHAPE || m->n_hand_pca < 0 || m->n_levels <= 0 || m->n_levels > m->J ||
-        m->ld < 3 * m->V || m->ld % D3GA_BODY_LD_ALIGN)
+    if (B < 0 || m->V <= 0 || m->J < 2 || m->J > D3GA_BODY_MAX_JOINTS || m->n_shape < 0 || m->n_expr < 0 ||
+        m->n_shape + m->n_expr > D3GA_BODY_MAX_SHAPE || m->n_hand_pca < 0 || m->n_hand_pca > 45 || m->n_levels <= 0 ||
+        m->n_levels > m->J || m->ld < 3 * m->V || m->ld % D3GA_BODY_LD_ALIGN)
         return D3GA_E_SIZE;
     if (pw != 3 * m->J && !(m->n_hand_pca > 0 && m->J == 55 && pw == 75 + 2 * m->n_hand_pca)) return D3GA_E_CONFIG;
     if (!m->v_template || !m->dirs || !m->w_ptr || !m->w_joint || !m->w_val || !m->wt_ptr || !m->wt_vert || !m->wt_val ||

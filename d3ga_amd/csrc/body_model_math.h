@@ -1,7 +1,20 @@
 // body_model_math.h -- per-element math of the SMPL(-X) body model kernels (body_model.hip): Rodrigues forward and
-// backward, 3x3 products and the rigid 4x4 compose.  Row-major 3x3 matrices in float[9].
+// backward, 3x3 products and the rigid 4x4 compose.  Row-major 3x3 matrices in float[9].  Also compiled for the host by the
+// arithmetic self-check in tests/hostcheck (g++, D3GA_HD = static inline), as d3ga_math.h is.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#else
+#include <cmath>
+#endif
+
+#ifndef D3GA_HD
+#ifdef __HIPCC__
+#define D3GA_HD __host__ __device__ __forceinline__
+#else
+#define D3GA_HD static inline
+#endif
+#endif
 
 namespace d3ga {
 namespace bm {
@@ -9,7 +22,7 @@ namespace bm {
 constexpr float kRodEps = 1e-8f;   // t = |r + eps| (d3ga_amd.cage_deform.batch_rodrigues): keeps the zero rotation finite
 
 // R = I + sin(t) K + (1 - cos t) K^2, t = |r + eps|, K = [r / t]x.  1 - cos t is formed as 2 sin^2(t/2) (no cancellation).
-__device__ __forceinline__ void rodrigues(const float r[3], float R[9]) {
+D3GA_HD void rodrigues(const float r[3], float R[9]) {
     const float ex = r[0] + kRodEps, ey = r[1] + kRodEps, ez = r[2] + kRodEps;
     const float t = sqrtf(ex * ex + ey * ey + ez * ez);
     const float kx = r[0] / t, ky = r[1] / t, kz = r[2] / t;
@@ -22,7 +35,7 @@ __device__ __forceinline__ void rodrigues(const float r[3], float R[9]) {
 }
 
 // dL/dr from G = dL/dR of rodrigues(r)
-__device__ __forceinline__ void rodrigues_bwd(const float r[3], const float G[9], float dr[3]) {
+D3GA_HD void rodrigues_bwd(const float r[3], const float G[9], float dr[3]) {
     const float ex = r[0] + kRodEps, ey = r[1] + kRodEps, ez = r[2] + kRodEps;
     const float t = sqrtf(ex * ex + ey * ey + ez * ez);
     const float k[3] = {r[0] / t, r[1] / t, r[2] / t};
@@ -57,26 +70,25 @@ __device__ __forceinline__ void rodrigues_bwd(const float r[3], const float G[9]
     dr[2] = dk[2] / t + dt * ez / t;
 }
 
-__device__ __forceinline__ void mm3(const float a[9], const float b[9], float o[9]) {
+D3GA_HD void mm3(const float a[9], const float b[9], float o[9]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
 }
 
-__device__ __forceinline__ void mv3(const float a[9], const float v[3], float o[3]) {
+D3GA_HD void mv3(const float a[9], const float v[3], float o[3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[i] = a[3 * i] * v[0] + a[3 * i + 1] * v[1] + a[3 * i + 2] * v[2];
 }
 
-__device__ __forceinline__ void mtv3(const float a[9], const float v[3], float o[3]) {    // a^T v
+D3GA_HD void mtv3(const float a[9], const float v[3], float o[3]) {    // a^T v
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[i] = a[i] * v[0] + a[3 + i] * v[1] + a[6 + i] * v[2];
 }
 
 // rigid compose [Rp | tp] . [R | t] -> [Rp R | Rp t + tp]
-__device__ __forceinline__ void compose(const float Rp[9], const float tp[3], const float R[9], const float t[3], float Ro[9],
-                                        float to[3]) {
+D3GA_HD void compose(const float Rp[9], const float tp[3], const float R[9], const float t[3], float Ro[9], float to[3]) {
     mm3(Rp, R, Ro);
     mv3(Rp, t, to);
     to[0] += tp[0]; to[1] += tp[1]; to[2] += tp[2];

@@ -240,18 +240,29 @@ def make_scene(wl, seed=17):
 SMPLX_SIZES = {"smplx": (10475, 55), "smpl": (6890, 24)}
 
 
-def smpl_model_data(kind="smplx", seed=0, V=None, chain=False, n_shapedirs=None, max_depth=15):
+def smpl_model_data(kind="smplx", seed=0, V=None, chain=False, n_shapedirs=None, max_depth=15, J=None, tree="random",
+                    max_weights=4, empty_rows=0.0, empty_joints=0.0):
     """A dict of numpy arrays with the keys and shapes of an SMPL-X (`kind="smplx"`: J = 55, posedirs (V,3,486),
-    shapedirs (V,3,400), hand PCA) or SMPL (J = 24, shapedirs (V,3,10)) model file.  `chain`: a 55-deep single chain."""
+    shapedirs (V,3,400), hand PCA) or SMPL (J = 24, shapedirs (V,3,10)) model file.  `chain`: a 55-deep single chain.
+    Fuzzing knobs (the defaults give the arrays above unchanged): `J` joints; `tree` "random" (parents among the last six
+    joints, depth < max_depth), "chain" (as `chain`), "star" (every joint a child of the root) or "bushy" (uniform random
+    parents, shallow and wide); 1..`max_weights` skinning joints per vertex; a share `empty_rows` of the vertices with no
+    weight at all and a share `empty_joints` of the joints that skin no vertex (their weight moves to the parent)."""
     rng = np.random.default_rng(seed)
-    V0, J = SMPLX_SIZES[kind]
+    V0, J0 = SMPLX_SIZES[kind]
+    J = J0 if J is None else J
     V = V0 if V is None else V
+    chain = chain or tree == "chain"
     S = n_shapedirs or (400 if kind == "smplx" else 10)
     parents = np.zeros(J, np.int64)
     depth = np.zeros(J, np.int64)
     for i in range(1, J):
         if chain:
             p = i - 1
+        elif tree == "star":
+            p = 0
+        elif tree == "bushy":
+            p = int(rng.integers(0, i))
         else:
             cand = [k for k in range(i) if depth[k] < max_depth - 1]
             p = int(cand[max(0, len(cand) - 1 - int(rng.integers(0, 6)))])
@@ -267,11 +278,19 @@ def smpl_model_data(kind="smplx", seed=0, V=None, chain=False, n_shapedirs=None,
     W = np.zeros((V, J))
     for v in range(V):
         j = prim[v]
-        near = [j] + ([int(parents[j])] if parents[j] >= 0 else []) + [int(x) for x in rng.integers(0, J, size=2)]
-        k = int(rng.integers(1, 5))
+        near = ([j] + ([int(parents[j])] if parents[j] >= 0 else [])
+                + [int(x) for x in rng.integers(0, J, size=max(2, max_weights - 2))])
+        k = int(rng.integers(1, max_weights + 1))
         sel = list(dict.fromkeys(near))[:k]
         w = rng.uniform(0.2, 1.0, size=len(sel))
         W[v, sel] += w / w.sum()
+    if empty_joints > 0 or empty_rows > 0:
+        aux = np.random.default_rng([seed, 1])
+        for j in sorted(aux.choice(np.arange(1, J), size=int(round(empty_joints * (J - 1))), replace=False), reverse=True):
+            W[:, parents[j]] += W[:, j]            # children before parents: the weight lands on a joint that keeps it
+            W[:, j] = 0.0
+        if empty_rows > 0:
+            W[aux.random(V) < empty_rows] = 0.0
     Jreg = np.zeros((J, V))
     for j in range(J):
         pool = np.nonzero(prim == j)[0]

@@ -164,8 +164,10 @@ int d3ga_fem_energy_bwd(int T, int V, const float *tetpoints, const int32_t *tet
  *   parents (J), parents[0] = -1; the kinematic tree by level (level_ptr (n_levels + 1), level_joint (J): a joint's parent sits
  *       in an earlier level) and by children (child_ptr (J+1), child_joint (J-1)).
  *   hand_comps (2, n_hand_pca, 45) left then right, hand_mean (2,45): the compact SMPL-X pose layout only.
+ * 2 <= J <= D3GA_BODY_MAX_JOINTS, 0 <= n_hand_pca <= 45 (else D3GA_E_SIZE).
  * Pose layouts (pose_width): 3J axis-angle rows in joint order, or for n_hand_pca > 0 and J = 55 the compact
- *   [body 66 | left-hand PCA n | right-hand PCA n | jaw, left eye, right eye 9], hands = PCA . comps + mean.
+ *   [body 66 | left-hand PCA n | right-hand PCA n | jaw, left eye, right eye 9], hands = PCA . comps + mean.  A width of
+ *   3J is always the full layout, also when n_hand_pca = 45 makes the compact width 3J as well.
  * R_j = Rodrigues(theta_j) with t = |theta_j + 1e-8|; forward kinematics G_j = G_parent [R_j | J_j - J_parent];
  *   A_j = [RG_j | tG_j - RG_j J_j] (not including Rh, Th); bs = dirs^T [beta; psi; pf] (= v_posed - v_template);
  *   T_v = sum_j w_vj A_j; verts = R(Rh) T_v [v_template + bs; 1] + Th.

@@ -1,10 +1,12 @@
-// hostcheck.cpp -- TEST-ONLY: runs the product's per-element arithmetic headers (d3ga_math.h, raster_pre_body.h)
+// hostcheck.cpp -- TEST-ONLY: runs the product's per-element arithmetic headers (d3ga_math.h, raster_pre_body.h,
+// body_model_math.h)
 // on the CPU so that `pytest -m "not gpu"` can compare the formulas the gfx950 kernels execute against the
 // oracle on a box without a GPU.  Never loaded by d3ga_amd/ (the product fails loudly without the HIP library).
 #include <cstdint>
 #include <cstring>
 
 #include "../../d3ga_amd/csrc/raster_pre_body.h"
+#include "../../d3ga_amd/csrc/body_model_math.h"
 
 using namespace d3ga;
 
@@ -170,6 +172,21 @@ void hc_preprocess_bwd_view(const d3ga_raster_params *prm, int kv, int v, const 
                            dL_dsh ? dL_dsh + (size_t)3 * prm->M * i : nullptr, dL_dcolors, dL_dcov3D, dL_dscales, dL_drots,
                            vis ? conic_o[4 * j + 3] : 0.f, dcol != nullptr, dcol ? dcol_load(dcol, stride, j) : ShColJ(), accum);
     }
+}
+
+// the SMPL(-X) body model's per-joint math (body_model.hip: pose_fwd, pose_bwd), n rows at a time
+void hc_body_rodrigues(int n, const float *r, float *R) {
+    for (int i = 0; i < n; ++i) bm::rodrigues(r + 3 * (size_t)i, R + 9 * (size_t)i);
+}
+
+void hc_body_rodrigues_bwd(int n, const float *r, const float *G, float *dr) {
+    for (int i = 0; i < n; ++i) bm::rodrigues_bwd(r + 3 * (size_t)i, G + 9 * (size_t)i, dr + 3 * (size_t)i);
+}
+
+void hc_body_compose(int n, const float *Rp, const float *tp, const float *R, const float *t, float *Ro, float *to) {
+    for (int i = 0; i < n; ++i)
+        bm::compose(Rp + 9 * (size_t)i, tp + 3 * (size_t)i, R + 9 * (size_t)i, t + 3 * (size_t)i, Ro + 9 * (size_t)i,
+                    to + 3 * (size_t)i);
 }
 
 }  // extern "C"

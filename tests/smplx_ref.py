@@ -21,6 +21,29 @@ def rodrigues(r, eps=1e-8):
     return eye + s * K + (1.0 - c) * torch.bmm(K, K)
 
 
+# |theta| of the rotation edge set: exact zero, tiny angles where t = |theta + 1e-8| is dominated by the offset, the
+# ordinary range, and the points where sin / cos change sign or the axis-angle wraps (pi, 2 pi and beyond).
+EDGE_ANGLES = (0.0, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3, 0.35, 1.0, np.pi / 2, np.pi - 1e-3, np.pi, np.pi + 1e-3, 4.0,
+               2 * np.pi - 1e-3, 2 * np.pi, 2 * np.pi + 1e-3)
+
+
+def edge_rotations(rng, n):
+    """(n, 3) float32 axis-angle vectors over EDGE_ANGLES (cycled), each on a random axis, a coordinate axis (zero
+    components) or a negative coordinate axis."""
+    out = np.zeros((n, 3))
+    for i in range(n):
+        a = EDGE_ANGLES[i % len(EDGE_ANGLES)]
+        kind = (i // len(EDGE_ANGLES)) % 3
+        if kind == 0:
+            d = rng.normal(size=3)
+            d /= np.linalg.norm(d)
+        else:
+            d = np.zeros(3)
+            d[int(rng.integers(0, 3))] = 1.0 if kind == 1 else -1.0
+        out[i] = a * d
+    return out.astype(np.float32)
+
+
 class RefSMPL:
     def __init__(self, data, model_type="smplx", num_pca_comps=6, use_flat_mean=True, dtype=torch.float64, device="cpu"):
         kw = dict(dtype=dtype)
@@ -46,7 +69,7 @@ class RefSMPL:
             self.hc = [_t(data["hands_components" + s], dtype)[:num_pca_comps].to(device) for s in ("l", "r")]
             self.hm = [torch.zeros(45, **kw).to(device) if use_flat_mean else _t(data["hands_mean" + s], dtype).to(device)
                        for s in ("l", "r")]
-        self.NUM_POSES = 75 + 2 * num_pca_comps if model_type == "smplx" else 3 * self.J
+        self.NUM_POSES = 75 + 2 * num_pca_comps if model_type == "smplx" and num_pca_comps > 0 else 3 * self.J
 
     def full_pose(self, poses):
         if poses.shape[1] == 3 * self.J:
@@ -60,11 +83,13 @@ class RefSMPL:
         dt = self.vt.dtype
         if shapes.shape[0] != B:
             shapes = shapes.expand(B, -1)
+        shapes = torch.nn.functional.pad(shapes, (0, 10 - shapes.shape[1]))      # fewer coefficients: the rest are zero
         coef = shapes
         if self.n_expr:
             e = expression if expression is not None else torch.zeros(B, 10, dtype=dt, device=poses.device)
             if e.shape[0] != B:
                 e = e.expand(B, -1)
+            e = torch.nn.functional.pad(e, (0, 10 - e.shape[1]))
             coef = torch.cat([shapes, e], dim=1)
         th = self.full_pose(poses).reshape(B * self.J, 3)
         R = rodrigues(th).view(B, self.J, 3, 3)

@@ -208,3 +208,68 @@ def test_compact_and_full_pose_layouts_agree_in_the_oracle(small):
     b = ref(full, torch.zeros(1, 10, dtype=torch.float64))
     for x, y in zip(a, b):
         assert (x - y).abs().max() < 1e-14
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# refusals: configurations the kernels cannot serve are turned away before anything is launched
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [46, 50, -1])
+def test_hand_pca_outside_0_to_45_is_refused(small, n):
+    """hands_components is (45, 45): more components would make the kernels read past hand_comps."""
+    _, paths = small
+    with pytest.raises(ValueError, match="num_pca_comps"):
+        _layer(paths["pkl"], num_pca_comps=n)
+
+
+def test_45_hand_components_keep_the_full_pose_width(small):
+    _, paths = small
+    L = _layer(paths["pkl"], num_pca_comps=45)
+    assert L.n_hand_pca == 45 and L.NUM_POSES == 165 == 3 * L.J
+
+
+@pytest.mark.parametrize("J", [1, 65])
+def test_joint_count_outside_2_to_64_is_refused(tmp_path, J):
+    """J = 65 is beyond D3GA_BODY_MAX_JOINTS (the kernels' LDS tables); J = 1 has no posed joint (no pose blend shapes):
+    a rigid body is the global Rh / Th of any model."""
+    p = syn.write_smpl_model(str(tmp_path / "m.npz"), syn.smpl_model_data("smpl", seed=3, V=40, J=J))
+    with pytest.raises(ValueError, match=f"{J} joint"):
+        _layer(p, model_type="smpl")
+
+
+def test_converted_layer_is_refused_before_any_launch(small):
+    """.double() / .half() convert the float buffers; the kernels read float32, so the layer refuses them (on the CPU too,
+    i.e. before the device check and any launch)."""
+    _, paths = small
+    for conv in (lambda m: m.double(), lambda m: m.half()):
+        L = conv(_layer(paths["pkl"]))
+        with pytest.raises(TypeError, match="float32"):
+            L.model_struct()
+        with pytest.raises(TypeError, match="float32"):
+            L(poses=torch.zeros(1, 87), shapes=torch.zeros(1, 10))
+    L = _layer(paths["pkl"]).double().float()         # back to float32: accepted again
+    assert L.model_struct().n_hand_pca == 6
+
+
+def test_c_abi_refuses_more_than_45_hand_components(small):
+    """body_check, reached through ctypes with no device: n_hand_pca > 45 and J < 2 are D3GA_E_SIZE for C callers too, and
+    a 165-wide pose with 45 components is the (accepted) full layout -- the call then stops at its NULL outputs."""
+    import ctypes
+    from d3ga_amd import _lib
+    _, paths = small
+    L = _layer(paths["pkl"], num_pca_comps=45)
+    lib = _lib.lib()
+
+    def fwd(s, pw):
+        return lib.d3ga_body_model_fwd(ctypes.byref(s), 1, pw, None, None, None, None, None, None, None, None, None, None,
+                                       None, 0, None)
+
+    def bwd(s, pw):
+        return lib.d3ga_body_model_bwd(ctypes.byref(s), 1, pw, None, None, None, None, None, None, None, None, None, None,
+                                       None, None, None, 0, None)
+
+    s = L.model_struct()
+    assert fwd(s, 165) == -1 and bwd(s, 165) == -1            # D3GA_E_NULL: past the layout checks
+    for field, value in (("n_hand_pca", 46), ("n_hand_pca", 90), ("J", 1)):
+        t = _lib.BodyModel.from_buffer_copy(s)
+        setattr(t, field, value)
+        assert fwd(t, 165) == -2 and bwd(t, 165) == -2, (field, value)        # D3GA_E_SIZE

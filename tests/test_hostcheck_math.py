@@ -1,15 +1,19 @@
 """The product's per-element arithmetic headers (d3ga_math.h, raster_pre_body.h -- the very code the gfx950
-kernels execute per Gaussian), compiled for the host, against the oracle.  Runs without a GPU."""
+kernels execute per Gaussian -- and body_model_math.h, the body model's per-joint math), compiled for the host, against the
+oracle.  Runs without a GPU."""
 import ctypes
+import os
+import subprocess
 
 import numpy as np
+import pytest
 import torch
 
-from conftest import ptr
+from conftest import ROOT, ptr
 from oracle import deform as od
 from oracle import raster_c as rc
 from oracle import raster_torch as rt
-from util import rel_err, scene_inputs
+from util import elementwise_excess, rel_err, scene_inputs
 
 from d3ga_amd._lib import RasterParams
 
@@ -312,3 +316,73 @@ def test_preprocess_backward_views_body_matches_single_view(hostcheck):
         if sr:
             for key in ("sc", "ro"):
                 assert rel_err(a[key], b[key]) < 1e-5, (c, key, rel_err(a[key], b[key]))
+
+
+@pytest.fixture(scope="module")
+def hostcheck_body():
+    """hostcheck.cpp built as the shared `hostcheck` fixture builds it, but rebuilt when body_model_math.h changes too (the
+    shared fixture does not watch that header)."""
+    src = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cpp")
+    out_dir = os.path.join(ROOT, "tests", "hostcheck", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    so = os.path.join(out_dir, "libhostcheck_body.so")
+    deps = [src] + [os.path.join(ROOT, "d3ga_amd", "csrc", h) for h in ("d3ga_math.h", "raster_pre_body.h", "body_model_math.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so])
+    return ctypes.CDLL(so)
+
+
+def _edge_rotations(seed):
+    from smplx_ref import EDGE_ANGLES, edge_rotations
+    return edge_rotations(np.random.default_rng(seed), 4 * 3 * len(EDGE_ANGLES))
+
+
+def test_body_rodrigues_forward_over_the_angle_edges(hostcheck_body):
+    """bm::rodrigues against the float64 oracle at the float32 inputs: exact zero, 1e-7 .. 1e-3, pi, 2 pi and beyond, on
+    random and coordinate axes.  Bar: 4 float32 ulps of max(1, |theta|) per entry (t carries |theta|'s rounding into sin)."""
+    from smplx_ref import rodrigues
+    r = _edge_rotations(0)
+    n = len(r)
+    R = np.zeros((n, 9), np.float32)
+    hostcheck_body.hc_body_rodrigues(n, ptr(r), ptr(R))
+    want = rodrigues(torch.from_numpy(r).double()).reshape(n, 9).numpy()
+    t = np.linalg.norm(r.astype(np.float64) + 1e-8, axis=1)
+    err = np.abs(R - want).max(1) / (2.0 ** -23 * np.maximum(1.0, t))
+    i = int(np.argmax(err))
+    assert err[i] <= 4.0, f"rodrigues: {err[i]:.2f} ulps at theta = {r[i]}"
+    assert np.all(R[np.linalg.norm(r, axis=1) == 0] == np.eye(3, dtype=np.float32).reshape(9)), "rodrigues(0) != I"
+
+
+def test_body_rodrigues_backward_over_the_angle_edges(hostcheck_body):
+    """bm::rodrigues_bwd against float64 autograd of the oracle's rodrigues (same 1e-8 offset), per rotation: the
+    element-wise bar, and the row's largest error within 2e-5 of its largest element (1.9e-6 measured, at 2 pi)."""
+    from smplx_ref import rodrigues
+    r = _edge_rotations(1)
+    n = len(r)
+    G = np.random.default_rng(2).normal(size=(n, 9)).astype(np.float32)
+    dr = np.zeros((n, 3), np.float32)
+    hostcheck_body.hc_body_rodrigues_bwd(n, ptr(r), ptr(G), ptr(dr))
+    rt = torch.from_numpy(r).double().requires_grad_(True)
+    (rodrigues(rt).reshape(n, 9) * torch.from_numpy(G).double()).sum().backward()
+    want = rt.grad.numpy()
+    assert np.isfinite(dr).all()
+    for i in range(n):
+        ex = elementwise_excess(dr[i], want[i])
+        rel = float(np.abs(dr[i] - want[i]).max() / np.abs(want[i]).max())
+        assert ex <= 1.0 and rel <= 2e-5, f"rodrigues_bwd at theta = {r[i]}: x{ex:.2f} of the bar, row error {rel:.2e}"
+
+
+def test_body_compose_matches_float64(hostcheck_body):
+    rng = np.random.default_rng(3)
+    n = 64
+    from smplx_ref import rodrigues
+    Rp = rodrigues(torch.from_numpy(rng.normal(size=(n, 3)))).numpy().astype(np.float32).reshape(n, 9)
+    R = rodrigues(torch.from_numpy(rng.normal(size=(n, 3)))).numpy().astype(np.float32).reshape(n, 9)
+    tp, t = (rng.normal(size=(n, 3)).astype(np.float32) for _ in range(2))
+    Ro, to = np.zeros((n, 9), np.float32), np.zeros((n, 3), np.float32)
+    hostcheck_body.hc_body_compose(n, ptr(Rp), ptr(tp), ptr(R), ptr(t), ptr(Ro), ptr(to))
+    Rp64, R64 = Rp.astype(np.float64).reshape(n, 3, 3), R.astype(np.float64).reshape(n, 3, 3)
+    want_R = (Rp64 @ R64).reshape(n, 9)
+    want_t = np.einsum("nij,nj->ni", Rp64, t.astype(np.float64)) + tp
+    assert np.abs(Ro - want_R).max() <= 4 * 2.0 ** -23
+    assert np.abs(to - want_t).max() <= 8 * 2.0 ** -23 * np.abs(want_t).max()
