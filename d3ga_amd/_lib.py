@@ -56,9 +56,17 @@ class BodyModel(ctypes.Structure):
                                                "hand_comps", "hand_mean")]
 
 
+class LbsPoseGrad(ctypes.Structure):
+    """struct d3ga_lbs_pose_grad (include/d3ga.h): the by-joint plan, scratch and outputs of the D0 pose backward."""
+    _fields_ = [("J", ctypes.c_int32), ("n_chunks", ctypes.c_int32), ("n_entries", ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in ("tmpl", "delta", "chunk_ptr", "chunk_range", "entries", "counter", "scratch", "g_joint_mats",
+                                               "g_Rh", "g_Th")]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _prm = ctypes.POINTER(RasterParams)
 _bm = ctypes.POINTER(BodyModel)
+_lpg = ctypes.POINTER(LbsPoseGrad)
 
 # name -> (argtypes, restype); the trailing _vp of every launch entry is the hipStream_t
 _SIGNATURES = {
@@ -68,12 +76,15 @@ _SIGNATURES = {
     "d3ga_debug_defaults": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32], _i),
     "d3ga_lbs_cage_fwd": ([_i, _i] + [_vp] * 8 + [_vp], _i),
     "d3ga_lbs_cage_bwd": ([_i, _i] + [_vp] * 6 + [_vp], _i),
+    "d3ga_lbs_pose_scratch_bytes": ([_i, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_lbs_cage_bwd_pose": ([_i, _i] + [_vp] * 6 + [_lpg, _vp], _i),
     "d3ga_cage_deform_fwd": ([_i] + [_vp] * 9 + [_vp], _i),
     "d3ga_cage_deform_bwd": ([_i, _i] + [_vp] * 16 + [_vp], _i),
     "d3ga_cage_deform_fwd_ex": ([_i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 2 + [_vp], _i),
     "d3ga_cage_deform_bwd_ex": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [_vp], _i),
     "d3ga_cage_deform_bwd_merged": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_vp], _i),
     "d3ga_cage_deform_bwd_merged_lbs": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_i] + [_vp] * 6 + [_vp], _i),
+    "d3ga_cage_deform_bwd_merged_lbs_pose": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_i] + [_vp] * 6 + [_lpg, _vp], _i),
     "d3ga_fem_energy_fwd": ([_i] + [_vp] * 4 + [_vp], _i),
     "d3ga_fem_energy_bwd": ([_i, _i] + [_vp] * 5 + [_vp], _i),
     "d3ga_raster_scratch_bytes": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.POINTER(_i64)], _i),

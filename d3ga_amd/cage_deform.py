@@ -7,6 +7,7 @@ Host-side mirror of the reference's per-frame tensor program (SURVEY.md sec. 8a 
     lib/cage.py:349-361           -> fem_energy
 All three call hand-written gfx950 kernels through the C ABI (include/d3ga.h); GPU tensors only.
 """
+import ctypes
 import os
 
 import torch
@@ -200,32 +201,171 @@ def cage_deform(tetpoints, tetras, tetra_id, barys, canonical_gradient, scales, 
                              delta_barys, flags)
 
 
+_pose_plan_cache = {}
+_POSE_CHUNK = 256         # = kBlock of csrc/deform.hip: the entries of one workgroup of the by-joint reduction
+
+
+def lbs_pose_plan(skin_idx, J):
+    """Static by-joint plan of the pose backward of lbs_cage / lbs_cage_deform (struct d3ga_lbs_pose_grad), built once per
+    binding and cached by the storage of `skin_idx` (V,K) and J:
+    -> dict(entries (V*K) int32 = the flat indices v*K + k sorted by joint (stable), chunk_range (n_chunks,2) int32 = [begin,
+            end) of every chunk of at most 256 entries of one joint, chunk_ptr (J+1) int32 = the first chunk of each joint,
+            n_chunks, n_entries, counter = the reduction's arrival count, kept at 0 between calls).
+    The pelvis and spine joints of SMPL-X carry thousands of entries: they get many chunks (workgroups), summed in chunk order.
+    Refuses (ValueError) an index outside [0, J) -- the forward would read outside joint_mats.  Building the plan reads two
+    numbers back to the host; calls that hit the cache do not synchronise (capturable)."""
+    if skin_idx.dim() != 2:
+        raise ValueError(f"skin_idx must be (V,K), got {tuple(skin_idx.shape)}")
+    if J <= 0:
+        raise ValueError(f"joint_mats must hold at least one joint, got J = {J}")
+    key = (skin_idx.data_ptr(), skin_idx._version, tuple(skin_idx.shape), skin_idx.dtype, J)
+    hit = _pose_plan_cache.get(key)
+    if hit is None:
+        with torch.no_grad():
+            dev = skin_idx.device
+            V, K = skin_idx.shape
+            flat = skin_idx.reshape(-1).long()
+            if flat.numel():
+                bad = (flat < 0) | (flat >= J)
+                nb = torch.nonzero(bad)
+                if nb.numel():
+                    q = int(nb[0, 0])
+                    raise ValueError(f"skin_idx[{q // K}, {q % K}] = {int(flat[q])} is outside [0, {J}) (J = joint_mats.shape[0]; "
+                                     f"{nb.shape[0]} such entries)")
+            order = torch.sort(flat, stable=True)[1]
+            counts = torch.bincount(flat, minlength=J)
+            start = torch.zeros(J + 1, dtype=torch.int64, device=dev)
+            start[1:] = torch.cumsum(counts, 0)
+            nch = (counts + _POSE_CHUNK - 1) // _POSE_CHUNK
+            chunk_ptr = torch.zeros(J + 1, dtype=torch.int64, device=dev)
+            chunk_ptr[1:] = torch.cumsum(nch, 0)
+            cj = torch.repeat_interleave(torch.arange(J, device=dev), nch)          # joint of every chunk
+            q = torch.arange(cj.numel(), device=dev) - chunk_ptr[cj]
+            beg = start[cj] + q * _POSE_CHUNK
+            end = torch.minimum(beg + _POSE_CHUNK, start[cj + 1])
+            hit = dict(entries=order.to(torch.int32).contiguous(), chunk_range=torch.stack([beg, end], 1).to(torch.int32).contiguous(),
+                       chunk_ptr=chunk_ptr.to(torch.int32).contiguous(), n_chunks=int(cj.numel()), n_entries=V * K, J=J,
+                       counter=torch.zeros(1, dtype=torch.int32, device=dev), pins=skin_idx)
+        if len(_pose_plan_cache) > 64:
+            _pose_plan_cache.clear()
+        _pose_plan_cache[key] = hit          # holds skin_idx alive: its address cannot be recycled
+    return hit
+
+
+def sparse_skin_weights(dense_w, rows=None, K=None):
+    """Exact K-sparse form of the dense skinning weights `dense_w[rows]` ((V,J) -> skin_idx (V,K) int32, skin_w (V,K)), the layout
+    lbs_cage / lbs_cage_deform take.  The reference skins the cage with `skin_weights[nn_ids]` rows of a dense (V, 55) table
+    (lib/smplman.py:155-164): pass that table and `rows=nn_ids`.  Each row keeps its non-zero weights in joint order; K is the
+    largest non-zero count unless given (a K below it is refused), and shorter rows are padded with weight 0 (on joints whose
+    weight is 0, or joint 0 beyond J).  Runs on whatever device the table lives."""
+    if dense_w.dim() != 2:
+        raise ValueError(f"dense_w must be (V,J), got {tuple(dense_w.shape)}")
+    W = dense_w if rows is None else dense_w[rows.long() if torch.is_tensor(rows) else rows]
+    V, J = W.shape
+    nz = W != 0
+    kmax = int(nz.sum(1).max()) if V else 0
+    if K is None:
+        K = max(kmax, 1)
+    elif K < kmax:
+        raise ValueError(f"K = {K} drops weights: a row has {kmax} non-zero entries")
+    elif K < 1:
+        raise ValueError(f"K must be >= 1, got {K}")
+    order = torch.sort((~nz).to(torch.int8), dim=1, stable=True)[1]            # non-zero joints first, each group in joint order
+    k = min(K, J)
+    idx = order[:, :k]
+    w = torch.gather(W, 1, idx)
+    if K > J:
+        idx = torch.cat([idx, idx.new_zeros(V, K - J)], 1)
+        w = torch.cat([w, w.new_zeros(V, K - J)], 1)
+    return idx.to(torch.int32).contiguous(), w.contiguous()
+
+
+def _pose_needed(need, i_A, i_Rh, i_Th):
+    return bool(need[i_A] or need[i_Rh] or need[i_Th])
+
+
+def _check_pose_plan(skin_idx, joint_mats, Rh, Th):
+    """With a pose gradient to come, build (or find) the by-joint plan now: it refuses an index outside [0, J) before the forward
+    would read joint_mats through it."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (joint_mats, Rh, Th)):
+        lbs_pose_plan(skin_idx, joint_mats.shape[0])
+
+
+def _pose_grad_struct(plan, V, fused, template, delta, dev):
+    """(struct, outputs, scratch) of one pose backward call; the tensors must stay alive until the launches are queued."""
+    nbytes = ctypes.c_int64(0)
+    check(_lib.lib().d3ga_lbs_pose_scratch_bytes(V, plan["n_chunks"], fused, ctypes.byref(nbytes)), "d3ga_lbs_pose_scratch_bytes")
+    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    J = plan["J"]
+    gA = torch.empty((J, 4, 4), dtype=torch.float32, device=dev)
+    gRh = torch.empty((3, 3), dtype=torch.float32, device=dev)
+    gTh = torch.empty((3,), dtype=torch.float32, device=dev)
+    st = _lib.LbsPoseGrad(J=J, n_chunks=plan["n_chunks"], n_entries=plan["n_entries"], tmpl=dptr(template), delta=dptr(delta),
+                          chunk_ptr=dptr(plan["chunk_ptr"]), chunk_range=dptr(plan["chunk_range"]), entries=dptr(plan["entries"]),
+                          counter=dptr(plan["counter"]), scratch=dptr(scratch), g_joint_mats=dptr(gA), g_Rh=dptr(gRh), g_Th=dptr(gTh))
+    return st, (gA, gRh, gTh), scratch
+
+
+def _pose_returns(ctx, need, i_A, i_Rh, i_Th, gA, gRh, gTh):
+    return (gA.view(ctx.shape_A) if need[i_A] else None, gRh.view(ctx.shape_Rh) if (ctx.has_Rh and need[i_Rh]) else None,
+            gTh.view(ctx.shape_Th) if (ctx.has_Th and need[i_Th]) else None)
+
+
 class _LbsCage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th):
         require_cuda(template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
+        ctx.pose = _pose_needed(ctx.needs_input_grad, 2, 5, 6)
+        if ctx.pose:
+            ctx.shape_A, ctx.shape_Rh, ctx.shape_Th = (joint_mats.shape, None if Rh is None else Rh.shape,
+                                                       None if Th is None else Th.shape)
         template, delta, joint_mats, skin_w, Rh, Th = map(_f32c, (template, delta, joint_mats, skin_w, Rh, Th))
         V, K = skin_w.shape
         out = torch.empty((V, 3), dtype=torch.float32, device=template.device)
         check(_lib.lib().d3ga_lbs_cage_fwd(V, K, dptr(template), dptr(delta), dptr(joint_mats), dptr(skin_idx),
                                            dptr(skin_w), dptr(Rh), dptr(Th), dptr(out), stream_handle()),
               "d3ga_lbs_cage_fwd")
-        ctx.save_for_backward(joint_mats, skin_idx, skin_w, Rh if Rh is not None else torch.empty(0, device=out.device))
+        none = torch.empty(0, device=out.device)
+        if ctx.pose:                         # the pose gradients read p~ = template + delta
+            ctx.save_for_backward(joint_mats, skin_idx, skin_w, Rh if Rh is not None else none, template,
+                                  delta if delta is not None else none)
+        else:
+            ctx.save_for_backward(joint_mats, skin_idx, skin_w, Rh if Rh is not None else none)
         ctx.has_Rh = Rh is not None
+        ctx.has_Th = Th is not None
         ctx.has_delta = delta is not None
         return out
 
     @staticmethod
     def backward(ctx, g):
-        joint_mats, skin_idx, skin_w, Rh = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not ctx.pose or not _pose_needed(need, 2, 5, 6):
+            joint_mats, skin_idx, skin_w, Rh = ctx.saved_tensors[:4]
+            V, K = skin_w.shape
+            gd = torch.empty((V, 3), dtype=torch.float32, device=g.device)
+            check(_lib.lib().d3ga_lbs_cage_bwd(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
+                                               dptr(Rh if ctx.has_Rh else None), dptr(_f32c(g)), dptr(gd),
+                                               stream_handle()), "d3ga_lbs_cage_bwd")
+            g_t = gd if ctx.needs_input_grad[0] else None
+            g_d = gd if (ctx.has_delta and ctx.needs_input_grad[1]) else None
+            return g_t, g_d, None, None, None, None, None
+        joint_mats, skin_idx, skin_w, Rh, template, delta = ctx.saved_tensors
         V, K = skin_w.shape
-        gd = torch.empty((V, 3), dtype=torch.float32, device=g.device)
-        check(_lib.lib().d3ga_lbs_cage_bwd(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
-                                           dptr(Rh if ctx.has_Rh else None), dptr(_f32c(g)), dptr(gd),
-                                           stream_handle()), "d3ga_lbs_cage_bwd")
-        g_t = gd if ctx.needs_input_grad[0] else None
-        g_d = gd if (ctx.has_delta and ctx.needs_input_grad[1]) else None
-        return g_t, g_d, None, None, None, None, None
+        dev = g.device
+        gd = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        if V == 0:
+            gA, gRh, gTh = (torch.zeros((joint_mats.shape[0], 4, 4), device=dev), torch.zeros((3, 3), device=dev),
+                            torch.zeros((3,), device=dev))
+        else:
+            plan = lbs_pose_plan(skin_idx, joint_mats.shape[0])
+            st, (gA, gRh, gTh), scratch = _pose_grad_struct(plan, V, 0, template, delta if ctx.has_delta else None, dev)
+            check(_lib.lib().d3ga_lbs_cage_bwd_pose(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
+                                                    dptr(Rh if ctx.has_Rh else None), dptr(_f32c(g)), dptr(gd), ctypes.byref(st),
+                                                    stream_handle()), "d3ga_lbs_cage_bwd_pose")
+        g_t = gd if need[0] else None
+        g_d = gd if (ctx.has_delta and need[1]) else None
+        g_A, g_Rh, g_Th = _pose_returns(ctx, need, 2, 5, 6, gA, gRh, gTh)
+        return g_t, g_d, g_A, None, None, g_Rh, g_Th
 
 
 def skeleton_matrices(bind_state, target_states):
@@ -264,8 +404,13 @@ def skeleton_matrices(bind_state, target_states):
 def lbs_cage(template, delta, joint_mats, skin_idx, skin_w, Rh=None, Th=None):
     """K-sparse linear blend skinning of cage vertices: (sum_k w_k A[idx_k]) [v+delta;1], then .Rh^T + Th
     (lib/smplman.py:155-171).  Differentiable in template and delta (the deformation_field output when
-    train.tet_offset_pre_lbs is on, models/cage_net.py:207-208); joint transforms are treated as constants."""
-    return _LbsCage.apply(template, delta, joint_mats, _i32c(skin_idx), skin_w, Rh, Th)
+    train.tet_offset_pre_lbs is on, models/cage_net.py:207-208), and in joint_mats (J,4,4), Rh (3,3) and Th (3,): the body pose
+    reaches the cage through them (use_opt_smplx, models/garment_net.py:211-236).  dL/d(joint_mats) has an exact-zero bottom row
+    (never read).  When one of the three requires a gradient, every skin_idx must lie in [0, J) (ValueError otherwise) and a
+    by-joint plan is built once per binding (lbs_pose_plan); without pose gradients the backward is the one launch it always was."""
+    skin_idx = _i32c(skin_idx)
+    _check_pose_plan(skin_idx, joint_mats, Rh, Th)
+    return _LbsCage.apply(template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
 
 
 class _LbsCageDeform(torch.autograd.Function):
@@ -277,6 +422,10 @@ class _LbsCageDeform(torch.autograd.Function):
     def forward(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th, tetras, tetra_id, barys, canon_grad, scales, rotations,
                 delta_barys, flags):
         require_cuda(template, delta, joint_mats, skin_idx, skin_w, Rh, Th, tetras, tetra_id, barys, canon_grad, scales, rotations)
+        ctx.pose = _pose_needed(ctx.needs_input_grad, 2, 5, 6)
+        if ctx.pose:
+            ctx.shape_A, ctx.shape_Rh, ctx.shape_Th = (joint_mats.shape, None if Rh is None else Rh.shape,
+                                                       None if Th is None else Th.shape)
         template, delta, joint_mats, skin_w, Rh, Th = map(_f32c, (template, delta, joint_mats, skin_w, Rh, Th))
         barys, canon_grad, scales, rotations, delta_barys = map(_f32c, (barys, canon_grad, scales, rotations, delta_barys))
         V, K = skin_w.shape
@@ -291,18 +440,22 @@ class _LbsCageDeform(torch.autograd.Function):
                                         dptr(scales), dptr(rotations), dptr(delta_barys), flags, dptr(means), dptr(cov6),
                                         stream_handle()), "d3ga_cage_deform_fwd_ex")
         ctx.flags, ctx.has_dbary, ctx.has_Rh, ctx.has_delta = flags, delta_barys is not None, Rh is not None, delta is not None
+        ctx.has_Th = Th is not None
         ctx.set_materialize_grads(False)
         none = torch.empty(0, device=dev)
+        pose = (template, delta if delta is not None else none) if ctx.pose else ()      # the pose gradients read p~ = template + delta
         ctx.save_for_backward(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations,
                               delta_barys if delta_barys is not None else none, joint_mats, skin_idx, skin_w,
-                              Rh if Rh is not None else none)
+                              Rh if Rh is not None else none, *pose)
         return means, cov6, tetpoints
 
     @staticmethod
     def backward(ctx, g_means, g_cov6, g_tp_extra):
         (tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, joint_mats, skin_idx, skin_w,
-         Rh) = ctx.saved_tensors
+         Rh) = ctx.saved_tensors[:12]
         P, V, K, dev = barys.shape[0], tetpoints.shape[0], skin_w.shape[1], barys.device
+        if ctx.pose and _pose_needed(ctx.needs_input_grad, 2, 5, 6):
+            return _LbsCageDeform._backward_pose(ctx, g_means, g_cov6, g_tp_extra)
         g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
         g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
         need = ctx.needs_input_grad
@@ -322,13 +475,48 @@ class _LbsCageDeform(torch.autograd.Function):
         return (g_d if need[0] else None, g_d if (ctx.has_delta and need[1]) else None, None, None, None, None, None, None, None,
                 g_b if need[9] else None, None, g_s, g_r, g_b if need[13] else None, None)
 
+    @staticmethod
+    def _backward_pose(ctx, g_means, g_cov6, g_tp_extra):
+        """The backward with dL/d(joint_mats, Rh, Th): d3ga_cage_deform_bwd_merged_lbs_pose (one launch more than the one above)."""
+        (tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, joint_mats, skin_idx, skin_w,
+         Rh, template, delta) = ctx.saved_tensors
+        P, V, K, dev = barys.shape[0], tetpoints.shape[0], skin_w.shape[1], barys.device
+        g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
+        g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
+        need = ctx.needs_input_grad
+        g_b = torch.empty((P, 4), dtype=torch.float32, device=dev) if (need[9] or need[13]) else None
+        g_s = torch.empty((P, 3), dtype=torch.float32, device=dev) if need[11] else None
+        g_r = torch.empty((P, 4), dtype=torch.float32, device=dev) if need[12] else None
+        g_d = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        if V == 0:
+            gA, gRh, gTh = (torch.zeros((joint_mats.shape[0], 4, 4), device=dev), torch.zeros((3, 3), device=dev),
+                            torch.zeros((3,), device=dev))
+            g_b, g_s, g_r = (None if t is None else t.zero_() for t in (g_b, g_s, g_r))     # no cage: no Gaussian either
+        else:
+            mplan = merge_plan(tetras, tetra_id, V)
+            partials = torch.empty((max(mplan["n_segments"], 1), 3), dtype=torch.float32, device=dev)
+            plan = lbs_pose_plan(skin_idx, joint_mats.shape[0])
+            st, (gA, gRh, gTh), scratch = _pose_grad_struct(plan, V, 1, template, delta if ctx.has_delta else None, dev)
+            check(_lib.lib().d3ga_cage_deform_bwd_merged_lbs_pose(
+                P, V, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys), dptr(canon_grad), dptr(scales), dptr(rotations),
+                dptr(delta_barys if ctx.has_dbary else None), ctx.flags, dptr(g_means), dptr(g_cov6), None, dptr(g_b), dptr(g_s),
+                dptr(g_r), dptr(mplan["item_pos"]), dptr(mplan["seg_ptr"]), dptr(mplan["seg_begin"]), mplan["n_segments"],
+                dptr(mplan["vert_start"]), dptr(mplan["vert_parts"]), dptr(partials), K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
+                dptr(Rh if ctx.has_Rh else None), dptr(None if g_tp_extra is None else _f32c(g_tp_extra)), dptr(g_d),
+                ctypes.byref(st), stream_handle()), "d3ga_cage_deform_bwd_merged_lbs_pose")
+        g_A, g_Rh, g_Th = _pose_returns(ctx, need, 2, 5, 6, gA, gRh, gTh)
+        return (g_d if need[0] else None, g_d if (ctx.has_delta and need[1]) else None, g_A, None, None, g_Rh, g_Th, None, None,
+                g_b if need[9] else None, None, g_s, g_r, g_b if need[13] else None, None)
+
 
 def lbs_cage_deform(template, delta, joint_mats, skin_idx, skin_w, tetras, tetra_id, barys, canonical_gradient, scales, rotations,
                     delta_barys=None, scale_activation=None, gradient_per_tet=None, Rh=None, Th=None):
     """`cage_deform(lbs_cage(template, delta, joint_mats, skin_idx, skin_w, Rh, Th), tetras, ...)` as one operator (an extension
     like `renderer.render_l1`; lib/smplman.py:155-171 feeding models/cage_net.py:218-230): same outputs, same gradients, one
     launch less in the backward.  -> (means3D (P,3), cov3D_precomp (P,6), tetpoints (V,3)); the posed cage vertices are returned
-    for the terms that read them directly (the FEM regulariser, lib/cage.py:349-361) -- their gradient joins the skinning backward."""
+    for the terms that read them directly (the FEM regulariser, lib/cage.py:349-361) -- their gradient joins the skinning backward.
+    Differentiable in joint_mats, Rh and Th as lbs_cage is (the pose gradients take one launch more in the backward, and only
+    when one of the three requires a gradient)."""
     if scale_activation not in (None, "exp"):
         raise ValueError(f"scale_activation must be None or 'exp', got {scale_activation!r}")
     P, T = barys.shape[0], tetras.shape[0]
@@ -341,7 +529,9 @@ def lbs_cage_deform(template, delta, joint_mats, skin_idx, skin_w, tetras, tetra
     if canonical_gradient.shape[0] != (T if gradient_per_tet else P):
         raise ValueError(f"canonical_gradient has {canonical_gradient.shape[0]} matrices, expected {T if gradient_per_tet else P}")
     flags = (1 if scale_activation == "exp" else 0) | (2 if gradient_per_tet else 0)
-    return _LbsCageDeform.apply(template, delta, joint_mats, _i32c(skin_idx), skin_w, Rh, Th, _i32c(tetras), _i32c(tetra_id), barys,
+    skin_idx = _i32c(skin_idx)
+    _check_pose_plan(skin_idx, joint_mats, Rh, Th)
+    return _LbsCageDeform.apply(template, delta, joint_mats, skin_idx, skin_w, Rh, Th, _i32c(tetras), _i32c(tetra_id), barys,
                                 canonical_gradient, scales, rotations, delta_barys, flags)
 
 

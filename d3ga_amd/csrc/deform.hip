@@ -13,6 +13,24 @@ namespace d3ga {
 
 __device__ __forceinline__ V3 load3(const float *p, int i) { return v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
 
+// 64-lane sum through DPP (see raster_composite.hip); result broadcast from lane 63
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add_(float v) {
+    const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true);
+    return v + __int_as_float(t);
+}
+__device__ __forceinline__ float wave_sum_(float v) {
+    v = dpp_add_<0xB1, 0xf>(v); v = dpp_add_<0x4E, 0xf>(v); v = dpp_add_<0x141, 0xf>(v); v = dpp_add_<0x140, 0xf>(v);
+    v = dpp_add_<0x142, 0xa>(v); v = dpp_add_<0x143, 0xc>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// The same over one 16-lane DPP row: every lane of the row ends with the row's total
+__device__ __forceinline__ float row_sum_(float v) {
+    v = dpp_add_<0xB1, 0xf>(v); v = dpp_add_<0x4E, 0xf>(v); v = dpp_add_<0x141, 0xf>(v); v = dpp_add_<0x140, 0xf>(v);
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // D0: v' = Rh (sum_k w_k A[idx_k]) [v + delta; 1] + Th
 // ---------------------------------------------------------------------------------------------------------
@@ -64,6 +82,120 @@ __global__ __launch_bounds__(kBlock) void lbs_bwd_kernel(int V, int K, const flo
     gdelta[3 * v] = T[0] * go.x + T[4] * go.y + T[8] * go.z;
     gdelta[3 * v + 1] = T[1] * go.x + T[5] * go.y + T[9] * go.z;
     gdelta[3 * v + 2] = T[2] * go.x + T[6] * go.y + T[10] * go.z;
+}
+
+// Pose gradients of D0 (dL/dA, dL/dRh, dL/dTh; d3ga_lbs_cage_bwd_pose, d3ga_cage_deform_bwd_merged_lbs_pose).  With
+// p~ = [tmpl + delta; 1], T = sum_k w_k A[idx_k], o = T p~ (before Rh), g = dL/dout and g' = Rh^T g:
+//   dA_j[0:3,0:4] = sum over the (v,k) with idx = j of w_vk g'_v p~_v^T   (row 3 is never read: exact zeros)
+//   dRh = sum_v g_v o_v^T,  dTh = sum_v g_v.
+// One launch after the unchanged per-vertex launch of the backward, which leaves g in memory (the upstream gradient itself, or
+// the gathered vertex gradient of the fused operator).  By-joint plan (cage_deform.py: lbs_pose_plan, built once per binding):
+// entries (V*K) = the flat indices v*K + k of skin_idx sorted by joint (stable), cut into chunks of at most kBlock entries that
+// never straddle a joint; chunk_rng (n_chunks) = [begin, end) of each chunk, chunk_ptr (J+1) = the first chunk of each joint.
+// Workgroup b < n_chunks sums its chunk (one entry per lane), the next ceil(V / kBlock) workgroups sum (g o^T, g) over kBlock
+// vertices each (o recomputed); every workgroup writes 12 partials, and the last one to arrive adds them per joint in chunk
+// order (row 3 of dA written 0) and the vertex partials in order for dRh / dTh, then re-arms the plan's counter.  Fixed-order
+// sums, no float atomics: bit-reproducible.
+__device__ __forceinline__ float block_sum12_(const float (&v)[12], float (*red)[12]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        const float t = wave_sum_(v[i]);
+        if (lane == 0) red[wv][i] = t;
+    }
+    __syncthreads();
+    float s = 0.f;
+    if (threadIdx.x < 12)
+        for (int k = 0; k < kBlock / 64; ++k) s += red[k][threadIdx.x];
+    return s;
+}
+
+__global__ __launch_bounds__(kBlock) void lbs_pose_reduce_kernel(
+    int V, int K, int J, int n_chunks, const int2 *__restrict__ chunk_rng, const int32_t *__restrict__ chunk_ptr,
+    const int32_t *__restrict__ entries, const float *__restrict__ A, const int32_t *__restrict__ idx,
+    const float *__restrict__ w, const float *__restrict__ tmpl, const float *__restrict__ delta, const float *__restrict__ Rh,
+    const float *__restrict__ g, float *part, unsigned *counter, float *__restrict__ gA, float *__restrict__ gRh,
+    float *__restrict__ gTh) {
+    __shared__ float red[kBlock / 64][12];
+    __shared__ int last;
+    const int b = blockIdx.x;
+    float ps[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ps[i] = 0.f;
+    if (b < n_chunks) {
+        const int2 r = chunk_rng[b];
+        const int e = r.x + (int)threadIdx.x;
+        if (e < r.y) {
+            const int q = entries[e], v = q / K;
+            const float wk = w[q];
+            V3 p = load3(tmpl, v);
+            if (delta) p = p + load3(delta, v);
+            V3 go = load3(g, v);
+            if (Rh) go = v3(Rh[0] * go.x + Rh[3] * go.y + Rh[6] * go.z, Rh[1] * go.x + Rh[4] * go.y + Rh[7] * go.z,
+                            Rh[2] * go.x + Rh[5] * go.y + Rh[8] * go.z);
+            const V3 wg = v3(wk * go.x, wk * go.y, wk * go.z);
+            ps[0] = wg.x * p.x; ps[1] = wg.x * p.y; ps[2] = wg.x * p.z; ps[3] = wg.x;
+            ps[4] = wg.y * p.x; ps[5] = wg.y * p.y; ps[6] = wg.y * p.z; ps[7] = wg.y;
+            ps[8] = wg.z * p.x; ps[9] = wg.z * p.y; ps[10] = wg.z * p.z; ps[11] = wg.z;
+        }
+    } else {
+        const int v = (b - n_chunks) * kBlock + (int)threadIdx.x;
+        if (v < V) {
+            V3 p = load3(tmpl, v);
+            if (delta) p = p + load3(delta, v);
+            float T[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) T[i] = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float wk = w[(size_t)v * K + k];
+                const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) T[i] += wk * a[i];
+            }
+            const V3 o = v3(T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
+                            T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]);
+            const V3 gv = load3(g, v);
+            ps[0] = gv.x * o.x; ps[1] = gv.x * o.y; ps[2] = gv.x * o.z;
+            ps[3] = gv.y * o.x; ps[4] = gv.y * o.y; ps[5] = gv.y * o.z;
+            ps[6] = gv.z * o.x; ps[7] = gv.z * o.y; ps[8] = gv.z * o.z;
+            ps[9] = gv.x; ps[10] = gv.y; ps[11] = gv.z;
+        }
+    }
+    const float s = block_sum12_(ps, red);
+    if (threadIdx.x < 64) {                                 // wavefront 0 wrote the partials: it releases them, then counts
+        if (threadIdx.x < 12) part[12 * (size_t)b + threadIdx.x] = s;
+        __threadfence();
+        if (threadIdx.x == 0) last = atomicAdd(counter, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    if (threadIdx.x == 0) *counter = 0u;                    // every other workgroup has counted: re-armed for the next call
+    for (int i = threadIdx.x; i < 12 * J; i += kBlock) {    // dA: one element per lane, its chunks in order
+        const int j = i / 12, e = i - 12 * j;
+        float t = 0.f;
+#pragma unroll 8
+        for (int c = chunk_ptr[j], ce = chunk_ptr[j + 1]; c < ce; ++c) t += part[12 * (size_t)c + e];
+        gA[16 * j + e] = t;
+    }
+    for (int i = threadIdx.x; i < 4 * J; i += kBlock) gA[16 * (i >> 2) + 12 + (i & 3)] = 0.f;
+    // dRh, dTh: 21 lanes per value, each over every 21st vertex partial, then the 21 sums in order
+    constexpr int kLanesPerValue = kBlock / 12;
+    float t = 0.f;
+    if (threadIdx.x < 12 * kLanesPerValue) {
+        const int e = threadIdx.x % 12, q = threadIdx.x / 12;
+#pragma unroll 4
+        for (int c = n_chunks + q; c < (int)gridDim.x; c += kLanesPerValue) t += part[12 * (size_t)c + e];
+    }
+    __shared__ float vs[kLanesPerValue * 12];
+    if (threadIdx.x < 12 * kLanesPerValue) vs[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        float u = 0.f;
+        for (int q = 0; q < kLanesPerValue; ++q) u += vs[12 * q + threadIdx.x];
+        if (threadIdx.x < 9) gRh[threadIdx.x] = u;
+        else gTh[threadIdx.x - 9] = u;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -196,18 +328,6 @@ __global__ __launch_bounds__(kBlock) void cage_deform_bwd_kernel(
     }
 }
 
-// 64-lane sum through DPP (see raster_composite.hip); result broadcast from lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_(float v) {
-    const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true);
-    return v + __int_as_float(t);
-}
-__device__ __forceinline__ float wave_sum_(float v) {
-    v = dpp_add_<0xB1, 0xf>(v); v = dpp_add_<0x4E, 0xf>(v); v = dpp_add_<0x141, 0xf>(v); v = dpp_add_<0x140, 0xf>(v);
-    v = dpp_add_<0x142, 0xa>(v); v = dpp_add_<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 // One wavefront per cage vertex: sums the corner gradients of every (Gaussian, corner) incident to the vertex.
 // vert_start (V+1) / vert_items (4P, item = 4*gaussian + corner) is the static CSR adjacency built once per cage.
 // No atomics, bit-reproducible.
@@ -231,10 +351,6 @@ __global__ __launch_bounds__(kBlock) void vertex_gather_kernel(int V, const int3
 // The same with ONE DPP ROW (16 lanes) per vertex, four vertices per wavefront: for short item lists -- the partials of the
 // block-merged backward, two to four per vertex with coherent numbering -- a whole wavefront per vertex leaves 60 lanes idle
 // and the launch is 4x the wavefronts (7.3 -> .. us at C3).
-__device__ __forceinline__ float row_sum_(float v) {          // every lane of the row ends with the row's total
-    v = dpp_add_<0xB1, 0xf>(v); v = dpp_add_<0x4E, 0xf>(v); v = dpp_add_<0x141, 0xf>(v); v = dpp_add_<0x140, 0xf>(v);
-    return v;
-}
 __global__ __launch_bounds__(kBlock) void vertex_gather_row_kernel(int V, const int32_t *__restrict__ vert_start,
                                                                    const int32_t *__restrict__ vert_items,
                                                                    const float *__restrict__ values,
@@ -351,6 +467,44 @@ extern "C" int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const in
     return check_launch((hipStream_t)stream, 0);
 }
 
+// scratch of the pose backward: partials (12 per workgroup of the reduction) | the fused operator's vertex gradient (3V)
+static int64_t pose_groups(int V, int n_chunks) { return (int64_t)n_chunks + (V + kBlock - 1) / kBlock; }
+
+extern "C" int d3ga_lbs_pose_scratch_bytes(int V, int32_t n_chunks, int32_t fused, int64_t *bytes) {
+    if (V < 0 || n_chunks < 0) return D3GA_E_SIZE;
+    if (!bytes) return D3GA_E_NULL;
+    *bytes = 4 * (12 * pose_groups(V, n_chunks) + (fused ? 3 * (int64_t)V : 0));
+    return D3GA_OK;
+}
+
+static int pose_check(int V, int K, const d3ga_lbs_pose_grad *pg) {
+    if (!pg) return D3GA_E_NULL;
+    if (pg->J <= 0 || pg->n_chunks <= 0 || (int64_t)V * K != pg->n_entries) return D3GA_E_SIZE;
+    if (!pg->tmpl || !pg->chunk_ptr || !pg->chunk_range || !pg->entries || !pg->counter || !pg->scratch || !pg->g_joint_mats ||
+        !pg->g_Rh || !pg->g_Th)
+        return D3GA_E_NULL;
+    if (((uintptr_t)pg->chunk_range & 7) || ((uintptr_t)pg->scratch & 3)) return D3GA_E_CONFIG;     // int2 / float reads
+    return D3GA_OK;
+}
+
+static int pose_reduce(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w, const float *Rh,
+                       const float *g, const d3ga_lbs_pose_grad *pg, hipStream_t s) {
+    hipLaunchKernelGGL(lbs_pose_reduce_kernel, dim3((unsigned)pose_groups(V, pg->n_chunks)), dim3(kBlock), 0, s, V, K, pg->J,
+                       pg->n_chunks, (const int2 *)pg->chunk_range, pg->chunk_ptr, pg->entries, joint_mats, skin_idx, skin_w,
+                       pg->tmpl, pg->delta, Rh, g, (float *)pg->scratch, (unsigned *)pg->counter, pg->g_joint_mats, pg->g_Rh,
+                       pg->g_Th);
+    return check_launch(s, 0);
+}
+
+extern "C" int d3ga_lbs_cage_bwd_pose(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
+                                      const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
+                                      d3ga_stream_t stream) {
+    if (V <= 0 || K <= 0) return D3GA_E_SIZE;
+    D3GA_TRY(pose_check(V, K, pose));
+    D3GA_TRY(d3ga_lbs_cage_bwd(V, K, joint_mats, skin_idx, skin_w, Rh, grad_out, grad_delta, stream));
+    return pose_reduce(V, K, joint_mats, skin_idx, skin_w, Rh, grad_out, pose, (hipStream_t)stream);
+}
+
 extern "C" int d3ga_cage_deform_fwd_ex(int P, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
                                        const float *barys, const float *canon_grad, const float *scales,
                                        const float *rots, const float *delta_barys, int32_t flags, float *means3D,
@@ -464,6 +618,27 @@ extern "C" int d3ga_cage_deform_bwd_merged_lbs(int P, int V, const float *tetpoi
                        vert_start, vert_parts, (const float *)partials, g_tetpoints_extra, joint_mats, skin_idx, skin_w, Rh,
                        g_tetpoints, g_delta);
     return check_launch(s, 0);
+}
+
+extern "C" int d3ga_cage_deform_bwd_merged_lbs_pose(int P, int V, const float *tetpoints, const int32_t *tetras,
+                                                    const int32_t *tetra_id, const float *barys, const float *canon_grad,
+                                                    const float *scales, const float *rots, const float *delta_barys, int32_t flags,
+                                                    const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
+                                                    float *g_scales, float *g_rots, const uint16_t *item_pos, const int32_t *seg_ptr,
+                                                    const uint16_t *seg_begin, int32_t n_segments, const int32_t *vert_start,
+                                                    const int32_t *vert_parts, float *partials, int K, const float *joint_mats,
+                                                    const int32_t *skin_idx, const float *skin_w, const float *Rh,
+                                                    const float *g_tetpoints_extra, float *g_delta, const d3ga_lbs_pose_grad *pose,
+                                                    d3ga_stream_t stream) {
+    if (V <= 0 || K <= 0) return D3GA_E_SIZE;
+    D3GA_TRY(pose_check(V, K, pose));
+    // the vertex gradient g: the caller's g_tetpoints, or the scratch behind the partials
+    float *gv = g_tetpoints ? g_tetpoints : (float *)pose->scratch + 12 * pose_groups(V, pose->n_chunks);
+    D3GA_TRY(d3ga_cage_deform_bwd_merged_lbs(P, V, tetpoints, tetras, tetra_id, barys, canon_grad, scales, rots, delta_barys, flags,
+                                             g_means, g_cov6, gv, g_barys, g_scales, g_rots, item_pos, seg_ptr, seg_begin, n_segments,
+                                             vert_start, vert_parts, partials, K, joint_mats, skin_idx, skin_w, Rh, g_tetpoints_extra,
+                                             g_delta, stream));
+    return pose_reduce(V, K, joint_mats, skin_idx, skin_w, Rh, gv, pose, (hipStream_t)stream);
 }
 
 extern "C" int d3ga_cage_deform_bwd(int P, int V, const float *tetpoints, const int32_t *tetras,

@@ -68,12 +68,48 @@ int d3ga_debug_defaults(int32_t *out, int32_t n);
  *   tmpl (V,3), delta (V,3)|NULL, joint_mats (J,4,4), skin_idx (V,K) int32, skin_w (V,K),
  *   Rh (3,3)|NULL, Th (3)|NULL  ->  out (V,3).
  * bwd: grad_out (V,3) -> grad_delta (V,3)  (= gradient w.r.t. the template offset / deformation_field output).
+ * bwd_pose: the same plus the pose gradients (the body pose reaches the cage through joint_mats, Rh and Th).  With
+ *   p~ = [tmpl + delta; 1], o = (sum_k w_k A[idx_k]) p~, g = grad_out and g' = Rh^T g:
+ *     g_joint_mats[j][0:3][0:4] = sum over the (v,k) with idx = j of w_vk g'_v p~_v^T, row 3 = 0 (the forward never reads it);
+ *     g_Rh = sum_v g_v o_v^T (3,3);  g_Th = sum_v g_v (3).
+ *   A joint listed twice in a row counts twice; a joint with no entry gets exact zeros.  The sums follow a static by-joint
+ *   plan (struct d3ga_lbs_pose_grad, built once per binding: d3ga_amd/cage_deform.py lbs_pose_plan) in a fixed order, with no
+ *   float atomics: repeated calls are bit-identical.  One launch after d3ga_lbs_cage_bwd's own (which runs unchanged, so
+ *   grad_delta is bit-identical to it): a by-joint reduction whose last workgroup forms the totals.  No host synchronisation,
+ *   capturable.
  * ------------------------------------------------------------------------------------------------------- */
 int d3ga_lbs_cage_fwd(int V, int K, const float *tmpl, const float *delta, const float *joint_mats,
                       const int32_t *skin_idx, const float *skin_w, const float *Rh, const float *Th, float *out,
                       d3ga_stream_t stream);
 int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
                       const float *Rh, const float *grad_out, float *grad_delta, d3ga_stream_t stream);
+/* The by-joint plan and the outputs of the pose backward.  entries (n_entries = V*K): the flat indices v*K + k of skin_idx
+ * sorted by joint (stable); chunk_range (n_chunks, 2; 8-byte aligned): [begin, end) of each chunk of entries, at most 256
+ * entries, never straddling a joint; chunk_ptr (J + 1): the first chunk of each joint.  Every skin_idx must lie in [0, J).
+ * tmpl (V,3), delta (V,3) | NULL: the forward's inputs.  counter: one uint32 of the plan, zero when the plan is built and left
+ * zero by every call (its last workgroup re-arms it), so calls that share a plan run one after another (one stream).
+ * scratch: d3ga_lbs_pose_scratch_bytes (4-byte aligned; no initialisation needed).  g_joint_mats (J,4,4), g_Rh (9), g_Th (3):
+ * written (never accumulated), all three required. */
+typedef struct d3ga_lbs_pose_grad {
+    int32_t J;
+    int32_t n_chunks;
+    int64_t n_entries;
+    const float *tmpl;
+    const float *delta;
+    const int32_t *chunk_ptr;
+    const int32_t *chunk_range;
+    const int32_t *entries;
+    uint32_t *counter;
+    void *scratch;
+    float *g_joint_mats;
+    float *g_Rh;
+    float *g_Th;
+} d3ga_lbs_pose_grad;
+/* bytes of scratch for V vertices and n_chunks chunks; fused = 1 for d3ga_cage_deform_bwd_merged_lbs_pose, 0 otherwise */
+int d3ga_lbs_pose_scratch_bytes(int V, int32_t n_chunks, int32_t fused, int64_t *bytes);
+int d3ga_lbs_cage_bwd_pose(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
+                           const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
+                           d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * D1-D5  Fused tetrahedral-cage deformation.
@@ -142,6 +178,18 @@ int d3ga_cage_deform_bwd_merged_lbs(int P, int V, const float *tetpoints, const 
                                     int32_t n_segments, const int32_t *vert_start, const int32_t *vert_parts, float *partials,
                                     int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w, const float *Rh,
                                     const float *g_tetpoints_extra, float *g_delta, d3ga_stream_t stream);
+/* ... and the pose gradients of D0 (as d3ga_lbs_cage_bwd_pose, with g = the gathered vertex gradient plus g_tetpoints_extra):
+ * d3ga_cage_deform_bwd_merged_lbs runs unchanged (its other outputs bit-identical), its vertex gradient kept in g_tetpoints or,
+ * when that is NULL, in the scratch; one by-joint reduction launch follows.  V > 0. */
+int d3ga_cage_deform_bwd_merged_lbs_pose(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
+                                         const float *barys, const float *canon_grad, const float *scales, const float *rots,
+                                         const float *delta_barys, int32_t flags, const float *g_means, const float *g_cov6,
+                                         float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
+                                         const uint16_t *item_pos, const int32_t *seg_ptr, const uint16_t *seg_begin,
+                                         int32_t n_segments, const int32_t *vert_start, const int32_t *vert_parts, float *partials,
+                                         int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w, const float *Rh,
+                                         const float *g_tetpoints_extra, float *g_delta, const d3ga_lbs_pose_grad *pose,
+                                         d3ga_stream_t stream);
 
 /* D6  FEM regulariser (lib/cage.py:349-361): per-tet energy 0.5(det F-1)^2 + 0.5(|F|_F^2-3), F = Ds Dn^-1.
  *   fwd: energy (T).  bwd: g_energy (T) -> g_tetpoints (V,3) [zeroed by the call]. */

@@ -17,6 +17,8 @@ called as they are:
   G7 ply      models.cage_net.CageNet.describe_ply / get_ply (unbound)     -> ply_case.npz
   G8 lbs (Goliath)  lbsmodel.body_model.states_to_matrix + LinearBlendSkinning.skinning (unbound; 8-sparse
               indices / weights) + autograd gradient w.r.t. the vertices          -> lbs_goliath_case.npz
+  G9 lbs pose  G6 with A, the Rh matrix and Th as leaves + G8 with target_states a leaf: autograd gradients
+              (only with the argument `lbs_pose`)                                  -> lbs_pose_grad_case.npz
 The only stand-in with numerical content is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
@@ -372,6 +374,61 @@ def gen_lbs_goliath(bm):
              mat=mat.detach().numpy(), out=out.detach().numpy(), grad_out=gout.numpy(), grad_vertices=verts.grad[0].numpy())
 
 
+def gen_lbs_pose(smplman_mod, bm):
+    """The pose gradients of the two skinnings (`python tools/gen_golden.py lbs_pose`; every other fixture is left as it is):
+    lib/smplman.py:155-171 Smplman.deform (unbound) with the joint transforms A, the global rotation matrix (a leaf returned by
+    the batch_rodrigues stand-in) and Th as leaves, and lbsmodel/body_model.py:208-234 + 350-387 with target_states a leaf; outputs
+    and the reference's autograd gradients for a fixed upstream gradient."""
+    g = torch.Generator().manual_seed(31)
+    V, J = 64, 7
+    w = torch.rand(V, J, generator=g)
+    w[w < 0.45] = 0.0                                # sparse rows, as SMPL-X's are
+    w[torch.arange(V), torch.randint(0, J, (V,), generator=g)] += 0.1
+    w[:, 5] = 0.0                                    # a joint no vertex uses: exact-zero gradient
+    w = w / w.sum(1, keepdim=True)
+    A = torch.eye(4)[None].repeat(J, 1, 1)
+    A[:, :3, :] += torch.randn(J, 3, 4, generator=g) * 0.2
+    A = A.requires_grad_(True)
+    tmpl = torch.randn(1, V, 3, generator=g)
+    delta = torch.randn(V, 3, generator=g) * 0.01
+    Rh_mat = torch.linalg.qr(torch.randn(3, 3, generator=g))[0].requires_grad_(True)
+    Th = torch.randn(1, 3, generator=g).requires_grad_(True)
+    smplman_mod.batch_rodrigues = lambda rh: Rh_mat[None]      # un-vendored tetra_sampler.lbs helper: the matrix is the leaf
+    ns = SimpleNamespace(lbs_module=SimpleNamespace(J_regressor=torch.zeros(J, 1)), skin_weights=w,
+                         body_template_vertices=tmpl, nn_ids=torch.arange(V))
+    ns.to_homo = lambda v: smplman_mod.Smplman.to_homo(ns, v)
+    out = smplman_mod.Smplman.deform(ns, A[None], torch.zeros(1, V, 3), torch.zeros(1, 3), Th, delta)
+    gout = torch.randn(out.shape, generator=g)
+    (out * gout).sum().backward()
+    smpl = dict(weights=w.numpy(), A=A.detach().numpy(), template=tmpl[0].numpy(), delta=delta.numpy(), Rh=Rh_mat.detach().numpy(),
+                Th=Th.detach()[0].numpy(), out=out.detach()[0].numpy(), grad_out=gout[0].numpy(), grad_A=A.grad.numpy(),
+                grad_Rh=Rh_mat.grad.numpy(), grad_Th=Th.grad[0].numpy())
+
+    Vg, Jg, K, B = 300, 24, 8, 2
+
+    def states(n):
+        q = torch.randn(n, Jg, 4, generator=g)
+        q = q / q.norm(dim=2, keepdim=True)
+        t = torch.randn(n, Jg, 3, generator=g) * 0.5
+        sc = torch.exp(0.2 * torch.randn(n, Jg, 1, generator=g))
+        return torch.cat([t, q, sc], dim=2)
+    bind, target = states(1), states(B).requires_grad_(True)
+    idx = torch.randint(0, Jg - 2, (Vg, K), generator=g)            # the last two joints carry no vertex
+    idx[:, 1] = idx[:, 0]                                            # a joint listed twice in a row counts twice
+    wg = torch.rand(Vg, K, generator=g)
+    wg[:, 6:] = 0.0
+    wg = wg / wg.sum(1, keepdim=True)
+    verts = torch.randn(1, Vg, 3, generator=g)
+    gns = SimpleNamespace(skin_indices=idx, skin_weights=wg)
+    gres = bm.LinearBlendSkinning.skinning(gns, bind, verts, target)
+    ggout = torch.randn(gres.shape, generator=g)
+    (gres * ggout).sum().backward()
+    np.savez(os.path.join(OUT, "lbs_pose_grad_case.npz"), **smpl, g_bind_state=bind.numpy(),
+             g_target_states=target.detach().numpy(), g_skin_indices=idx.numpy().astype(np.int32), g_skin_weights=wg.numpy(),
+             g_vertices=verts[0].numpy(), g_out=gres.detach().numpy(), g_grad_out=ggout.numpy(),
+             g_grad_target_states=target.grad.numpy())
+
+
 def gen_losses(loss_utils):
     """utils/loss_utils.py: l1_loss (:29) and ssim (:59-86) of the reference on seeded images, values and autograd
     gradients w.r.t. the first image (sizes chosen to cross tile borders of the HIP kernel: not multiples of 16)."""
@@ -534,6 +591,10 @@ def main():
 
     if sys.argv[1:] == ["ply"]:                 # one section only (the other fixtures are left untouched)
         gen_ply(cn)
+        return
+    if sys.argv[1:] == ["lbs_pose"]:
+        import lbsmodel.body_model as bm
+        gen_lbs_pose(smplman_mod, bm)
         return
     if sys.argv[1:] == ["lbs_goliath"]:
         import lbsmodel.body_model as bm

@@ -17,4 +17,5 @@ run lbs_fuzz      D3GA_LBS_FUZZ_N=${N_LBS:-500} timeout 900 python -m pytest tes
 run fem_fuzz      D3GA_FEM_FUZZ_N=${N_FEM:-600} timeout 1200 python -m pytest tests -m gpu -q -k fem_energy_fuzz
 run init_fuzz     D3GA_INIT_FUZZ_N=${N_INIT:-400} timeout 1200 python -m pytest tests -m gpu -q -k init_helpers_fuzz
 run body_fuzz     D3GA_BODY_FUZZ_N=${N_BODY:-500} timeout 900 python -m pytest tests -m gpu -q -k test_body_model_fuzz
+run lbs_pose_fuzz D3GA_LBS_POSE_FUZZ_N=${N_LBS_POSE:-500} timeout 1200 python -m pytest tests -m gpu -q -k test_lbs_pose_fuzz
 cat gpurun_out/campaigns.log
