@@ -73,30 +73,33 @@ __device__ __forceinline__ void row_scan_add4(float &a, float &b, float &c, floa
     if constexpr (R >= 4) asm("s_nop 1\n" D3GA_SCANX("v_add_f32_dpp", "row_bcast:31", "0xc") : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
 
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+// (vector types: each load's registers stay one tuple that the prefetch fills in place -- as scalars the compiler may give
+// them scattered registers and copy them over right behind the load, waiting for it)
 struct ScanEntry {          // one list entry as the lane that owns it holds it
     uint32_t pos, gid;      // 1-based position in the tile list (0: no entry), Gaussian index
-    float2 xy;
-    float4 co;              // conic a, b, c | opacity
-    float4 rgb;             // colour | 1/depth (unused here)
+    f2 xy;
+    f4 co;                  // conic a, b, c | opacity
+    f4 rgb;                 // colour | 1/depth (unused here)
     float c2r, c2g, c2b;    // DUAL: the second image's colour
 };
 
+// Loads the entry pg into e.  A lane without an entry (pg.x = 0) loads nothing and keeps what e held (zeros, or an entry of
+// an earlier group: finite values) -- the validity test's list-position term rejects it at every pixel (composite below), so no
+// zeroing and no copies are needed here.
 template <bool DUAL>
-__device__ __forceinline__ ScanEntry scan_gather(uint2 pg, const float2 *__restrict__ xy, const float4 *__restrict__ conic_o,
-                                                 const float4 *__restrict__ rgb_invd, const float *__restrict__ colors2 /* DUAL: already moved back by 3 x view x P (the lists hold (view, Gaussian) indices, colors2 is per Gaussian) */) {
-    ScanEntry e;
+__device__ __forceinline__ void scan_gather(ScanEntry &e, uint2 pg, const float2 *__restrict__ xy, const float4 *__restrict__ conic_o,
+                                            const float4 *__restrict__ rgb_invd, const float *__restrict__ colors2 /* DUAL: already moved back by 3 x view x P (the lists hold (view, Gaussian) indices, colors2 is per Gaussian) */) {
     e.pos = pg.x; e.gid = pg.y;
-    e.xy = make_float2(0.f, 0.f);
-    e.co = make_float4(0.f, 0.f, 0.f, 0.f);
-    e.rgb = make_float4(0.f, 0.f, 0.f, 0.f);
-    e.c2r = e.c2g = e.c2b = 0.f;
     if (pg.x != 0u) {
-        e.xy = xy[2 * (size_t)pg.y]; e.co = conic_o[pg.y]; e.rgb = rgb_invd[pg.y];      // xy: the xyh records viewed as float2 (stride 2)
+        e.xy = *reinterpret_cast<const f2 *>(xy + 2 * (size_t)pg.y);      // xy: the xyh records viewed as float2 (stride 2)
+        e.co = *reinterpret_cast<const f4 *>(conic_o + pg.y);
+        e.rgb = *reinterpret_cast<const f4 *>(rgb_invd + pg.y);
         if constexpr (DUAL) {
             e.c2r = colors2[3 * (size_t)pg.y]; e.c2g = colors2[3 * (size_t)pg.y + 1]; e.c2b = colors2[3 * (size_t)pg.y + 2];
         }
     }
-    return e;
 }
 
 #ifdef D3GA_DIAG
@@ -106,12 +109,10 @@ __device__ unsigned long long g_diag_waves[32768 * 4];   // per active wave: s_m
 // forces the compiler's s_waitcnt for these registers HERE (an empty asm that reads them)
 template <bool DUAL>
 __device__ __forceinline__ void scan_consume(ScanEntry &e, uint2 &pg) {
-    asm volatile("" : "+v"(e.xy.x), "+v"(e.xy.y), "+v"(e.co.x), "+v"(e.co.y), "+v"(e.co.z), "+v"(e.co.w));
-    asm volatile("" : "+v"(e.rgb.x), "+v"(e.rgb.y), "+v"(e.rgb.z), "+v"(pg.x), "+v"(pg.y));
+    asm volatile("" : "+v"(e.xy), "+v"(e.co), "+v"(e.rgb), "+v"(pg.x), "+v"(pg.y));
     if constexpr (DUAL) asm volatile("" : "+v"(e.c2r), "+v"(e.c2g), "+v"(e.c2b));
 }
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
@@ -181,10 +182,10 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
     float *const wr_base = lseg == LW - 1 ? pixrow : s_dump + 2 * lane;
     {
         float *rec = pixrow + l16 * PIXF;
-        *reinterpret_cast<float4 *>(rec) = make_float4(T_final, 0.f, g0, g1);
+        *reinterpret_cast<float4 *>(rec) = make_float4(T_final, T_final * bg_dot, g0, g1);      // (T, S + T_final (bg . g)) carried
         float gd = 0.f;
         if constexpr (INVD) gd = inside ? A.dL_dinvd[pid1] : 0.f;
-        *reinterpret_cast<float4 *>(rec + 4) = make_float4(g2, T_final * bg_dot, __uint_as_float(last), gd);
+        *reinterpret_cast<float4 *>(rec + 4) = make_float4(g2, 0.f, __uint_as_float(last), gd);
         if constexpr (DUAL) *reinterpret_cast<float4 *>(rec + 8) = make_float4(h0, h1, h2, 0.f);
     }
     const uint32_t blk_cap = end - begin;
@@ -204,22 +205,32 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
         return v;
     };
     const float *const colors2v = DUAL ? A.colors2 - 3 * (size_t)view * (size_t)A.P : nullptr;
-    ScanEntry e = scan_gather<DUAL>(list_entry(0), A.xy, A.conic_o, A.rgb_invd, colors2v);
+    ScanEntry e0, e1;
+    e0.xy = f2{0.f, 0.f};
+    e0.co = f4{0.f, 0.f, 0.f, 0.f};
+    e0.rgb = f4{0.f, 0.f, 0.f, 0.f};
+    e0.c2r = e0.c2g = e0.c2b = 0.f;
+    scan_gather<DUAL>(e0, list_entry(0), A.xy, A.conic_o, A.rgb_invd, colors2v);
+    e1 = e0;
     uint2 pg1 = list_entry(1);
     __builtin_amdgcn_wave_barrier();
 
-    for (int g = 0; g < ngroups; ++g) {
-        ScanEntry nxt = scan_gather<DUAL>(pg1, A.xy, A.conic_o, A.rgb_invd, colors2v);
+    // One group: entry e (loaded one group ahead into nxt, list entries two groups ahead).  The loop below runs two groups per
+    // trip with the roles of e0 and e1 swapped, so the prefetch lands in place: no register copies between groups and no
+    // wait on the loads before the group's work (a rotation e = nxt made the compiler copy the loaded registers right
+    // behind the loads).
+    auto group = [&](ScanEntry &e, ScanEntry &nxt, const int g) {
+        scan_gather<DUAL>(nxt, pg1, A.xy, A.conic_o, A.rgb_invd, colors2v);
         uint2 pg2 = list_entry(g + 2);
         const bool act = e.pos != 0u;
         const float exr = e.xy.x - bxr, eyr = e.xy.y - byr;
         const ConicQ cq = conic_q(e.co.x, e.co.y, e.co.z);
-        // Geometric moments with the weight gop = G dL/dalpha (the opacity factor is applied once per entry) and the pixel
+        // Geometric moments with the weight gop = o G dL/dalpha (dL/do = sum G dL/dalpha: divided by o once per entry) and the pixel
         // offsets k = 0..3 of a block line as compile-time constants: per line  A = sum gop, B = sum k gop, C = sum k^2 gop
-        // (7 instructions for 4 pixels), accumulated as sums of A, B, C, dy A, dy B, dy^2 A; the centred moments follow at the
-        // end of the group from dx = exr - k:  sum gop dx = exr SA - SB,  sum gop dx^2 = exr^2 SA - 2 exr SB + SC, ...
+        // (7 instructions for 4 pixels), accumulated as sums of A, B, C, ky A, ky B, ky^2 A; the centred moments follow at the
+        // end of the group from dx = exr - k, dy = eyr - ky:  sum gop dx = exr SA - SB,  sum gop dx^2 = exr^2 SA - 2 exr SB + SC, ...
         // (3.5 instructions per pixel step instead of 9: w, wx, wy and six accumulations).
-        float SA = 0.f, SB = 0.f, SC = 0.f, SyA = 0.f, SyB = 0.f, SyyA = 0.f, M6 = 0.f, M7 = 0.f, M8 = 0.f, M9 = 0.f;
+        float SA = 0.f, SB = 0.f, SC = 0.f, TyA = 0.f, TyB = 0.f, TyyA = 0.f, M6 = 0.f, M7 = 0.f, M8 = 0.f, M9 = 0.f;
 #if D3GA_TILE_PRIO
         {   // (the priority is an immediate)
             const int left = ngroups - g;
@@ -229,7 +240,17 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
             else __builtin_amdgcn_s_setprio(0);
         }
 #endif
-#pragma unroll 1
+        float dx[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dx[k] = exr - (float)k;
+        // The four block lines, unrolled (record offsets and k, ky are immediates; no loop bookkeeping).  Per pixel step:
+        //   * one select: an invalid pair gets o G = 0, so alpha = 0 (r = 1) and the pair's weight Gr = o G r is 0 too --
+        //     its gradient terms vanish through the products that are already there;
+        //   * the record carries S + T_final (bg . g) (the prologue seeds it), and with the INCLUSIVE colour-behind sum
+        //     S' = S_i + u_i + T_final (bg . g), u_i = alpha_i T_i (c_i . g), dL/dalpha_i = T_i (c . g) - (S_i + T_final (bg . g)) r_i
+        //     is (T_i (c . g) - S') r_i exactly (T_i (c . g) - u_i = T_i (c . g) / r_i): one fma, and r_i folds into Gr;
+        //   * the geometric moments carry the opacity (Gr = o G r): the per-entry factor o is gone, dL/do = SA / o.
+#pragma unroll
         for (int ky = 0; ky < (D3GA_SCAN_ABL == 8 ? 0 : 4); ++ky) {
             const float *const pixq = pixrow + ky * 4 * PIXF;
             float4 pa[4], pb[4], pc[4];
@@ -238,58 +259,69 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
                 pa[k] = *reinterpret_cast<const float4 *>(pixq + k * PIXF);
                 pb[k] = *reinterpret_cast<const float4 *>(pixq + k * PIXF + 4);
                 if constexpr (DUAL) pc[k] = *reinterpret_cast<const float4 *>(pixq + k * PIXF + 8);
-                // the whole record is loaded HERE: left alone the compiler sinks the load of T_final (A.bg . g) into a
-                // divergent region behind `valid` -- an LDS round trip in the middle of every block line
-                asm volatile("" : "+v"(pb[k].x), "+v"(pb[k].y), "+v"(pb[k].z));
+                // the whole record is loaded HERE: left alone the compiler sinks the load of the colour gradient into a
+                // divergent region -- an LDS round trip in the middle of every block line
+                asm volatile("" : "+v"(pb[k].x), "+v"(pb[k].z));
                 if constexpr (INVD) asm volatile("" : "+v"(pb[k].w));
             }
             const float dy = eyr - (float)ky;
             const float tb = cq.b * dy, tc = (cq.c * dy) * dy;
-            float al[4], G[4], r[4], u[4], cgv[4], dx[4];
-            bool valid[4];
+            float al[4], Gr[4], cgv[4], r4[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                dx[k] = exr - (float)k;
+                // alpha as the forward forms it (splat_eval_q: p, G = exp2(p), alpha = min(kAlphaMax, o G)) and the forward's
+                // test (p <= 0, alpha >= 1/255 -- for alpha = min(kAlphaMax, o G) the same as o G >= 1/255 --, list
+                // position <= the pixel's n_contrib); a lane without an entry (pos = 0) is never valid
+                float alpha, G;
                 bool ok;
-                splat_eval_q(dx[k], tb, tc, cq.a, e.co.w, al[k], G[k], ok);
-                valid[k] = ok & (e.pos <= __float_as_uint(pb[k].z));     // (a lane without an entry has opacity 0: never ok)
+                splat_eval_q(dx[k], tb, tc, cq.a, e.co.w, alpha, G, ok);
+                const float p = fmaf(dx[k], fmaf(cq.a, dx[k], tb), tc);      // (splat_eval_q's log2 G: the same instructions)
+                const float oG = e.co.w * G;
+                const bool valid = (p <= 0.0f) & (oG >= kAlphaMin) & (e.pos - 1u < __float_as_uint(pb[k].z));   // pos <= n_contrib, and never for pos = 0
 #ifdef D3GA_DIAG_COUNTERS
-                dg.valid += valid[k] ? 1 : 0;          // lane efficiency: valid (entry, pixel) pairs / issued lane slots
+                dg.valid += valid ? 1 : 0;          // lane efficiency: valid (entry, pixel) pairs / issued lane slots
 #endif
-                al[k] = valid[k] ? al[k] : 0.f;
-                r[k] = __builtin_amdgcn_rcpf(1.0f - al[k]);
+                const float oGv = valid ? oG : 0.f;
+                al[k] = fminf(kAlphaMax, oGv);                                     // == alpha where valid, else 0
+                const float r = __builtin_amdgcn_rcpf(1.0f - al[k]);
+                Gr[k] = oGv * r;
                 cgv[k] = e.rgb.x * pa[k].z + e.rgb.y * pa[k].w + e.rgb.z * pb[k].x;
                 if constexpr (DUAL) cgv[k] += e.c2r * pc[k].x + e.c2g * pc[k].y + e.c2b * pc[k].z;
                 if constexpr (INVD) cgv[k] = fmaf(e.rgb.w, pb[k].w, cgv[k]);
+                r4[k] = r;
             }
-            float p0 = r[0], p1 = r[1], p2 = r[2], p3 = r[3];
-            row_scan_mul4<R>(p0, p1, p2, p3);
-            const float Ti[4] = {pa[0].x * p0, pa[1].x * p1, pa[2].x * p2, pa[3].x * p3};
-            float dch[4];
+            row_scan_mul4<R>(r4[0], r4[1], r4[2], r4[3]);
+            float Ti[4], dch[4], s[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { dch[k] = al[k] * Ti[k]; u[k] = cgv[k] * dch[k]; }
-            float s0 = u[0], s1 = u[1], s2 = u[2], s3 = u[3];
-            row_scan_add4<R>(s0, s1, s2, s3);
-            const float Sin[4] = {s0 + pa[0].y, s1 + pa[1].y, s2 + pa[2].y, s3 + pa[3].y};
+            for (int k = 0; k < 4; ++k) { Ti[k] = pa[k].x * r4[k]; dch[k] = al[k] * Ti[k]; s[k] = cgv[k] * dch[k]; }
+            row_scan_add4<R>(s[0], s[1], s[2], s[3]);
             float *const wq = wr_base + ky * 4 * PIXF;
             float gop[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float dLda = Ti[k] * cgv[k] - (Sin[k] - u[k] + pb[k].y) * r[k];
-                gop[k] = valid[k] ? G[k] * dLda : 0.f;
-                M6 += dch[k] * pa[k].z; M7 += dch[k] * pa[k].w; M8 += dch[k] * pb[k].x;
+                const float Sin = s[k] + pa[k].y;
+                gop[k] = Gr[k] * fmaf(Ti[k], cgv[k], -Sin);
+                M6 = fmaf(dch[k], pa[k].z, M6); M7 = fmaf(dch[k], pa[k].w, M7); M8 = fmaf(dch[k], pb[k].x, M8);
                 if constexpr (INVD) M9 = fmaf(dch[k], pb[k].w, M9);
-                *reinterpret_cast<float2 *>(wq + k * PIXF) = make_float2(Ti[k], Sin[k]);
+                *reinterpret_cast<float2 *>(wq + k * PIXF) = make_float2(Ti[k], Sin);
             }
             const float A = (gop[0] + gop[1]) + (gop[2] + gop[3]);
             const float B = fmaf(3.0f, gop[3], fmaf(2.0f, gop[2], gop[1]));
             const float C = fmaf(9.0f, gop[3], fmaf(4.0f, gop[2], gop[1]));
-            SA += A; SB += B; SC += C;
-            SyA = fmaf(dy, A, SyA); SyB = fmaf(dy, B, SyB); SyyA = fmaf(dy * dy, A, SyyA);
+            // (the lines are unrolled: the first one sets the sums, and the y moments are taken about the block's first line
+            // with ky, ky^2 as immediates -- sums of ky A, ky B, ky^2 A -- and centred at the end of the group like the x ones)
+            if (ky == 0) { SA = A; SB = B; SC = C; }
+            else { SA += A; SB += B; SC += C; }
+            if (ky == 1) { TyA = A; TyB = B; TyyA = A; }
+            if (ky >= 2) { TyA = fmaf((float)ky, A, TyA); TyB = fmaf((float)ky, B, TyB); TyyA = fmaf((float)(ky * ky), A, TyyA); }
         }
-        const float M5 = SA, ow = e.co.w;
-        const float M0 = ow * (exr * SA - SB), M1 = ow * SyA;
-        const float M2 = ow * (exr * (exr * SA - 2.0f * SB) + SC), M3 = ow * (exr * SyA - SyB), M4 = ow * SyyA;
+        // dy = eyr - ky:  sum dy A = eyr SA - sum ky A,  sum dy^2 A = eyr (eyr SA - 2 sum ky A) + sum ky^2 A
+        const float eSA = eyr * SA;
+        const float SyA = eSA - TyA, SyB = fmaf(eyr, SB, -TyB), SyyA = fmaf(eyr, fmaf(-2.0f, TyA, eSA), TyyA);
+        // dL/do = sum G dL/dalpha = SA / o (a lane whose opacity is below 1/255 has no valid pair: SA = 0)
+        const float M5 = SA * __builtin_amdgcn_rcpf(fmaxf(e.co.w, kAlphaMin));
+        const float M0 = exr * SA - SB, M1 = SyA;
+        const float M2 = exr * (exr * SA - 2.0f * SB) + SC, M3 = exr * SyA - SyB, M4 = SyyA;
         const float v0 = -(e.co.x * M0 + e.co.y * M1) * ddelx_dx;
         const float v1 = -(e.co.z * M1 + e.co.y * M0) * ddely_dy;
         const float4 va = make_float4(v0, v1, -0.5f * M2, -0.5f * M3), vb = make_float4(-0.5f * M4, M5, M6, M7);
@@ -301,7 +333,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
         // lock holder owns it; a loser discards them.  Stores + the releasing tag store likewise need no wait.
         const uint32_t saddr = (uint32_t)(uintptr_t)(lds_u32 *)(s_cache + ((e.pos - 1u) & (uint32_t)(S - 1)) * kSlot);
         // an entry that touched no pixel has nothing but (exact) zeros: it stays out of the cache
-        const uint32_t anybits = (__float_as_uint(SA) | __float_as_uint(SB) | __float_as_uint(SC)) | (__float_as_uint(SyA) | __float_as_uint(SyB) | __float_as_uint(SyyA)) |
+        const uint32_t anybits = (__float_as_uint(SA) | __float_as_uint(SB) | __float_as_uint(SC)) | (__float_as_uint(TyA) | __float_as_uint(TyB) | __float_as_uint(TyyA)) |
                                  (__float_as_uint(M6) | __float_as_uint(M7) | __float_as_uint(M8) | __float_as_uint(M9));
         bool pending = D3GA_SCAN_ABL == 1 ? (anybits == 0x12345u) : (D3GA_SCAN_ABL == 8 ? act : (anybits << 1) != 0u);
 #ifdef D3GA_DIAG_TIMELINE
@@ -392,8 +424,12 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
                 }
             }
         }
-        e = nxt;
         pg1 = pg2;
+    };
+    for (int g = 0; g < ngroups; g += 2) {
+        group(e0, e1, g);
+        if (g + 1 == ngroups) break;
+        group(e1, e0, g + 1);
     }
 }
 
