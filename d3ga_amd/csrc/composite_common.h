@@ -97,14 +97,26 @@ struct ConicQ { float a, b, c; };
 __device__ __forceinline__ ConicQ conic_q(float a, float b, float c) {
     return ConicQ{(-0.5f * kLog2e) * a, (-kLog2e) * b, (-0.5f * kLog2e) * c};
 }
-__device__ __forceinline__ void splat_eval_q(float dx, float tb, float tc, float qa, float o, float &alpha, float &G, bool &ok) {
+__device__ __forceinline__ float splat_eval_q_p(float dx, float tb, float tc, float qa, float o, float &alpha, float &G) {
     const float p = fmaf(dx, fmaf(qa, dx, tb), tc);       // log2 of G
     G = __builtin_amdgcn_exp2f(p);
     alpha = fminf(kAlphaMax, o * G);
+    return p;
+}
+__device__ __forceinline__ void splat_eval_q(float dx, float tb, float tc, float qa, float o, float &alpha, float &G, bool &ok) {
+    const float p = splat_eval_q_p(dx, tb, tc, qa, o, alpha, G);
     ok = (p <= 0.0f) && (alpha >= kAlphaMin);
 }
 __device__ __forceinline__ void splat_eval_q(float dx, float dy, const ConicQ &q, float o, float &alpha, float &G, bool &ok) {
     splat_eval_q(dx, q.b * dy, (q.c * dy) * dy, q.a, o, alpha, G, ok);
+}
+// The same evaluation for a whole wavefront, the verdict as a WAVE MASK (bit l = ok of lane l) instead of a per-lane bool: the
+// forward's blend loop keeps its predicates in SGPR pairs and combines them with scalar instructions.  One expression tree with
+// splat_eval_q (splat_eval_q_p); a ballot of a compare is the compare itself (v_cmp into an
+// SGPR pair: no select, no second compare); only lanes that are active count, so callers run it with every lane active.
+__device__ __forceinline__ unsigned long long splat_eval_q_mask(float dx, float dy, const ConicQ &q, float o, float &alpha, float &G) {
+    const float p = splat_eval_q_p(dx, q.b * dy, (q.c * dy) * dy, q.a, o, alpha, G);
+    return __builtin_amdgcn_ballot_w64(p <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha >= kAlphaMin);
 }
 
 struct RowGeom {
@@ -198,13 +210,15 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v) {       // every lan
 // that hit block r, in list order, and is padded with kNullRec -- the offset of a record with opacity 0, which never blends --
 // so the blend loop needs neither a per-row count nor an index mask.  Returns the trip count (longest list); m[] are the
 // four hit masks.  (LDS instructions of one wavefront execute in order: the padding lands before the entries.)
-constexpr uint16_t kNullRec = 64 * 16;
+// The offsets are 32 bits wide and a row starts 8-byte aligned: the blend loop fetches the two offsets of an iteration with ONE
+// 8-byte read and uses them as addresses as they come (16-bit offsets cost a read each, or an unpack on the VALU).
+constexpr uint32_t kNullRec = 64 * 16;
 constexpr int kListStride = 66;       // 64 entries + two null records: the blend loop reads its offsets one iteration ahead
-__device__ __forceinline__ int build_row_lists(uint16_t (*s_list)[kListStride], bool r0, bool r1, bool r2, bool r3, int lane,
+__device__ __forceinline__ int build_row_lists(uint32_t (*s_list)[kListStride], bool r0, bool r1, bool r2, bool r3, int lane,
                                                unsigned long long (&m)[4]) {
     m[0] = __ballot(r0); m[1] = __ballot(r1); m[2] = __ballot(r2); m[3] = __ballot(r3);
     s_list[0][lane] = kNullRec; s_list[1][lane] = kNullRec; s_list[2][lane] = kNullRec; s_list[3][lane] = kNullRec;
-    const uint16_t mine = (uint16_t)(lane * 16);
+    const uint32_t mine = (uint32_t)(lane * 16);
     if (r0) s_list[0][lanes_below(m[0])] = mine;
     if (r1) s_list[1][lanes_below(m[1])] = mine;
     if (r2) s_list[2][lanes_below(m[2])] = mine;

@@ -106,17 +106,22 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     // (a row maximum), the batch's positions and the row's hit mask -- nothing per blended entry.
     uint32_t used0 = 0, used1 = 0, used2 = 0, used3 = 0;
 
-    __shared__ float4 s_co[65];
-    __shared__ float4 s_rgb[65];
-    __shared__ float4 s_xyp[65];
-    __shared__ float4 s_rgb2[DUAL ? 65 : 1];
-    __shared__ uint16_t s_list[4][kListStride];
+    // The wave-private slab: what the blend needs of a staged entry -- ten dwords -- in records of which EVERY dword is read, so
+    // that no read narrows to ds_read_b96 (8 LDS-array cycles for 12 bytes; a ds_read_b128 takes 4, a ds_read_b64 2), all at
+    // 16 x slot so that one list offset addresses them:
+    //   s_xyq {x, y, q.a, q.b}   s_cor {q.c, opacity, r, g}   s_bp {b, 1-based list position | DUAL: r2, g2 | DEPTH alone: -, 1/depth}
+    // DUAL's remaining dwords {b2, 1/depth} live at 8 x slot in s_ext.  Slot 64 is the null record (opacity 0).
+    __shared__ float4 s_xyq[65];
+    __shared__ float4 s_cor[65];
+    __shared__ float4 s_bp[65];
+    __shared__ float2 s_ext[DUAL ? 65 : 1];
+    __shared__ __attribute__((aligned(8))) uint32_t s_list[4][kListStride];
     constexpr int kRing = 256;                            // survivors of stage one: (1-based list position, Gaussian id)
     __shared__ uint2 s_ring[kRing];
     if (threadIdx.x == 0) {
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        s_co[64] = z; s_rgb[64] = z; s_xyp[64] = z;
-        if constexpr (DUAL) s_rgb2[64] = z;
+        s_xyq[64] = z; s_cor[64] = z; s_bp[64] = z;
+        if constexpr (DUAL) s_ext[64] = make_float2(0.f, 0.f);
     }
     if (threadIdx.x < 8) s_list[threadIdx.x >> 1][64 + (threadIdx.x & 1)] = kNullRec;
 
@@ -130,7 +135,9 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f;
     float E0 = 0.f, E1 = 0.f, E2 = 0.f;
     uint32_t last = 0;
-    bool done = !inside;
+    // the saturated (or absent) pixels as a wave mask: it is combined with the alpha verdicts on the scalar side and tested whole
+    // (every lane of the wavefront is active from here to the end of the batch loop)
+    unsigned long long donem = ~__builtin_amdgcn_ballot_w64(inside);
 
     // ---- stage one state: the list is consumed 128 entries at a time, lane l looks at entries sbase + l and sbase + 64 + l ----
     uint32_t sbase = begin;                               // first list entry of the chunk whose records are in flight
@@ -204,10 +211,16 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
         __builtin_amdgcn_wave_barrier();                  // previous batch's LDS reads are done (program order)
         {
             const ConicQ cq = conic_q(cco.x, cco.y, cco.z);
-            s_co[lane] = make_float4(cq.a, cq.b, cq.c, have ? cco.w : 0.f);
-            s_rgb[lane] = crgb;
-            s_xyp[lane] = make_float4(cxy.x, cxy.y, __uint_as_float(cpg.x), 0.f);
-            if constexpr (DUAL) s_rgb2[lane] = crgb2;
+            s_xyq[lane] = make_float4(cxy.x, cxy.y, cq.a, cq.b);
+            s_cor[lane] = make_float4(cq.c, have ? cco.w : 0.f, crgb.x, crgb.y);
+            if constexpr (DUAL) {
+                s_bp[lane] = make_float4(crgb.z, __uint_as_float(cpg.x), crgb2.x, crgb2.y);
+                s_ext[lane] = make_float2(crgb2.z, crgb.w);
+            } else if constexpr (DEPTH) {
+                s_bp[lane] = make_float4(crgb.z, __uint_as_float(cpg.x), 0.f, crgb.w);
+            } else {
+                *reinterpret_cast<float2 *>(&s_bp[lane]) = make_float2(crgb.z, __uint_as_float(cpg.x));
+            }
         }
         BlockHits bh = block_hits4(cxy.x, cxy.y, hx, hy, bx0, by0);
         if (exact_cull) bh = block_hits4_exact(cxy.x, cxy.y, cco.x, cco.y, cco.z, sc, bx0, by0, bh);
@@ -220,28 +233,18 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
         df_pairs += __popcll(m[0]) + __popcll(m[1]) + __popcll(m[2]) + __popcll(m[3]);
 #endif
         const uint32_t bcb0 = bc0, bcb1 = bc1, bcb2 = bc2, bcb3 = bc3;      // the blocks' counts in front of this batch
-        bool em0 = false, em1 = false, em2 = false, em3 = false;            // the rows that emit this batch's hits
+        // the rows that emit this batch's hits, bit r = row r (an integer on purpose: a bool that lives across the blend loop is kept
+        // as a lane mask, and what is selected by it -- `used` -- lands in vector registers)
+        uint32_t em = 0;
         if (blk_base) {
-            const unsigned long long dm = __builtin_amdgcn_ballot_w64(done);
             const uint2 rec = cpg;                        // 1-based list position, id
-            em0 = (dm & 0xffffull) != 0xffffull; em1 = ((dm >> 16) & 0xffffull) != 0xffffull;
-            em2 = ((dm >> 32) & 0xffffull) != 0xffffull; em3 = (dm >> 48) != 0xffffull;
-            if ((dm & 0xffffull) != 0xffffull) {
-                if (bh.r0) blk_base[bc0 + (uint32_t)lanes_below(m[0])] = rec;
-                bc0 += (uint32_t)__popcll(m[0]);
-            }
-            if (((dm >> 16) & 0xffffull) != 0xffffull) {
-                if (bh.r1) blk_base[blk_cap + bc1 + (uint32_t)lanes_below(m[1])] = rec;
-                bc1 += (uint32_t)__popcll(m[1]);
-            }
-            if (((dm >> 32) & 0xffffull) != 0xffffull) {
-                if (bh.r2) blk_base[2 * (size_t)blk_cap + bc2 + (uint32_t)lanes_below(m[2])] = rec;
-                bc2 += (uint32_t)__popcll(m[2]);
-            }
-            if ((dm >> 48) != 0xffffull) {
-                if (bh.r3) blk_base[3 * (size_t)blk_cap + bc3 + (uint32_t)lanes_below(m[3])] = rec;
-                bc3 += (uint32_t)__popcll(m[3]);
-            }
+            auto emit = [&](int r, bool hit, unsigned long long mr, uint32_t &bc) {
+                if (((donem >> (16 * r)) & 0xffffull) == 0xffffull) return;      // the row's 16 pixels are saturated (wave-uniform)
+                if (hit) blk_base[(size_t)r * blk_cap + bc + (uint32_t)lanes_below(mr)] = rec;
+                bc += (uint32_t)__popcll(mr);
+                em |= 1u << r;
+            };
+            emit(0, bh.r0, m[0], bc0); emit(1, bh.r1, m[1], bc1); emit(2, bh.r2, m[2], bc2); emit(3, bh.r3, m[3], bc3);
         }
         // ---- the next batch: stage one from the chunk in flight, then its gathers and the next chunk's loads ----
         fill();
@@ -249,68 +252,70 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
         issue_batch();
         __builtin_amdgcn_wave_barrier();
         // ---- blend ----
-        const uint16_t *const my_list = s_list[rg.row];
-        bool all_done = false;
+        const uint32_t *const my_list = s_list[rg.row];
 #ifdef D3GA_DIAG_TIMELINE
         const unsigned long long df_tb = __builtin_amdgcn_s_memrealtime();
 #endif
-        uint32_t p0 = my_list[0], p1 = my_list[1];         // list offsets are read one iteration ahead: off the dependent chain
-        for (int i = 0; i < trip; i += 2) {
-            const uint32_t o0 = p0, o1 = p1;
-            p0 = my_list[i + 2]; p1 = my_list[i + 3];      // (i + 3 <= 65: two null records behind the 64 entries)
-            const float4 e0xy = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_xyp) + o0);
-            const float4 e1xy = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_xyp) + o1);
-            const float4 e0co = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_co) + o0);
-            const float4 e1co = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_co) + o1);
-            const float4 e0rgb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rgb) + o0);
-            const float4 e1rgb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rgb) + o1);
+        // one staged entry through its slab offset; the dwords an instantiation does not use are not read
+        struct Entry { float x, y, qa, qb, qc, o, r, g, b; uint32_t pos; float invd, r2, g2, b2; };
+        auto entry_at = [&](uint32_t off) {
+            const float4 a = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_xyq) + off);
+            const float4 c = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_cor) + off);
+            Entry e = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w, 0.f, 0u, 0.f, 0.f, 0.f, 0.f};
+            if constexpr (DUAL) {
+                const float4 d = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_bp) + off);
+                e.b = d.x; e.pos = __float_as_uint(d.y); e.r2 = d.z; e.g2 = d.w;
+                if constexpr (DEPTH) {
+                    const float2 x = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(s_ext) + (off >> 1));
+                    e.b2 = x.x; e.invd = x.y;
+                } else {
+                    e.b2 = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_ext) + (off >> 1));
+                }
+            } else {
+                const float2 d = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(s_bp) + off);
+                e.b = d.x; e.pos = __float_as_uint(d.y);
+                if constexpr (DEPTH) e.invd = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_bp) + off + 12);
+            }
+            return e;
+        };
+        // front to back, `ok` = the alpha verdict of the 64 pixels as a wave mask
+        auto blend = [&](const Entry &e, float al, unsigned long long ok) {
+            const unsigned long long act = ok & ~donem;
+            const float test_T = T * (1.0f - al);
+            const unsigned long long blm = act & __builtin_amdgcn_ballot_w64(!(test_T < kTmin));
+            const bool bl = __builtin_amdgcn_inverse_ballot_w64(blm);
+            const float w = bl ? al * T : 0.f;
+            C0 += e.r * w; C1 += e.g * w; C2 += e.b * w;
+            if constexpr (DEPTH) Dp += e.invd * w;
+            if constexpr (DUAL) { E0 += e.r2 * w; E1 += e.g2 * w; E2 += e.b2 * w; }
+            T = bl ? test_T : T;
+            last = bl ? e.pos : last;
+            donem |= act ^ blm;                           // reached the entry and stopped at it: saturated
+#ifdef D3GA_DIAG_COUNTERS
+            df_blend += __popcll(blm);
+#endif
+        };
+        // iteration j blends list entries 2j and 2j + 1; their two offsets come with one 8-byte read, one iteration ahead (off
+        // the dependent chain; pair j + 1 <= 32 exists: two null records behind the 64 entries)
+        typedef uint32_t OffPair __attribute__((ext_vector_type(2)));      // (a native vector: stays ONE 8-byte load)
+        const OffPair *lp = reinterpret_cast<const OffPair *>(my_list);
+        const int pairs = (trip + 1) >> 1;
+        OffPair pn = *lp;
+        for (int j = 0; j < pairs; ++j) {
+            const OffPair po = pn;
+            pn = *++lp;
+            const Entry e0 = entry_at(po.x), e1 = entry_at(po.y);
             float al0, G0, al1, G1;
-            bool ok0, ok1;
-            splat_eval_q(e0xy.x - fx, e0xy.y - fy, ConicQ{e0co.x, e0co.y, e0co.z}, e0co.w, al0, G0, ok0);
-            splat_eval_q(e1xy.x - fx, e1xy.y - fy, ConicQ{e1co.x, e1co.y, e1co.z}, e1co.w, al1, G1, ok1);
-            {
-                const bool act = ok0 && !done;
-                const float test_T = T * (1.0f - al0);
-                const bool keep = !(test_T < kTmin);
-                const bool bl = act && keep;
-                const float w = bl ? al0 * T : 0.f;
-                C0 += e0rgb.x * w; C1 += e0rgb.y * w; C2 += e0rgb.z * w;
-                if constexpr (DEPTH) Dp += e0rgb.w * w;
-                if constexpr (DUAL) {
-                    const float4 u = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rgb2) + o0);
-                    E0 += u.x * w; E1 += u.y * w; E2 += u.z * w;
-                }
-                T = bl ? test_T : T;
-                last = bl ? __float_as_uint(e0xy.z) : last;
-                done = done || (act != bl);
-#ifdef D3GA_DIAG_COUNTERS
-                df_blend += __popcll(__builtin_amdgcn_ballot_w64(bl));
-#endif
-            }
-            {
-                const bool act = ok1 && !done;
-                const float test_T = T * (1.0f - al1);
-                const bool keep = !(test_T < kTmin);
-                const bool bl = act && keep;
-                const float w = bl ? al1 * T : 0.f;
-                C0 += e1rgb.x * w; C1 += e1rgb.y * w; C2 += e1rgb.z * w;
-                if constexpr (DEPTH) Dp += e1rgb.w * w;
-                if constexpr (DUAL) {
-                    const float4 u = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rgb2) + o1);
-                    E0 += u.x * w; E1 += u.y * w; E2 += u.z * w;
-                }
-                T = bl ? test_T : T;
-                last = bl ? __float_as_uint(e1xy.z) : last;
-                done = done || (act != bl);
-#ifdef D3GA_DIAG_COUNTERS
-                df_blend += __popcll(__builtin_amdgcn_ballot_w64(bl));
-#endif
+            const unsigned long long ok0 = splat_eval_q_mask(e0.x - fx, e0.y - fy, ConicQ{e0.qa, e0.qb, e0.qc}, e0.o, al0, G0);
+            const unsigned long long ok1 = splat_eval_q_mask(e1.x - fx, e1.y - fy, ConicQ{e1.qa, e1.qb, e1.qc}, e1.o, al1, G1);
+            blend(e0, al0, ok0);
+            blend(e1, al1, ok1);
 #ifdef D3GA_DIAG_TIMELINE
-                df_iters += 1;
+            df_iters += 1;
 #endif
-            }
-            if (__builtin_amdgcn_ballot_w64(done) == ~0ull) { i = trip; all_done = true; }      // whole quadrant saturated
+            if (donem == ~0ull) j = pairs;                // whole quadrant saturated (one exit: a `break` makes the compiler sink the offset read into the next iteration)
         }
+        const bool all_done = donem == ~0ull;
 #ifdef D3GA_DIAG_TIMELINE
         df_blend_ticks += __builtin_amdgcn_s_memrealtime() - df_tb;
 #endif
@@ -321,10 +326,10 @@ __global__ __launch_bounds__(64, (DUAL ? D3GA_FWD_DUAL_WAVES : D3GA_FWD_WAVES)) 
             const uint32_t l2 = (uint32_t)__builtin_amdgcn_readlane((int)rowlast, 32), l3 = (uint32_t)__builtin_amdgcn_readlane((int)rowlast, 48);
             const uint32_t n0 = (uint32_t)__popcll(m[0] & __ballot(cpg.x <= l0)), n1 = (uint32_t)__popcll(m[1] & __ballot(cpg.x <= l1));
             const uint32_t n2 = (uint32_t)__popcll(m[2] & __ballot(cpg.x <= l2)), n3 = (uint32_t)__popcll(m[3] & __ballot(cpg.x <= l3));
-            if (em0 && n0) used0 = bcb0 + n0;
-            if (em1 && n1) used1 = bcb1 + n1;
-            if (em2 && n2) used2 = bcb2 + n2;
-            if (em3 && n3) used3 = bcb3 + n3;
+            if ((em & 1u) && n0) used0 = bcb0 + n0;
+            if ((em & 2u) && n1) used1 = bcb1 + n1;
+            if ((em & 4u) && n2) used2 = bcb2 + n2;
+            if ((em & 8u) && n3) used3 = bcb3 + n3;
         }
         if (all_done) break;
     }
