@@ -16,6 +16,7 @@ ABI_VERSION = 111       # D3GA_VERSION (include/d3ga.h)
 KNOBS = ("composite_variant", "merge_slots", "tile_assign", "bwd_split", "sort_merge", "ssim_impl", "wgrad_ws", "chain_abl", "chain_grid")
 CAMERA_SLOT_WINDOWED = -1.0    # D3GA_CAMERA_SLOT_WINDOWED (include/d3ga.h): tanfovx of a windowed camera slot, 9 floats per view in campos
 LOSS_PARTIALS = 2048     # D3GA_LOSS_PARTIALS (include/d3ga.h): floats of scratch behind a two-stage loss reduction
+BLUR_PARTIALS = 6144     # D3GA_BLUR_PARTIALS (include/d3ga.h): floats of scratch behind d3ga_blur_mix_bwd's three sums
 
 
 class D3GAError(RuntimeError):
@@ -142,6 +143,9 @@ _SIGNATURES = {
     "d3ga_ssim_bwd": ([ctypes.c_int32] * 3 + [_vp] * 7 + [_vp], _i),
     "d3ga_ssim_l1_fwd": ([ctypes.c_int32] * 3 + [_vp] * 7 + [_vp], _i),
     "d3ga_ssim_l1_bwd": ([ctypes.c_int32] * 3 + [_vp] * 8 + [_vp], _i),
+    "d3ga_blur_mix_fwd": ([ctypes.c_int32] * 4 + [_vp] * 4 + [_vp], _i),
+    "d3ga_blur_mix_bwd": ([ctypes.c_int32] * 4 + [_vp] * 7 + [_vp], _i),
+    "d3ga_compose_target": ([ctypes.c_int32] * 3 + [_vp] * 4 + [ctypes.c_int32] + [_vp] * 3 + [_vp], _i),
     "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),
     "d3ga_body_model_fwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 10 + [_vp, _i64, _vp], _i),
     "d3ga_body_model_bwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 12 + [_vp, _i64, _vp], _i),

@@ -564,6 +564,36 @@ int d3ga_ssim_l1_bwd(int32_t C, int32_t H, int32_t W, const float *img1, const f
                      const float *Dq1, const float *Dq12, const float *g, const float *g_l1, float *grad_img1,
                      d3ga_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Image tail of the Goliath configuration (configs/goliath_axe184.yml: use_blur), between render() and the losses.
+ * Learnable blur, models/learnable_blur.py:34-44 (called at models/trainer.py:124-126):
+ *     w = softmax(weights_raw[cam]);   out = w0 img + w1 B3(img) + w2 B7(img)
+ * with Bk the separable k-tap Gaussian (sigma_k = 0.15 k + 0.35, taps exp(-(x / sigma_k)^2 / 2) normalised to sum 1)
+ * over the image extended by k / 2 pixels of reflect padding (torchvision's gaussian_blur; -1 -> 1, H -> H - 2).
+ *   img, out, grad_out, grad_img (C,H,W) f32; weights_raw, grad_weights_raw (n_cameras,3) f32; cam_idx: ONE int32 in
+ *   DEVICE memory, read when the kernel starts (a captured step follows another camera by overwriting it) and clamped to
+ *   [0, n_cameras).  H, W >= 4 (else D3GA_E_SIZE, nothing launched).
+ *   fwd: one launch.
+ *   bwd: grad_img = w0 g + w1 B3^T g + w2 B7^T g (B^T: the adjoint of blur-with-reflect-padding; NULL: skipped), and
+ *        grad_weights_raw[cam][j] = w_j (s_j - sum_i w_i s_i) with s = (<g, img>, <B3^T g, img>, <B7^T g, img>), every
+ *        other row 0: the whole tensor is written (NULL: skipped; img may then be NULL too).  The three sums go through
+ *        `partials` (>= D3GA_BLUR_PARTIALS floats, contents irrelevant): one partial per workgroup, added in index order
+ *        by a second launch -- no zero fill, no atomics, bit-reproducible.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_BLUR_PARTIALS 6144
+int d3ga_blur_mix_fwd(int32_t C, int32_t H, int32_t W, int32_t n_cameras, const float *img, const float *weights_raw,
+                      const int32_t *cam_idx, float *out, d3ga_stream_t stream);
+int d3ga_blur_mix_bwd(int32_t C, int32_t H, int32_t W, int32_t n_cameras, const float *img, const float *weights_raw,
+                      const int32_t *cam_idx, const float *grad_out, float *grad_img, float *grad_weights_raw,
+                      float *partials, d3ga_stream_t stream);
+/* Target composition, train.py:182-188 (no gradient):  m = 1 - float(boundary_fg),
+ *     gt_image = (image alpha + (1 - alpha) bg_c) m + (1 - m) bg_c,     gt_silhouette = silhouette alpha m
+ * image, silhouette, gt_image, gt_silhouette (C,H,W) f32; alpha (H,W) f32; boundary_fg (H,W) uint8 / bool bytes, or f32
+ * with boundary_is_float != 0; bg (C) f32 in device memory. */
+int d3ga_compose_target(int32_t C, int32_t H, int32_t W, const float *image, const float *alpha, const float *silhouette,
+                        const void *boundary_fg, int32_t boundary_is_float, const float *bg, float *gt_image,
+                        float *gt_silhouette, d3ga_stream_t stream);
+
 /* Test hook, not part of the drop-in surface: the 16-lane DPP row scans of the compositing backward.  n multiple of
  * 256; in (n) -> out (8n): for element i (lane l of its row), out[8i+k] = sum over lanes <= l of (k+1) in, k < 4, and
  * out[8i+4+k] = product over lanes <= l of (1 + (k+1)/8 in). */

@@ -19,7 +19,9 @@ called as they are:
               indices / weights) + autograd gradient w.r.t. the vertices          -> lbs_goliath_case.npz
   G9 lbs pose  G6 with A, the Rh matrix and Th as leaves + G8 with target_states a leaf: autograd gradients
               (only with the argument `lbs_pose`)                                  -> lbs_pose_grad_case.npz
-The only stand-in with numerical content is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
+  G10 blur    models.learnable_blur.LearnableBlur (forward, reg, autograd gradients) with the absent torchvision
+              gaussian_blur bound to tests/image_tail_ref.py (only with the argument `blur`, or a full run) -> blur_cases.npz
+The only stand-in with numerical content besides that blur is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
 import importlib.abc
@@ -578,9 +580,42 @@ def gen_ply(cn):
              rotation=self.rotation.numpy(), f_dc=f_dc, f_rest=f_rest, opacity=op, scale=sc, rot=rot)
 
 
+def gen_blur(lb_mod):
+    """G10: models.learnable_blur.LearnableBlur as it is (softmax, mix, camera indexing, reg, the zero rows of the
+    parameter gradient), float64, with autograd gradients for a fixed upstream gradient.  The ONE stand-in is the blur:
+    `torchvision.transforms.functional.gaussian_blur` is absent here, so the name the module imported is bound to
+    tests/image_tail_ref.py:gaussian_blur_ref (the restatement the fixture therefore does NOT pin; its own first-principles
+    tests are in tests/test_image_tail_host.py)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from image_tail_ref import gaussian_blur_ref
+    lb_mod.gaussian_blur = gaussian_blur_ref
+    g = torch.Generator().manual_seed(31)
+    names = ["cam_a", "cam_b", "cam_c"]
+    # (H, W, cameras of the batch): odd sizes, H or W = 4..8, and one batch of two with a repeated camera (summed gradient)
+    cases = [(4, 4, ["cam_a"]), (5, 9, ["cam_c"]), (8, 6, ["cam_b"]), (7, 4, ["cam_b"]), (16, 23, ["cam_a"]),
+             (33, 17, ["cam_c"]), (6, 11, ["cam_b", "cam_b"])]
+    out = {"n": np.array(len(cases)), "names": np.array(names)}
+    for i, (H, W, cams) in enumerate(cases):
+        m = lb_mod.LearnableBlur(names).double()
+        with torch.no_grad():
+            m.weights_raw.copy_(torch.randn(len(names), 3, generator=g, dtype=torch.float64))
+        img = torch.rand(len(cams), 3, H, W, generator=g, dtype=torch.float64).requires_grad_(True)
+        up = torch.randn(len(cams), 3, H, W, generator=g, dtype=torch.float64)
+        res = m(img, cams)
+        g_img, g_w = torch.autograd.grad(res, [img, m.weights_raw], up)
+        out.update({f"cams{i}": np.array(cams), f"idx{i}": m.name_to_idx(cams).numpy(), f"img{i}": img.detach().numpy(),
+                    f"w{i}": m.weights_raw.detach().numpy(), f"up{i}": up.numpy(), f"out{i}": res.detach().numpy(),
+                    f"reg{i}": m.reg(cams).detach().numpy(), f"g_img{i}": g_img.numpy(), f"g_w{i}": g_w.numpy()})
+    np.savez(os.path.join(OUT, "blur_cases.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_harness()
+    if sys.argv[1:] == ["blur"]:                # one section only (the other fixtures are left untouched)
+        import models.learnable_blur as lb_mod
+        gen_blur(lb_mod)
+        return
     import models.cage_net as cn
     from lib.cage import CageBase
     import lib.cameras as cameras_mod
@@ -614,6 +649,8 @@ def main():
     gen_lbs(smplman_mod)
     import lbsmodel.body_model as bm
     gen_lbs_goliath(bm)
+    import models.learnable_blur as lb_mod
+    gen_blur(lb_mod)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
