@@ -594,6 +594,50 @@ int d3ga_compose_target(int32_t C, int32_t H, int32_t W, const float *image, con
                         const void *boundary_fg, int32_t boundary_is_float, const float *bg, float *gt_image,
                         float *gt_silhouette, d3ga_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
+ * parameter in THREE launches whatever the number of tensors (two with clipping off).  The tensors are described by tables
+ * that the caller builds once per set of addresses, in device memory or in pinned host memory mapped to the device (read by
+ * the kernels when they run, the chunk table once per call with clipping on: the form for a captured step, whose replays then
+ * contain no copy node -- the host buffer must stay alive and unmodified as long as the graph is replayed):
+ *   table         n_chunks records, one per run of at most D3GA_OPTIM_CHUNK consecutive elements of one tensor; the chunks
+ *                 of a tensor need not be adjacent in the table.  flags & D3GA_OPTIM_ALIGNED16: p, g, m and v of the chunk
+ *                 are all 16-byte aligned (16-byte loads and stores; otherwise element by element).
+ *   tensor_state  n_tensors records: `step`, ONE float32 in device memory (torch.optim.Adam's state["step"]), read,
+ *                 incremented and written back by the call; `group` indexes group_hparams.
+ *   group_hparams n_groups x 4 doubles in DEVICE memory: lr, beta1, beta2, eps.  Read when the kernels run, so a captured
+ *                 step follows a learning-rate schedule by overwriting them.
+ * With N = sqrt(sum over all chunks of g^2):
+ *     clip_coef = min(1, max_norm / (N + 1e-6))                      (max_norm < 0: no clipping, N is not computed)
+ *     g' = clip_coef g;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2
+ *     p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * g is only read (the gradients stay unclipped).  grad_norm_out: one float32 in device memory receiving N (NULL: skipped;
+ * untouched without clipping).  N is summed without atomics in a fixed order (per chunk in float32; the chunks in double, thread t of one workgroup taking chunks t, t + 256, ... and an LDS tree over
+ * the 256 threads): bit-identical from run to run.  Non-finite gradients propagate as in the reference.
+ * scratch: d3ga_optim_scratch_bytes() bytes, 256-byte aligned, contents irrelevant.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_OPTIM_CHUNK 8192
+#define D3GA_OPTIM_ALIGNED16 1
+typedef struct d3ga_optim_chunk { /* 48 bytes */
+    float *p;                     /* parameter   (read, written) */
+    const float *g;               /* gradient    (read) */
+    float *m;                     /* exp_avg     (read, written) */
+    float *v;                     /* exp_avg_sq  (read, written) */
+    int32_t n;                    /* elements, 1 .. D3GA_OPTIM_CHUNK */
+    int32_t tensor;               /* index into tensor_state */
+    int32_t flags;                /* D3GA_OPTIM_ALIGNED16 */
+    int32_t reserved;
+} d3ga_optim_chunk;
+typedef struct d3ga_optim_tensor { /* 16 bytes */
+    float *step;
+    int32_t group;
+    int32_t reserved;
+} d3ga_optim_tensor;
+int d3ga_optim_scratch_bytes(int32_t n_chunks, int32_t n_tensors, int32_t n_groups, int64_t *out); /* host only */
+int d3ga_optim_clip_adam_step(const d3ga_optim_chunk *table, int32_t n_chunks, const d3ga_optim_tensor *tensor_state,
+                              int32_t n_tensors, const double *group_hparams, int32_t n_groups, float max_norm,
+                              void *scratch, float *grad_norm_out, d3ga_stream_t stream);
+
 /* Test hook, not part of the drop-in surface: the 16-lane DPP row scans of the compositing backward.  n multiple of
  * 256; in (n) -> out (8n): for element i (lane l of its row), out[8i+k] = sum over lanes <= l of (k+1) in, k < 4, and
  * out[8i+4+k] = product over lanes <= l of (1 + (k+1)/8 in). */
