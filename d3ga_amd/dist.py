@@ -285,20 +285,13 @@ class ViewShardedGrads:
     def parked_gradients(self):
         """Deferred mode, after `exchange_parked` (capturable): rasterizer input name -> reduced gradient summed over the
         step's renders, with the SH block rebuilt from the gathered factors (d3ga_sh_grad_from_views)."""
-        from . import _lib
-        from ._lib import check, dptr, stream_handle
+        from .rasterizer import _sh_grad_from_factors
         out = {}
         for e in self.parked:
             mine = dict(e["parts"]) if e.get("head", e) is e else {}       # (a merged entry's parts are inside its head's sum)
             sh = e["sh"]
             if sh is not None:
-                P, M, deg, means3D = sh["P"], sh["M"], sh["sh_degree"], sh["means3D"]
-                g_sh = torch.empty((P, M, 3), dtype=torch.float32, device=means3D.device)
-                g = e["gathered"].view(-1, P + 1, 3)       # (world, P+1, 3), or (world, k, P+1, 3) from a view-batched render: world x k views
-                check(_lib.lib().d3ga_sh_grad_from_views(P, M, deg, g.shape[0], dptr(means3D), dptr(g), 3 * (P + 1),
-                                                         dptr(g[0, P]), 3 * (P + 1), self.scale, dptr(g_sh), stream_handle()),
-                      "d3ga_sh_grad_from_views")
-                mine["shs"] = g_sh
+                mine["shs"] = _sh_grad_from_factors(e["gathered"], sh["P"], sh["M"], sh["sh_degree"], sh["means3D"], self.scale)
             for k, v in mine.items():
                 out[k] = v if k not in out else out[k] + v
         return out

@@ -9,12 +9,10 @@ single-view backwards.
     CameraBatch(k, width, height)            k cameras in one static device buffer (graph-replayable: `set(batches)`)
     rasterize_gaussians_views(...)           -> (colors (k,3,H,W), radii (k,P), loss | None)
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from ._lib import RasterParams, check, dptr, require_cuda, stream_handle
+from ._lib import require_cuda
 from .cameras import Camera, crop_window
 from . import rasterizer as _R
 
@@ -79,15 +77,6 @@ class CameraBatch:
         return self
 
 
-def _scratch_views(P, W, H, k, cap, dev, fwd_only, windowed=False):
-    sizes = (ctypes.c_int64 * 3)()
-    if windowed:
-        check(_lib.lib().d3ga_raster_scratch_bytes_window(P, W, H, k, cap, int(fwd_only), sizes), "d3ga_raster_scratch_bytes_window")
-        return [torch.empty(int(n), dtype=torch.uint8, device=dev) for n in sizes]
-    check(_lib.lib().d3ga_raster_scratch_bytes_views(P, W, H, k, cap, int(fwd_only), sizes), "d3ga_raster_scratch_bytes_views")
-    return [torch.empty(int(n), dtype=torch.uint8, device=dev) for n in sizes]
-
-
 class _RasterizeViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cams, bg, sh_degree,
@@ -97,11 +86,7 @@ class _RasterizeViews(torch.autograd.Function):
         f32 = lambda t: _R._f32(t, dev)
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg = map(
             f32, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg))
-        if (sh is None) == (colors_precomp is None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if ((scales is None or rotations is None) and cov3Ds_precomp is None) or (
-                (scales is not None or rotations is not None) and cov3Ds_precomp is not None):
-            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        _R._check_exactly_one(sh, colors_precomp, scales, rotations, cov3Ds_precomp)
         k, W, H = cams.n_views, cams.image_width, cams.image_height
         windowed = getattr(cams, "windowed", False)
         if windowed and grad_sync is not None:
@@ -131,10 +116,8 @@ class _RasterizeViews(torch.autograd.Function):
             if tuple(colors2.shape) != (P, 3) or bg2.numel() != 3:
                 raise ValueError("rasterize_gaussians_views: colors2 is (P,3) and bg2 (3,), shared by the views")
         marker = _lib.CAMERA_SLOT_WINDOWED if windowed else 0.0         # camera slots: tangents (and windows) from the device rows
-        prm = RasterParams(P=P, M=M, sh_degree=int(sh_degree), W=W, H=H, tanfovx=marker, tanfovy=marker,
-                           scale_modifier=float(scale_modifier), antialiasing=int(bool(antialiasing)), prefiltered=0, debug=0,
-                           opacity_activation=_R._ACTIVATIONS[opacity_activation], forward_only=int(fwd_only), n_views=k,
-                           per_view_geometry=int(per_view), per_view_appearance=int(pva), per_view_background=int(pvb))
+        prm = _R._params(P, M, int(sh_degree), W, H, marker, marker, float(scale_modifier), bool(antialiasing), False, False,
+                         opacity_activation, fwd_only, k, per_view, pva, pvb)
         colors2_img = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev) if dual else None
         colors = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((k, P), dtype=torch.int32, device=dev)
@@ -144,58 +127,27 @@ class _RasterizeViews(torch.autograd.Function):
             if tuple(tgt.shape) != (k, 3, H, W):
                 raise ValueError(f"rasterize_gaussians_views: the targets must be ({k}, 3, {H}, {W}), got {tuple(tgt.shape)}")
             loss = torch.empty((), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        st, pp = stream_handle(), ctypes.byref(prm)
-        static = _R._policy["mode"] == "static"
-        cap = _R._policy["static"] if static else max(k * _R._hwm.get(dev.index, 0), k * (4 * P + 1024))
-        while True:
-            geom, binning, img = _scratch_views(P, W, H, k, cap, dev, fwd_only, windowed)
-            tm = _R.stage_timer
-            tm.stage("preprocess", lambda: check(L.d3ga_raster_preprocess(
-                pp, dptr(means3D), dptr(sh), dptr(colors_precomp), dptr(opacities), dptr(scales), dptr(rotations),
-                dptr(cov3Ds_precomp), dptr(cams.viewmatrices), dptr(cams.projmatrices), dptr(cams.campos), dptr(geom), dptr(binning),
-                cap, dptr(radii), st), "d3ga_raster_preprocess"))
-            tm.stage("bin_sort", lambda: check(L.d3ga_raster_bin_sort(pp, dptr(geom), dptr(binning), cap, st), "d3ga_raster_bin_sort"))
-            if tgt is not None and P > 0:
-                ws = torch.empty(4 * k * ((W + 15) // 16 + windowed) * ((H + 15) // 16 + windowed), dtype=torch.float32, device=dev)
-                tm.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd_l1(
-                    pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(colors), None, dptr(tgt), None, dptr(loss), dptr(ws), st),
-                    "d3ga_raster_composite_fwd_l1"))
-            elif dual and P > 0:
-                tm.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd2(
-                    pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), cap, dptr(img), dptr(colors), dptr(colors2_img),
-                    None, st), "d3ga_raster_composite_fwd2"))
-            else:
-                tm.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd(
-                    pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(colors), None, st), "d3ga_raster_composite_fwd"))
-                if tgt is not None:
-                    _R.l1_mean_forward(colors, tgt, None, loss, dev)
-                if dual:
-                    colors2_img.copy_(bg2.view(1, 3, 1, 1).expand_as(colors2_img))
-            _R._last[dev.index] = (binning, cap)
-            if _R._capture_log is not None:
-                _R._capture_log.append((binning, cap))
-            if static:
-                break
-            cnt = binning[:32].view(torch.int32)[:2].cpu().tolist()           # host sync (upstream: num_rendered)
-            D = cnt[0] & 0xFFFFFFFF
-            _R._hwm[dev.index] = max(_R._hwm.get(dev.index, 0), int(D * 1.25 / k) + 1024)      # the mark is per view
-            if not cnt[1]:
-                break
-            cap = k * _R._hwm[dev.index]
+        gauss = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        cam = (cams.viewmatrices, cams.projmatrices, cams.campos)
+        # nothing to blend (P == 0): every image is its background, the loss and the second image are formed from that
+        pair = (colors2, bg2, colors2_img) if (dual and P > 0) else None
+        l1 = (tgt, None, loss) if (tgt is not None and P > 0) else None
+        cap, geom, binning, img = _R._forward_with_capacity(P, k, dev, lambda cap: _R._launch_forward(
+            prm, cap, windowed, gauss, cam, bg, colors, radii, None, pair, l1))
+        if tgt is not None and l1 is None:
+            _R.l1_mean_forward(colors, tgt, None, loss, dev)
+        if dual and pair is None:
+            colors2_img.copy_(bg2.view(1, 3, 1, 1).expand_as(colors2_img))
         ctx.prm, ctx.cap, ctx.cams = prm, cap, cams
-        ctx.l1 = tgt is not None and P > 0
+        ctx.l1 = l1 is not None
         ctx.dual, ctx.per_view, ctx.pva = dual, per_view, pva
         # camera-sharded training (d3ga_amd/dist.py: ViewShardedGrads): every gradient that leaves this op is summed over the ranks
         # at this cut -- this rank's k views arrive already summed, their k SH factors travel in one all-gather
-        ctx.grad_sync = grad_sync if (grad_sync is not None and (grad_sync.world > 1 or getattr(grad_sync, "always", False)) and P > 0) else None
-        if ctx.grad_sync is not None:
-            if per_view:
-                raise ValueError("rasterize_gaussians_views: grad_sync needs view-independent geometry (k cameras of one pose); a batch of "
-                                 "frames is reduced at the parameters (dist.GradReducer)")
-            if hasattr(grad_sync, "verify_inputs"):
-                grad_sync.verify_inputs({"means3D": means3D, "opacities": opacities, "colors_precomp": colors_precomp, "shs": sh,
-                                         "cov3D_precomp": cov3Ds_precomp, "scales": scales, "rotations": rotations})
+        ctx.grad_sync = _R._admit_grad_sync(grad_sync, P)
+        if ctx.grad_sync is not None and per_view:
+            raise ValueError("rasterize_gaussians_views: grad_sync needs view-independent geometry (k cameras of one pose); a batch of "
+                             "frames is reduced at the parameters (dist.GradReducer)")
+        _R._verify_sync_inputs(ctx.grad_sync, means3D, opacities, colors_precomp, sh, cov3Ds_precomp, scales, rotations)
         ctx.save_for_backward(means3D, sh, scales, rotations, cov3Ds_precomp, bg, geom, binning, img,
                               colors if ctx.l1 else None, tgt if ctx.l1 else None, colors2, bg2)
         ctx.mark_non_differentiable(radii)
@@ -218,84 +170,20 @@ class _RasterizeViews(torch.autograd.Function):
         if grad_colors is None and g_loss is None:
             grad_colors = torch.zeros((k, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
         grad_colors = _R._f32(grad_colors, dev)
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        # (k P, 16) screen-space accumulator: under rasterizer.set_accumulator_policy("persistent") ONE zeroed buffer per size is kept
-        # and the per-Gaussian backward leaves it all zero again -- no 64 B x k P fill per backward
-        acc, self_clearing = _R._accumulator(k * P, dev)
-        from_sr = cov3Ds_precomp is None
-        sync, flat, factor = ctx.grad_sync, None, None
-        if sync is None:
-            gshape = (k, P) if ctx.per_view else (P,)                 # a batch of frames: geometry gradients per view
-            g_means3D = new(*gshape, 3)
-            g_opac = new(*ctx.opacities_shape) if ctx.pva else new(P, 1)        # per-view appearance: (k,P[,1]) and (k,P,3), per view
-            g_sh = new(P, prm.M, 3) if sh is not None else None
-            g_col = new(k, P, 3) if (sh is not None or ctx.pva) else new(P, 3)  # SH: the per-view factors of the rank-1 SH gradient (scratch)
-            g_cov = None if from_sr else new(*gshape, 6)
-            g_scales = new(*gshape, 3) if from_sr else None
-            g_rots = new(*gshape, 4) if from_sr else None
-        else:
-            # one planar buffer for the all-reduce (as rasterizer._RasterizeGaussians.backward lays it out); the SH gradient leaves
-            # as k factors of (P + 1, 3) -- row P carries the view's camera position -- for ONE all-gather of (k, P + 1, 3) per rank
-            widths = [3, 1] + ([3, 4] if from_sr else [6]) + ([3] if sh is None else [])
-            flat = new(P * sum(widths))
-            parts, off = [], 0
-            for w in widths:
-                parts.append(flat[off:off + P * w].view(P, w))
-                off += P * w
-            g_means3D, g_opac = parts[0], parts[1]
-            g_scales, g_rots = (parts[2], parts[3]) if from_sr else (None, None)
-            g_cov = None if from_sr else parts[2]
-            g_sh = None
-            if sh is None:
-                g_col = parts[-1]
-            else:
-                factor = new(k, P + 1, 3)
-                g_col = factor
-                p2 = RasterParams(**{f: getattr(prm, f) for f, _ in RasterParams._fields_})
-                p2.factor_rows = P + 1
-                prm = p2
-        if self_clearing != bool(prm.acc_self_clearing):
-            p3 = RasterParams(**{f: getattr(prm, f) for f, _ in RasterParams._fields_})      # (ctx.prm may be shared with a retained graph)
-            p3.acc_self_clearing = int(self_clearing)
-            prm = p3
-        L = _lib.lib()
-        st, pp = stream_handle(), ctypes.byref(prm)          # (prm: the block with factor_rows when the gradients are exchanged)
-        tm = _R.stage_timer
-        if not self_clearing:
-            acc.zero_()
-        if ctx.dual:
-            tm.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd2(
-                pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), ctx.cap, dptr(img), dptr(grad_colors),
-                dptr(grad_colors2), dptr(acc), st), "d3ga_raster_composite_bwd2"))
-        elif g_loss is not None:
-            tm.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd_l1(
-                pp, dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img), dptr(image), dptr(tgt), None, dptr(g_loss),
-                dptr(grad_colors), dptr(acc), st), "d3ga_raster_composite_bwd_l1"))
-        else:
-            tm.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd(
-                pp, dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img), dptr(grad_colors), dptr(acc), st),
-                "d3ga_raster_composite_bwd"))
-        tm.stage("preprocess_bwd", lambda: check(L.d3ga_raster_preprocess_bwd(
-            pp, dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp), dptr(cams.viewmatrices),
-            dptr(cams.projmatrices), dptr(cams.campos), dptr(geom), dptr(acc), dptr(g_means3D), None, dptr(g_opac),
-            dptr(g_sh if sync is None else None), dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), st), "d3ga_raster_preprocess_bwd"))
+        has_sh, from_sr, sync = sh is not None, cov3Ds_precomp is None, ctx.grad_sync
+        geo = (k, P) if ctx.per_view else (P,)                 # a batch of frames: geometry gradients per view
+        # per-view appearance: (k,P[,1]) and (k,P,3), per view; SH: the per-view factors of the rank-1 SH gradient (scratch)
+        g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm = _R._grad_buffers(
+            prm, has_sh, from_sr, dev, exchanged=sync is not None, geo=geo, opac=ctx.opacities_shape if ctx.pva else (P, 1),
+            col=(k, P, 3) if (has_sh or ctx.pva) else (P, 3), lead=(k,))
+        _R._launch_backward(prm, ctx.cap, (means3D, sh, scales, rotations, cov3Ds_precomp), (cams.viewmatrices, cams.projmatrices, cams.campos),
+                            bg, geom, binning, img, grad_colors, (g_means3D, None, g_opac, g_sh, g_col, g_cov, g_scales, g_rots),
+                            (colors2, bg2, grad_colors2) if ctx.dual else None, None,
+                            (image, tgt, None, g_loss) if g_loss is not None else None)
         if sync is not None:
-            if factor is not None:
-                factor[:, P].copy_(cams.campos[:, :3])
-            if getattr(sync, "deferred", False):          # two-graph step (graph.CapturedCutStep): the collectives run between the graphs
-                by_name = {"means3D": g_means3D, "opacities": g_opac}
-                by_name.update({"scales": g_scales, "rotations": g_rots} if from_sr else {"cov3D_precomp": g_cov})
-                if sh is None:
-                    by_name["colors_precomp"] = g_col
-                sync.park(flat, factor, by_name, None if factor is None else {"P": P, "M": prm.M, "sh_degree": prm.sh_degree, "means3D": means3D})
+            parked, g_sh = _R._exchange_gradients(sync, prm, cut, cams.campos, means3D)
+            if parked:
                 return (None,) * 17
-            gathered = sync.exchange(flat, factor)        # flat: averaged over the ranks in place; gathered: (world, k, P + 1, 3)
-            if factor is not None:
-                g_sh = new(P, prm.M, 3)
-                g = gathered.view(-1, P + 1, 3)
-                check(L.d3ga_sh_grad_from_views(P, prm.M, prm.sh_degree, g.shape[0], dptr(means3D), dptr(g), 3 * (P + 1), dptr(g[0, P]),
-                                                3 * (P + 1), sync.scale, dptr(g_sh), stream_handle()), "d3ga_sh_grad_from_views")
-                g_col = None
         return (g_means3D, g_sh, g_col if sh is None else None, g_opac, g_scales, g_rots, g_cov,
                 None, None, None, None, None, None, None, None, None, None)
 

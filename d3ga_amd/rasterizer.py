@@ -52,11 +52,38 @@ _capture_log = None  # while graph.CapturedStep / CapturedCutStep capture: list 
 
 def set_capacity_policy(mode, capacity=0):
     """"auto": read the duplicate count back after every forward and retry on overflow (default).
-    "static": use `capacity` duplicates, never synchronise; check `last_counters()["overflow"]` yourself."""
+    "static": use `capacity` duplicates, never synchronise; check `last_counters()["overflow"]` yourself.  A view-batched
+    render (raster_views) bins its k views into ONE list, so a static capacity counts the duplicates of all k views together."""
     if mode not in ("auto", "static"):
         raise ValueError(mode)
     _policy["mode"] = mode
     _policy["static"] = int(capacity)
+
+
+def _record_forward(dev, binning, cap):
+    _last[dev.index] = (binning, cap)
+    if _capture_log is not None:
+        _capture_log.append((binning, cap))
+
+
+def _forward_with_capacity(P, k, dev, launch):
+    """The capacity policy around one forward of k views (k = 1: the single-view operator).  launch(cap) -> (geom, binning, img)
+    enqueues the forward with room for `cap` duplicates; "auto" reads the counter block back (the only host sync, upstream:
+    num_rendered), raises the per-view high-water mark and launches again when the lists overflowed.  -> (cap, geom, binning, img)"""
+    static = _policy["mode"] == "static"
+    cap = _policy["static"] if static else k * max(_hwm.get(dev.index, 0), 4 * P + 1024)
+    while True:
+        geom, binning, img = launch(cap)
+        _record_forward(dev, binning, cap)
+        if static:
+            break
+        cnt = binning[:32].view(torch.int32)[:2].cpu().tolist()
+        D = cnt[0] & 0xFFFFFFFF
+        _hwm[dev.index] = max(_hwm.get(dev.index, 0), int(D * 1.25 / k) + 1024)      # the mark is per view
+        if not cnt[1]:
+            break
+        cap = k * _hwm[dev.index]
+    return cap, geom, binning, img
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -167,30 +194,61 @@ stage_timer = StageTimer()
 
 
 _scratch_sizes = {}
-_prm_cache = {}          # parameter blocks by value (never mutated: the backward copies one when it needs another acc_self_clearing)
+_prm_cache = {}          # parameter blocks by value (never mutated: _prm_variant copies one when a field has to differ)
 
 
-def _scratch(P, W, H, cap, device, forward_only=False, binning=True, windowed=False):
-    """(geom, binning, img) byte tensors.  forward_only: the img buffer without the per-block lists of the backward
-    (128 B per duplicate of capacity -- several hundred MB per render at a few million duplicates); binning=False: None
-    for the binning buffer (a geometry-cache hit shares the first pass's).  windowed: a W x H window of a windowed camera slot
-    (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED -- the window's tile grid and table)."""
-    key = (P, W, H, cap, bool(forward_only), bool(windowed))
+def _scratch(P, W, H, k, cap, device, forward_only, windowed, binning=True):
+    """(geom, binning, img) byte tensors for k views (k = 1: the single-view operator).  forward_only: the img buffer without
+    the per-block lists of the backward (128 B per duplicate of capacity -- several hundred MB per render at a few million
+    duplicates); binning=False: None for the binning buffer (a geometry-cache hit shares the first pass's).  windowed: W x H
+    windows of windowed camera slots (include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED -- the window's tile grid and table)."""
+    key = (P, W, H, k, cap, bool(forward_only), bool(windowed))
     sz = _scratch_sizes.get(key)
-    if sz is None:                                   # (two ctypes calls per render otherwise: the sizes of a training loop never change)
+    if sz is None:                                   # (a ctypes call per render otherwise: the sizes of a training loop never change)
         sizes = (ctypes.c_int64 * 3)()
-        L = _lib.lib()
-        if windowed:
-            check(L.d3ga_raster_scratch_bytes_window(P, W, H, 1, cap, int(bool(forward_only)), sizes), "d3ga_raster_scratch_bytes_window")
-            img_bytes = int(sizes[2])
-        else:
-            check(L.d3ga_raster_scratch_bytes(P, W, H, cap, sizes), "d3ga_raster_scratch_bytes")
-            img_bytes = int(L.d3ga_raster_img_bytes(W, H, cap, 1)) if forward_only else int(sizes[2])
+        name = "d3ga_raster_scratch_bytes_window" if windowed else "d3ga_raster_scratch_bytes_views"
+        check(getattr(_lib.lib(), name)(P, W, H, k, cap, int(bool(forward_only)), sizes), name)
         if len(_scratch_sizes) > 64:
             _scratch_sizes.clear()
-        sz = _scratch_sizes[key] = (int(sizes[0]), int(sizes[1]), img_bytes)
+        sz = _scratch_sizes[key] = tuple(int(n) for n in sizes)
     new = lambda n: torch.empty(n, dtype=torch.uint8, device=device)
     return [new(sz[0]), new(sz[1]) if binning else None, new(sz[2])]
+
+
+def _params(P, M, sh_degree, W, H, tanfovx, tanfovy, scale_modifier, antialiasing, prefiltered, debug, opacity_activation,
+            forward_only, n_views=0, per_view_geometry=False, per_view_appearance=False, per_view_background=False):
+    """The parameter block with these field values, built once per distinct value: the block of a training loop repeats, and
+    building the ctypes structure costs ~6 us of an ~80 us host-bound render.  Shared (a retained graph, this cache): never
+    written to -- `_prm_variant` gives the block that differs in a field."""
+    key = (P, M, sh_degree, W, H, tanfovx, tanfovy, scale_modifier, antialiasing, prefiltered, debug, opacity_activation,
+           forward_only, n_views, per_view_geometry, per_view_appearance, per_view_background)
+    prm = _prm_cache.get(key)
+    if prm is None:
+        if len(_prm_cache) > 64:
+            _prm_cache.clear()
+        prm = _prm_cache[key] = RasterParams(
+            P=P, M=M, sh_degree=sh_degree, W=W, H=H, tanfovx=tanfovx, tanfovy=tanfovy, scale_modifier=scale_modifier,
+            antialiasing=int(antialiasing), prefiltered=int(prefiltered), debug=int(debug),
+            opacity_activation=_ACTIVATIONS[opacity_activation], forward_only=int(forward_only), n_views=n_views,
+            per_view_geometry=int(per_view_geometry), per_view_appearance=int(per_view_appearance),
+            per_view_background=int(per_view_background))
+        prm.cache_key = key          # (a Python attribute on the ctypes instance, not a field of the C structure: _prm_variant's key)
+    return prm
+
+
+def _prm_variant(prm, **fields):
+    """`prm` with `fields` set to other values -- a block of its own, cached like the one it was copied from (under that
+    one's key extended by the fields, so a variant of a variant nests)."""
+    key = (prm.cache_key, tuple(fields.items()))
+    p2 = _prm_cache.get(key)
+    if p2 is None:
+        if len(_prm_cache) > 64:
+            _prm_cache.clear()
+        p2 = _prm_cache[key] = RasterParams(**{f: getattr(prm, f) for f, _ in RasterParams._fields_})
+        for f, value in fields.items():
+            setattr(p2, f, value)
+        p2.cache_key = key
+    return p2
 
 
 def _f32(t, device):
@@ -199,6 +257,189 @@ def _f32(t, device):
     if t.dtype != torch.float32 or t.device != device:
         t = t.to(device=device, dtype=torch.float32)
     return t if t.is_contiguous() else t.contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the launches of one render of k views (k = 1: the single-view operator); shared with raster_views
+# ------------------------------------------------------------------------------------------------------------
+# gauss: (means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp); cam: (view matrices, full projections,
+# camera rows) -- the tensors of a GaussianRasterizationSettings or the (k, .) blocks of a raster_views.CameraBatch.
+def _views_of(prm):
+    return max(prm.n_views, 1)
+
+
+def _composite_forward(prm, cap, windowed, bg, geom, binning, img, color, invdepth, pair, l1):
+    """The compositing stage: `pair` = (colors2, bg2, color2) blends a second image with the same alphas, `l1` = (target,
+    target cell, loss) forms mean |color - target| while the colours are in registers, else the plain kernel."""
+    L, st, pp = _lib.lib(), stream_handle(), ctypes.byref(prm)
+    if pair is not None:
+        colors2, bg2, color2 = pair
+        stage_timer.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd2(
+            pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), cap, dptr(img), dptr(color), dptr(color2),
+            dptr(invdepth), st), "d3ga_raster_composite_fwd2"))
+    elif l1 is not None:
+        target, cell, loss = l1
+        # one partial sum per quadrant of every tile, then one small sum
+        ws = torch.empty(4 * _views_of(prm) * ((prm.W + 15) // 16 + windowed) * ((prm.H + 15) // 16 + windowed),
+                         dtype=torch.float32, device=color.device)
+        stage_timer.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd_l1(
+            pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(color), dptr(invdepth),
+            dptr(None if cell is not None else target), dptr(cell), dptr(loss), dptr(ws), st), "d3ga_raster_composite_fwd_l1"))
+    else:
+        stage_timer.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd(
+            pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(color), dptr(invdepth), st), "d3ga_raster_composite_fwd"))
+
+
+def _launch_forward(prm, cap, windowed, gauss, cam, bg, color, radii, invdepth, pair=None, l1=None):
+    """preprocess -> bin + sort -> composite into fresh scratch with room for `cap` duplicates.  -> (geom, binning, img)"""
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = gauss
+    view, proj, campos = cam
+    k = _views_of(prm)
+    geom, binning, img = _scratch(prm.P, prm.W, prm.H, k, cap, color.device, prm.forward_only, windowed)
+    L = _lib.lib()
+    if stage_timer.enabled or k > 1 or pair is not None or l1 is not None:
+        st, pp = stream_handle(), ctypes.byref(prm)
+        stage_timer.stage("preprocess", lambda: check(L.d3ga_raster_preprocess(
+            pp, dptr(means3D), dptr(sh), dptr(colors_precomp), dptr(opacities), dptr(scales), dptr(rotations),
+            dptr(cov3Ds_precomp), dptr(view), dptr(proj), dptr(campos), dptr(geom), dptr(binning), cap,
+            dptr(radii), st), "d3ga_raster_preprocess"))
+        stage_timer.stage("bin_sort", lambda: check(L.d3ga_raster_bin_sort(
+            pp, dptr(geom), dptr(binning), cap, st), "d3ga_raster_bin_sort"))
+        _composite_forward(prm, cap, windowed, bg, geom, binning, img, color, invdepth, pair, l1)
+    else:
+        # one ctypes call instead of three: the eager step is host-bound
+        check(L.d3ga_raster_forward(ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(colors_precomp),
+                                    dptr(opacities), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
+                                    dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning),
+                                    dptr(img), cap, dptr(color), dptr(radii), dptr(invdepth), stream_handle()),
+              "d3ga_raster_forward")
+    return geom, binning, img
+
+
+def _grad_buffers(prm, has_sh, from_sr, dev, exchanged, geo, opac, col, lead):
+    """The gradients the per-Gaussian backward writes.  Plain: dL/dmeans3D, dL/dcov3D | dL/dscales, dL/drots of shape
+    (*geo, .), dL/dopacity `opac`, dL/dcolour `col` (None: no such buffer).  `exchanged` (view-sharded training, dist.py:
+    ViewShardedGrads): every gradient that leaves the op is summed over the ranks at this cut -- ONE planar buffer `flat` for
+    the all-reduce and, on the SH path, the (P + 1, 3) factor of every view's rank-1 SH gradient (row P: the view's camera
+    position) for ONE all-gather of (*lead, P + 1, 3) per rank.
+    -> (g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm); cut: None, or what `_exchange_gradients` moves --
+    (flat, factor, rasterizer input name -> its gradient, a view of `flat`)."""
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    P, cut = prm.P, None
+    if not exchanged:
+        g_means3D, g_opac = new(*geo, 3), new(*opac)
+        g_sh = new(P, prm.M, 3) if has_sh else None
+        g_col = None if col is None else new(*col)
+        g_cov = None if from_sr else new(*geo, 6)
+        g_scales = new(*geo, 3) if from_sr else None
+        g_rots = new(*geo, 4) if from_sr else None
+    else:
+        widths = [3, 1] + ([3, 4] if from_sr else [6]) + ([] if has_sh else [3])
+        flat = new(P * sum(widths))
+        parts, off = [], 0
+        for w in widths:
+            parts.append(flat[off:off + P * w].view(P, w))
+            off += P * w
+        g_means3D, g_opac = parts[0], parts[1]
+        g_scales, g_rots = (parts[2], parts[3]) if from_sr else (None, None)
+        g_cov = None if from_sr else parts[2]
+        g_sh = factor = None
+        by_name = {"means3D": g_means3D, "opacities": g_opac}
+        by_name.update({"scales": g_scales, "rotations": g_rots} if from_sr else {"cov3D_precomp": g_cov})
+        if not has_sh:
+            g_col = by_name["colors_precomp"] = parts[-1]
+        else:
+            # the kernel writes a view's dL/dcolour into the first P rows of its factor: the factor's own address
+            g_col = factor = new(*lead, P + 1, 3)
+            if _views_of(prm) > 1:                 # rows between the views' factors (include/d3ga.h: meaningful for n_views > 1)
+                prm = _prm_variant(prm, factor_rows=P + 1)
+        cut = (flat, factor, by_name)
+    return g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm
+
+
+def _launch_backward(prm, cap, gauss, cam, bg, geom, binning, img, grad_color, grads, pair=None, g_invd=None, l1=None):
+    """composite_bwd -> preprocess_bwd.  gauss: (means3D, sh, scales, rotations, cov3D_precomp); grads: (g_means3D, g_means2D,
+    g_opac, g_sh, g_col, g_cov, g_scales, g_rots); pair = (colors2, bg2, grad_color2); g_invd: the gradient of the inverse-depth
+    image; l1 = (image, target, target cell, g_loss): the gradient of the fused L1 loss, formed per pixel inside the kernel."""
+    means3D, sh, scales, rotations, cov3Ds_precomp = gauss
+    view, proj, campos = cam
+    g_means3D, g_means2D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots = grads
+    k = _views_of(prm)
+    # (k P, 16) screen-space accumulator: under set_accumulator_policy("persistent") ONE zeroed buffer per size is kept and the
+    # per-Gaussian backward leaves it all zero again -- no 64 B x k P fill per backward
+    acc, self_clearing = _accumulator(k * prm.P, means3D.device)
+    if self_clearing != bool(prm.acc_self_clearing):
+        prm = _prm_variant(prm, acc_self_clearing=int(self_clearing))
+    L = _lib.lib()
+    if stage_timer.enabled or k > 1 or pair is not None or g_invd is not None:
+        st, pp = stream_handle(), ctypes.byref(prm)
+        if not self_clearing:
+            acc.zero_()
+        if pair is not None:
+            colors2, bg2, grad_color2 = pair
+            stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd2(
+                pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), cap, dptr(img), dptr(grad_color),
+                dptr(grad_color2), dptr(acc), st), "d3ga_raster_composite_bwd2"))
+        elif g_invd is not None:
+            stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd_depth(
+                pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(grad_color), dptr(g_invd), dptr(acc), st),
+                "d3ga_raster_composite_bwd_depth"))
+        elif l1 is not None:
+            image, target, cell, g_loss = l1
+            stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd_l1(
+                pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(image), dptr(target), dptr(cell),
+                dptr(g_loss), dptr(grad_color), dptr(acc), st), "d3ga_raster_composite_bwd_l1"))
+        else:
+            stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd(
+                pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(grad_color), dptr(acc), st),
+                "d3ga_raster_composite_bwd"))
+        stage_timer.stage("preprocess_bwd", lambda: check(L.d3ga_raster_preprocess_bwd(
+            pp, dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp), dptr(view), dptr(proj),
+            dptr(campos), dptr(geom), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh),
+            dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), st), "d3ga_raster_preprocess_bwd"))
+    elif l1 is not None:
+        image, target, cell, g_loss = l1
+        check(L.d3ga_raster_backward_l1(
+            ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
+            dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), cap, dptr(img),
+            dptr(image), dptr(target), dptr(cell), dptr(g_loss), dptr(grad_color), dptr(acc), dptr(g_means3D),
+            dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots),
+            stream_handle()), "d3ga_raster_backward_l1")
+    else:
+        check(L.d3ga_raster_backward(
+            ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
+            dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), cap, dptr(img),
+            dptr(grad_color), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col),
+            dptr(g_cov), dptr(g_scales), dptr(g_rots), stream_handle()), "d3ga_raster_backward")
+
+
+def _sh_grad_from_factors(gathered, P, M, sh_degree, means3D, scale):
+    """dL/dsh (P, M, 3) = scale * sum over the views of Y(dir_v) (x) g_v, from the gathered (.., P + 1, 3) factors of all views of
+    all ranks -- (world, P + 1, 3), or (world, k, P + 1, 3) from view-batched renders; row P is the view's camera position."""
+    g_sh = torch.empty((P, M, 3), dtype=torch.float32, device=means3D.device)
+    g = gathered.view(-1, P + 1, 3)
+    check(_lib.lib().d3ga_sh_grad_from_views(P, M, sh_degree, g.shape[0], dptr(means3D), dptr(g), 3 * (P + 1), dptr(g[0, P]),
+                                             3 * (P + 1), scale, dptr(g_sh), stream_handle()), "d3ga_sh_grad_from_views")
+    return g_sh
+
+
+def _exchange_gradients(sync, prm, cut, campos, means3D):
+    """The tail of a backward whose gradients are exchanged (cut: from `_grad_buffers`): the views' camera positions into row P
+    of their factors, then the collectives.  -> (parked, g_sh): parked -- the
+    two-graph step (graph.CapturedCutStep) runs the collectives between the graphs, on these buffers, and the gradients come
+    back REDUCED through it (returning them from the backward as well would leave the unreduced copy on the detached leaves,
+    where the step adds the other loss terms' gradients); else `flat` is summed (averaged) in place and g_sh rebuilt from the
+    gathered factors (None without SH)."""
+    P = prm.P
+    flat, factor, by_name = cut
+    if factor is not None:
+        factor.view(-1, P + 1, 3)[:, P].copy_(campos.reshape(_views_of(prm), -1)[:, :3])
+    if getattr(sync, "deferred", False):
+        sync.park(flat, factor, by_name,
+                  None if factor is None else {"P": P, "M": prm.M, "sh_degree": prm.sh_degree, "means3D": means3D})
+        return True, None
+    gathered = sync.exchange(flat, factor)
+    return False, None if factor is None else _sh_grad_from_factors(gathered, P, prm.M, prm.sh_degree, means3D, sync.scale)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -258,6 +499,30 @@ def _empty_to_none(t):
     return None if (t is None or t.numel() == 0) else t
 
 
+def _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """upstream's two argument checks, with its texts"""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
+            (scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+
+
+def _admit_grad_sync(grad_sync, P):
+    """-> `grad_sync` when the backward exchanges its gradients through it (more than one rank, or forced: `always`; and something
+    to exchange), else None."""
+    if grad_sync is None or P == 0 or not (grad_sync.world > 1 or getattr(grad_sync, "always", False)):
+        return None
+    return grad_sync
+
+
+def _verify_sync_inputs(sync, means3D, opacities, colors_precomp, sh, cov3Ds_precomp, scales, rotations):
+    """the cut exchange is only valid for view-independent inputs (dist.ViewShardedGrads): checked on the first call(s)"""
+    if sync is not None and hasattr(sync, "verify_inputs"):
+        sync.verify_inputs({"means3D": means3D, "opacities": opacities, "colors_precomp": colors_precomp,
+                            "shs": sh, "cov3D_precomp": cov3Ds_precomp, "scales": scales, "rotations": rotations})
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -290,18 +555,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                                  "camera slot (tanfovx = tanfovy = 0 with a 5-float campos: cameras.CameraSlot) reads them from the device")
         # no input requires a gradient (inference, torch.no_grad): the forward skips the per-block lists of the backward
         fwd_only = not any(ctx.needs_input_grad[:8])
-        # (the parameter block of a training loop repeats: building the ctypes structure costs ~6 us of an ~80 us host-bound render)
-        pkey = (P, M, int(s.sh_degree), W, H, tfx, tfy, float(s.scale_modifier), bool(s.antialiasing), bool(s.prefiltered), bool(s.debug),
-                opacity_activation, fwd_only)
-        prm = _prm_cache.get(pkey)
-        if prm is None:
-            if len(_prm_cache) > 64:
-                _prm_cache.clear()
-            prm = _prm_cache[pkey] = RasterParams(P=P, M=M, sh_degree=int(s.sh_degree), W=W, H=H, tanfovx=tfx,
-                                                  tanfovy=tfy, scale_modifier=float(s.scale_modifier),
-                                                  antialiasing=int(bool(s.antialiasing)), prefiltered=int(bool(s.prefiltered)),
-                                                  debug=int(bool(s.debug)), opacity_activation=_ACTIVATIONS[opacity_activation],
-                                                  forward_only=int(fwd_only))
+        prm = _params(P, M, int(s.sh_degree), W, H, tfx, tfy, float(s.scale_modifier), bool(s.antialiasing), bool(s.prefiltered),
+                      bool(s.debug), opacity_activation, fwd_only)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         # fused L1 image loss (rasterize_gaussians_l1): the loss VALUE is formed by the compositing forward while the colours
         # are in registers (d3ga_raster_composite_fwd_l1: one partial per quadrant, then one small sum), its gradient inside
@@ -314,88 +569,46 @@ class _RasterizeGaussians(torch.autograd.Function):
             if tuple(l1_t.shape) != (3, H, W):
                 raise ValueError(f"rasterize_gaussians_l1: the target must be (3, {H}, {W}), got {tuple(l1_t.shape)}")
             loss = torch.empty((), dtype=torch.float32, device=dev)
-        l1_in_fwd = l1_target is not None and P > 0 and colors2 is None and _l1_policy["fused_value"]
-
-        def composite_fwd_single(L, pp, geom, binning, cap, img, st):
-            if l1_in_fwd:
-                ws = torch.empty(4 * ((W + 15) // 16 + windowed) * ((H + 15) // 16 + windowed), dtype=torch.float32, device=dev)
-                check(L.d3ga_raster_composite_fwd_l1(pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(color),
-                                                     dptr(invdepth), dptr(None if l1_cell is not None else l1_t), dptr(l1_cell),
-                                                     dptr(loss), dptr(ws), st), "d3ga_raster_composite_fwd_l1")
-            else:
-                check(L.d3ga_raster_composite_fwd(pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(color),
-                                                  dptr(invdepth), st), "d3ga_raster_composite_fwd")
+        # the loss value from the compositing forward; else (P == 0: the image is its background, or D3GA_L1_VALUE=separate) from
+        # its own pass over the finished image
+        l1 = (l1_t, l1_cell, loss) if (l1_target is not None and P > 0 and colors2 is None and _l1_policy["fused_value"]) else None
         # the inverse-depth image of branch dr_aa: on request only (renderer.render* use the colour alone, renderer.py:141)
         invdepth = torch.empty((1, H, W), dtype=torch.float32, device=dev) if want_invdepth else None
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        L = _lib.lib()
-        static = _policy["mode"] == "static"
-        cap = _policy["static"] if static else max(_hwm.get(dev.index, 0), 4 * P + 1024)
+        gauss = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        cam = (view, proj, campos)
         geo_inputs = (means3D, opacities, scales, rotations, cov3Ds_precomp, view, proj)
         color2 = torch.empty((3, H, W), dtype=torch.float32, device=dev) if dual else None
+        pair = (colors2, bg2, color2) if dual else None
         use_cache = _reuse["enabled"] and P > 0 and not dual and not windowed and not torch.cuda.is_current_stream_capturing()
-        key = _geometry_key(prm, ("static", cap) if static else "auto", geo_inputs) if use_cache else None
-        hit = _geom_cache.get(dev.index) if use_cache else None
+        key = hit = None
+        if use_cache:
+            key = _geometry_key(prm, ("static", _policy["static"]) if _policy["mode"] == "static" else "auto", geo_inputs)
+            hit = _geom_cache.get(dev.index)
         if hit is not None and hit["key"] == key:
             cap, binning, radii = hit["cap"], hit["binning"], hit["radii"]
-            geom, _unused, img = _scratch(P, W, H, cap, dev, fwd_only, binning=False)     # img carries the per-block lists: sized by cap
-            st, pp = stream_handle(), ctypes.byref(prm)
+            geom, _unused, img = _scratch(P, W, H, 1, cap, dev, fwd_only, False, binning=False)     # img carries the per-block lists: sized by cap
+            L, st, pp = _lib.lib(), stream_handle(), ctypes.byref(prm)
             stage_timer.stage("recolor", lambda: check(L.d3ga_raster_recolor(
                 pp, dptr(means3D), dptr(sh), dptr(colors_precomp), dptr(campos), dptr(hit["geom"]), dptr(geom), st),
                 "d3ga_raster_recolor"))
-            stage_timer.stage("composite_fwd", lambda: composite_fwd_single(L, pp, geom, binning, cap, img, st))
-            _last[dev.index] = (binning, cap)
-            if _capture_log is not None:
-                _capture_log.append((binning, cap))
-        while hit is None or hit["key"] != key:
-            geom, binning, img = _scratch(P, W, H, cap, dev, fwd_only, windowed=windowed)
-            if stage_timer.enabled or dual or l1_in_fwd:
-                st, pp = stream_handle(), ctypes.byref(prm)
-                stage_timer.stage("preprocess", lambda: check(L.d3ga_raster_preprocess(
-                    pp, dptr(means3D), dptr(sh), dptr(colors_precomp), dptr(opacities), dptr(scales), dptr(rotations),
-                    dptr(cov3Ds_precomp), dptr(view), dptr(proj), dptr(campos), dptr(geom), dptr(binning), cap,
-                    dptr(radii), st), "d3ga_raster_preprocess"))
-                stage_timer.stage("bin_sort", lambda: check(L.d3ga_raster_bin_sort(
-                    pp, dptr(geom), dptr(binning), cap, st), "d3ga_raster_bin_sort"))
-                if dual:
-                    stage_timer.stage("composite_fwd", lambda: check(L.d3ga_raster_composite_fwd2(
-                        pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), cap, dptr(img), dptr(color),
-                        dptr(color2), dptr(invdepth), st), "d3ga_raster_composite_fwd2"))
-                else:
-                    stage_timer.stage("composite_fwd", lambda: composite_fwd_single(L, pp, geom, binning, cap, img, st))
-            else:
-                check(L.d3ga_raster_forward(ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(colors_precomp),
-                                            dptr(opacities), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
-                                            dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning),
-                                            dptr(img), cap, dptr(color), dptr(radii), dptr(invdepth), stream_handle()),
-                      "d3ga_raster_forward")
-            _last[dev.index] = (binning, cap)
-            if _capture_log is not None:
-                _capture_log.append((binning, cap))
-            if static:
-                break
-            cnt = binning[:32].view(torch.int32)[:2].cpu().tolist()       # host sync (upstream: num_rendered)
-            D = cnt[0] & 0xFFFFFFFF
-            _hwm[dev.index] = max(_hwm.get(dev.index, 0), int(D * 1.25) + 1024)
-            if not cnt[1]:
-                break
-            cap = _hwm[dev.index]
-        if use_cache and (hit is None or hit["key"] != key):
-            _geom_cache[dev.index] = {"key": key, "geom": geom, "binning": binning, "cap": cap, "radii": radii,
-                                      # detached aliases: they pin the storage without keeping an autograd graph alive
-                                      "pins": tuple(None if t is None else t.detach() for t in geo_inputs)}
+            _composite_forward(prm, cap, windowed, bg, geom, binning, img, color, invdepth, None, l1)
+            _record_forward(dev, binning, cap)
+        else:
+            cap, geom, binning, img = _forward_with_capacity(P, 1, dev, lambda cap: _launch_forward(
+                prm, cap, windowed, gauss, cam, bg, color, radii, invdepth, pair, l1))
+            if use_cache:
+                _geom_cache[dev.index] = {"key": key, "geom": geom, "binning": binning, "cap": cap, "radii": radii,
+                                          # detached aliases: they pin the storage without keeping an autograd graph alive
+                                          "pins": tuple(None if t is None else t.detach() for t in geo_inputs)}
         ctx.prm = prm
-        ctx.pkey = pkey
         ctx.cap = cap
         ctx.has_means2D = means2D is not None
-        ctx.grad_sync = grad_sync if (grad_sync is not None and (grad_sync.world > 1 or getattr(grad_sync, "always", False)) and P > 0) else None
-        if ctx.grad_sync is not None and hasattr(grad_sync, "verify_inputs"):
-            # the cut exchange is only valid for view-independent inputs (dist.ViewShardedGrads): checked on the first call(s)
-            grad_sync.verify_inputs({"means3D": means3D, "opacities": opacities, "colors_precomp": colors_precomp,
-                                     "shs": sh, "cov3D_precomp": cov3Ds_precomp, "scales": scales, "rotations": rotations})
+        ctx.grad_sync = _admit_grad_sync(grad_sync, P)
+        _verify_sync_inputs(ctx.grad_sync, means3D, opacities, colors_precomp, sh, cov3Ds_precomp, scales, rotations)
         ctx.dual = dual
         ctx.l1 = l1_target is not None and P > 0 and not dual
-        if l1_target is not None and not l1_in_fwd:      # P == 0 (the image is its background) or D3GA_L1_VALUE=separate
+        if l1_target is not None and l1 is None:
             l1_mean_forward(color, l1_t, l1_cell, loss, dev)
         _last_img[dev.index] = (img, W, H, geom, P)
         ctx.save_for_backward(means3D, sh, scales, rotations, cov3Ds_precomp, view, proj, campos, bg, geom, binning, img,
@@ -433,108 +646,19 @@ class _RasterizeGaussians(torch.autograd.Function):
         grad_color = _f32(grad_color, dev)
         if dual:
             grad_color2 = (torch.zeros_like(grad_color) if grad_color2 is None else _f32(grad_color2, dev))
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        acc, self_clearing = _accumulator(P, dev)
-        if self_clearing != bool(prm.acc_self_clearing):
-            # (ctx.prm is shared -- a retained graph, the cache of parameter blocks: the variant is a block of its own, cached too)
-            key2 = (ctx.pkey, self_clearing)
-            p2 = _prm_cache.get(key2)
-            if p2 is None:
-                p2 = RasterParams(**{f: getattr(prm, f) for f, _ in RasterParams._fields_})
-                p2.acc_self_clearing = int(self_clearing)
-                _prm_cache[key2] = p2
-            prm = p2
-        from_sr = cov3Ds_precomp is None
-        sync = ctx.grad_sync
-        if sync is None:
-            g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(P, 1)
-            g_sh = new(P, prm.M, 3) if sh is not None else None
-            g_col = new(P, 3) if sh is None else None
-            g_cov = None if from_sr else new(P, 6)
-            g_scales = new(P, 3) if from_sr else None
-            g_rots = new(P, 4) if from_sr else None
-        else:
-            # view-sharded training: every gradient that leaves this op is summed over the ranks HERE, at the narrowest
-            # cut of the graph (d3ga_amd/dist.py:ViewShardedGrads) -- one planar buffer for the all-reduce, and for the SH
-            # path the (P,3) factor of the rank-1 SH gradient (+ this view's camera position as row P) for the all-gather
-            g_means2D = new(P, 3)
-            widths = [3, 1] + ([3, 4] if from_sr else [6]) + ([3] if sh is None else [])
-            flat = new(P * sum(widths))
-            parts, off = [], 0
-            for w in widths:
-                parts.append(flat[off:off + P * w].view(P, w))
-                off += P * w
-            g_means3D, g_opac = parts[0], parts[1]
-            g_scales, g_rots = (parts[2], parts[3]) if from_sr else (None, None)
-            g_cov = None if from_sr else parts[2]
-            g_sh = None
-            if sh is None:
-                g_col, factor = parts[-1], None
-            else:
-                factor = new(P + 1, 3)
-                g_col = factor[:P]
-        L = _lib.lib()
-        if stage_timer.enabled or dual or g_invd is not None:
-            st, pp = stream_handle(), ctypes.byref(prm)
-            if not self_clearing:
-                acc.zero_()
-            if dual:
-                stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd2(
-                    pp, dptr(bg), dptr(bg2), dptr(geom), dptr(colors2), dptr(binning), ctx.cap, dptr(img), dptr(grad_color),
-                    dptr(grad_color2), dptr(acc), st), "d3ga_raster_composite_bwd2"))
-            elif g_invd is not None:
-                stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd_depth(
-                    pp, dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img), dptr(grad_color), dptr(g_invd), dptr(acc), st),
-                    "d3ga_raster_composite_bwd_depth"))
-            elif g_loss is not None:
-                stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd_l1(
-                    pp, dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img), dptr(image), dptr(l1_t), dptr(l1_cell),
-                    dptr(g_loss), dptr(grad_color), dptr(acc), st), "d3ga_raster_composite_bwd_l1"))
-            else:
-                stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd(
-                    pp, dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img), dptr(grad_color), dptr(acc), st),
-                    "d3ga_raster_composite_bwd"))
-            stage_timer.stage("preprocess_bwd", lambda: check(L.d3ga_raster_preprocess_bwd(
-                pp, dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp), dptr(view), dptr(proj),
-                dptr(campos), dptr(geom), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh),
-                dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), st), "d3ga_raster_preprocess_bwd"))
-        elif g_loss is not None:
-            check(L.d3ga_raster_backward_l1(
-                ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
-                dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img),
-                dptr(image), dptr(l1_t), dptr(l1_cell), dptr(g_loss), dptr(grad_color), dptr(acc), dptr(g_means3D),
-                dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots),
-                stream_handle()), "d3ga_raster_backward_l1")
-        else:
-            check(L.d3ga_raster_backward(
-                ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
-                dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), ctx.cap, dptr(img),
-                dptr(grad_color), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col),
-                dptr(g_cov), dptr(g_scales), dptr(g_rots), stream_handle()), "d3ga_raster_backward")
+        has_sh, from_sr, sync = sh is not None, cov3Ds_precomp is None, ctx.grad_sync
+        g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm = _grad_buffers(
+            prm, has_sh, from_sr, dev, exchanged=sync is not None, geo=(P,), opac=(P, 1), col=None if has_sh else (P, 3), lead=())
+        g_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        _launch_backward(prm, ctx.cap, (means3D, sh, scales, rotations, cov3Ds_precomp), (view, proj, campos), bg, geom, binning, img,
+                         grad_color, (g_means3D, g_means2D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots),
+                         (colors2, bg2, grad_color2) if dual else None, g_invd,
+                         (image, l1_t, l1_cell, g_loss) if g_loss is not None else None)
         if sync is not None:
-            if factor is not None:
-                factor[P].copy_(campos.reshape(-1)[:3])
-            if getattr(sync, "deferred", False):
-                # two-graph step (d3ga_amd.graph.CapturedCutStep): the collectives run between the graphs, on these buffers
-                parts_by_name = {"means3D": g_means3D, "opacities": g_opac}
-                if from_sr:
-                    parts_by_name.update(scales=g_scales, rotations=g_rots)
-                else:
-                    parts_by_name["cov3D_precomp"] = g_cov
-                if sh is None:
-                    parts_by_name["colors_precomp"] = g_col
-                sync.park(flat, factor, parts_by_name,
-                          None if factor is None else {"P": P, "M": prm.M, "sh_degree": prm.sh_degree, "means3D": means3D})
-                # the parked gradients come back REDUCED through graph.CapturedCutStep: returning them here as well would
-                # leave the unreduced copy on the (detached) leaves, where the step adds the other loss terms' gradients
-                return (None, g_means2D if ctx.has_means2D else None, None, None, None, None, None, None, None, None, None,
-                        None, None, None, None)
-            gathered = sync.exchange(flat, factor)         # flat: summed (averaged) in place; gathered: (world, P+1, 3)
-            if factor is not None:
-                g_sh = new(P, prm.M, 3)
-                check(L.d3ga_sh_grad_from_views(P, prm.M, prm.sh_degree, sync.world, dptr(means3D), dptr(gathered),
-                                                3 * (P + 1), dptr(gathered[0, P]), 3 * (P + 1), sync.scale, dptr(g_sh),
-                                                stream_handle()), "d3ga_sh_grad_from_views")
+            parked, g_sh = _exchange_gradients(sync, prm, cut, campos, means3D)
+            if parked:
+                return (None, g_means2D if ctx.has_means2D else None) + (None,) * 13
+            if has_sh:
                 g_col = None
         return (g_means3D, g_means2D if ctx.has_means2D else None, g_sh, g_col, g_opac, g_scales, g_rots, g_cov, None,
                 None, None, None, None, None, None)
@@ -594,11 +718,7 @@ class GaussianRasterizer(nn.Module):
     def forward(self, means3D, means2D, opacities, shs: Optional[torch.Tensor] = None,
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
                 rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None):
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-                (scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, self.grad_sync, self.opacity_activation, self.want_invdepth)
 

@@ -96,6 +96,15 @@ def test_scratch_sizing_and_layout_no_gpu_needed():
     off = list(o)
     assert off == sorted(off) and off[0] == 0 and all(x % 256 == 0 for x in off)
     assert binning >= off[5] + 4 * 2_000_000
+    # the single-view sizes are the n_views = 1 case of the batched entry point (the Python layer calls only the latter)
+    v = (ctypes.c_int64 * 3)()
+    for P, W, H, cap in ((0, 64, 64, 1024), (1, 16, 16, 1), (300, 97, 61, 4 * 300 + 1024), (5000, 640, 360, 21024),
+                         (500000, 1920, 1080, 2_000_000), (2_000_000, 3840, 2160, 9_000_000)):
+        assert L.d3ga_raster_scratch_bytes(P, W, H, cap, s) == 0
+        for forward_only in (0, 1):
+            assert L.d3ga_raster_scratch_bytes_views(P, W, H, 1, cap, forward_only, v) == 0
+            assert list(v) == [s[0], s[1], L.d3ga_raster_img_bytes(W, H, cap, forward_only)]
+        assert s[2] == L.d3ga_raster_img_bytes(W, H, cap, 0)
     assert L.d3ga_raster_scratch_bytes(-1, 10, 10, 1, s) == -2          # D3GA_E_SIZE
     assert L.d3ga_raster_scratch_bytes(1, 10, 10, 1, None) == -1        # D3GA_E_NULL
 
