@@ -66,10 +66,23 @@ class LbsPoseGrad(ctypes.Structure):
                                                "g_Rh", "g_Th")]
 
 
+SKEL_MAX_JOINTS = 512    # D3GA_SKEL_MAX_JOINTS (include/d3ga.h)
+SKEL_SAVED_FLOATS = 12   # D3GA_SKEL_SAVED_FLOATS: floats per joint of the skeleton forward's `saved` buffer
+
+
+class Skeleton(ctypes.Structure):
+    """struct d3ga_skeleton (include/d3ga.h): sizes and device pointers of a prepared Goliath skeleton."""
+    _fields_ = [("J", ctypes.c_int32), ("n_params", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("n_children", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("parents", "level_ptr", "level_joint", "child_ptr", "child_joint", "joint_offset",
+                                               "joint_rotation", "transform_offsets", "csr_ptr", "csr_col", "csr_val", "csc_ptr",
+                                               "csc_row", "csc_val")]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _prm = ctypes.POINTER(RasterParams)
 _bm = ctypes.POINTER(BodyModel)
 _lpg = ctypes.POINTER(LbsPoseGrad)
+_sk = ctypes.POINTER(Skeleton)
 
 # name -> (argtypes, restype); the trailing _vp of every launch entry is the hipStream_t
 _SIGNATURES = {
@@ -153,6 +166,11 @@ _SIGNATURES = {
     "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),
     "d3ga_body_model_fwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 10 + [_vp, _i64, _vp], _i),
     "d3ga_body_model_bwd": ([_bm, ctypes.c_int32, ctypes.c_int32] + [_vp] * 12 + [_vp, _i64, _vp], _i),
+    "d3ga_skeleton_check": ([_sk] + [ctypes.c_int32] * 3, _i),
+    "d3ga_skeleton_fwd": ([_sk] + [ctypes.c_int32] * 3 + [_vp, _vp, ctypes.c_int32, _vp, _vp, _f, ctypes.c_int32] + [_vp] * 4 + [_vp], _i),
+    "d3ga_skeleton_bwd": ([_sk] + [ctypes.c_int32] * 4 + [_vp, _f, ctypes.c_int32] + [_vp] * 8 + [_vp], _i),
+    "d3ga_skeleton_mats_fwd": ([ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "d3ga_skeleton_mats_bwd": ([ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -752,6 +752,60 @@ int d3ga_color_rows_fwd(int32_t P, int32_t F, const float *dirs, const float *fe
 int d3ga_color_rows_bwd(int32_t P, int32_t F, const float *dirs, const float *d_x, float *d_dirs, float *d_feats,
                         d3ga_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * B2  Goliath skeleton (added without an ABI number change: new entry points only, no existing layout moves).
+ * The momentum-style skeleton of lbsmodel/body_model.py: ParameterTransform (:23-46), solve_skeleton_state (:311-347),
+ * states_to_matrix (:350-387) and the root transform (:176-191).  Host side: d3ga_amd/skeleton_model.py.
+ *   A skeleton state is 8 floats: translation 3 | quaternion xyzw 4 | scale 1.  Quaternions are used as given (never normalised;
+ *   the bind inverse divides by |q|^2).
+ *   Every joint has 7 skeleton parameters [t 3 | Euler xyz 3 | log2 scale] = transform . [poses; scales] + transform_offsets;
+ *   the (7J, n_params) transform is held twice, nonzeros only: CSR (csr_ptr (7J+1), csr_col ascending, csr_val) for the forward
+ *   and CSC (csc_ptr (n_params+1), csc_row ascending, csc_val) for its transpose in the backward.
+ *   Local transform: t + joint_offset, joint_rotation (x) q(Euler) with half angles (-rx/2, ry/2, rz/2), scale 2^p.
+ *   Child from parent: q = q_p (x) q_l, t = rot(q_p, t_l s_p) + t_p, s = s_p s_l; parents[j] < 0 is a root (its state is its
+ *   local transform).  The tree by level (level_ptr (n_levels+1), level_joint (J): a parent sits in an earlier level) and by
+ *   children (child_ptr (J+1), child_joint (n_children), a joint's children ascending).  2 <= J <= D3GA_SKEL_MAX_JOINTS.
+ *   Joint matrix against a bind state (J,8): [R(q (x) q_b^-1) s / s_b | t], written as the row-major 4x4 d3ga_lbs_cage_fwd reads,
+ *   its translation column multiplied by trans_scale (a unit change folded into the skinning; the root output is not scaled).
+ * fwd: one workgroup per (frame, scale set).  poses (B, pose_width) are parameters 0 .. pose_width, scales the remaining
+ *   n_params - pose_width ones: (scale_rows, .) with scale_rows 1 (shared by the frames) or B, NULL = zeros.  Scale set 0 reads
+ *   `scales`, sets 1 .. n_sets-1 read zeros (the root solve of LinearBlendSkinning.compute_root_rigid_transform).  direct != NULL:
+ *   (B, 7J) skeleton parameters as they are, no transform (n_sets must be 1).
+ *   -> states (n_sets,B,J,8), saved (n_sets,B,J,D3GA_SKEL_SAVED_FLOATS) for the backward, mats (n_sets,B,J,4,4) | NULL,
+ *   root (n_sets,B,12) = [R 9 row-major | t 3] of joint root_joint | NULL; mats and root need bind.
+ * bwd: one workgroup per frame.  Upstream g_states, g_mats (bottom row ignored), g_root in the forward's layouts, NULL = zero
+ *   -> g_poses (B, pose_width), g_scales (B, n_params - pose_width) per frame (from set 0 only), or with direct_mode
+ *   g_direct (B, 7J); NULL = not written.  No atomics: two calls give bitwise-equal gradients.
+ * No scratch, no host synchronisation: capturable.  d3ga_skeleton_check: the host-side size / NULL checks of both.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_SKEL_MAX_JOINTS 512
+#define D3GA_SKEL_SAVED_FLOATS 12       /* per joint: local state 8 | Euler angles 3 | 0 */
+typedef struct d3ga_skeleton {
+    int32_t J, n_params;        /* joints; pose + scale parameters */
+    int32_t n_levels;           /* levels of the kinematic tree */
+    int32_t n_children;         /* joints with a parent */
+    const int32_t *parents, *level_ptr, *level_joint, *child_ptr, *child_joint;
+    const float *joint_offset;      /* (J,3) */
+    const float *joint_rotation;    /* (J,4) xyzw */
+    const float *transform_offsets; /* (7J) */
+    const int32_t *csr_ptr, *csr_col;
+    const float *csr_val;
+    const int32_t *csc_ptr, *csc_row;
+    const float *csc_val;
+} d3ga_skeleton;
+int d3ga_skeleton_check(const d3ga_skeleton *model, int32_t B, int32_t n_sets, int32_t pose_width);
+int d3ga_skeleton_fwd(const d3ga_skeleton *model, int32_t B, int32_t n_sets, int32_t pose_width, const float *poses,
+                      const float *scales, int32_t scale_rows, const float *direct, const float *bind, float trans_scale,
+                      int32_t root_joint, float *states, float *saved, float *mats, float *root, d3ga_stream_t stream);
+int d3ga_skeleton_bwd(const d3ga_skeleton *model, int32_t B, int32_t n_sets, int32_t pose_width, int32_t direct_mode,
+                      const float *bind, float trans_scale, int32_t root_joint, const float *states, const float *saved,
+                      const float *g_states, const float *g_mats, const float *g_root, float *g_poses, float *g_scales,
+                      float *g_direct, d3ga_stream_t stream);
+/* states (B,J,8) -> mats (B,J,4,4) against bind (J,8), and dL/d(states) from g_mats (bottom row ignored; bind is a constant) */
+int d3ga_skeleton_mats_fwd(int32_t B, int32_t J, const float *bind, const float *states, float *mats, d3ga_stream_t stream);
+int d3ga_skeleton_mats_bwd(int32_t B, int32_t J, const float *bind, const float *states, const float *g_mats, float *g_states,
+                           d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -21,6 +21,8 @@ called as they are:
               (only with the argument `lbs_pose`)                                  -> lbs_pose_grad_case.npz
   G10 blur    models.learnable_blur.LearnableBlur (forward, reg, autograd gradients) with the absent torchvision
               gaussian_blur bound to tests/image_tail_ref.py (only with the argument `blur`, or a full run) -> blur_cases.npz
+  G11 skeleton  lbsmodel.body_model.LBSModule on a synthetic rig: parameter transform, skeleton solve, joint matrices, skinning,
+              root transform, autograd gradients (only with the argument `skeleton`)   -> skeleton_cases.npz
 The only stand-in with numerical content besides that blur is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
@@ -609,9 +611,65 @@ def gen_blur(lb_mod):
     np.savez(os.path.join(OUT, "blur_cases.npz"), **out)
 
 
+def gen_skeleton(bm):
+    """lbsmodel/body_model.py on a small synthetic rig of our own (tests/goliath_ref.py: random_rig, rig_json): 24 joints in a
+    random parent-first tree, a sparse parameter transform (10 pose + 4 scale parameters), pre-rotations of which two have norm
+    1 +- 1e-3, 200 vertices with 8-sparse weights.  The reference's LBSModule is built from it and run as it is:
+    ParameterTransform, solve_skeleton_state, states_to_matrix, LinearBlendSkinning.forward, compute_root_rigid_transform and
+    LBSModule.pose, plus autograd gradients of forward for a fixed upstream gradient w.r.t. poses, scales and verts_unposed, and
+    of the root transform w.r.t. poses.  Arrays only, plus the state_dict key names of the reference's LBSModule."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import goliath_ref as gr
+    rng = np.random.default_rng(41)
+    J, NP, NS, V, B = 24, 10, 4, 200, 2
+    rig = gr.random_rig(rng, J, NP, NS, kind="bushy", V=V, t_mag=0.5, unused=1)
+    jrot = rig.joint_rotation.numpy().astype(np.float32)
+    jrot[3] *= np.float32(1.001)                       # "as given", not "normalised first"
+    jrot[11] *= np.float32(0.999)
+    joff = rig.joint_offset.numpy().astype(np.float32)
+    T, off = rig.transform.numpy().astype(np.float32), rig.offsets.numpy().astype(np.float32)
+    idx, w = rig.skin_idx.numpy(), rig.skin_w.numpy().astype(np.float32)
+    rest = rng.normal(size=(V, 3)).astype(np.float32)
+    template = (rest + 0.05 * rng.normal(size=(V, 3))).astype(np.float32)
+    lbs_scale = (0.2 * rng.normal(size=(1, NS))).astype(np.float32)
+    global_scaling = np.asarray([1.1, 0.9, 1.05], dtype=np.float32)
+    mod = bm.LBSModule(gr.rig_json(joff, jrot, rig.parents, idx, w, rest), gr.rig_config(T, off, NP, NS), template, lbs_scale,
+                       global_scaling)
+    lbs = mod.lbs_fn
+    g = torch.Generator().manual_seed(43)
+    poses = (0.8 * torch.randn(B, NP, generator=g)).requires_grad_(True)
+    scales = (0.3 * torch.randn(B, NS, generator=g)).requires_grad_(True)
+    verts = torch.randn(B, V, 3, generator=g).requires_grad_(True)
+    param = lbs.param_transform(torch.cat([poses, scales], 1))
+    states = bm.solve_skeleton_state(param, lbs.joint_offset, lbs.joint_rotation, lbs.joint_parents)
+    mat = bm.states_to_matrix(lbs.bind_state, states)
+    out = lbs(poses, scales, verts)
+    gout = torch.randn(out.shape, generator=g)
+    (out * gout).sum().backward()
+    g_poses, g_scales, g_verts = poses.grad.clone(), scales.grad.clone(), verts.grad.clone()
+    poses.grad = None
+    t_root, R_root = lbs.compute_root_rigid_transform(poses)
+    gt, gR = torch.randn(t_root.shape, generator=g), torch.randn(R_root.shape, generator=g)
+    ((t_root * gt).sum() + (R_root * gR).sum()).backward()
+    posed = mod.pose(poses.detach())
+    np.savez(os.path.join(OUT, "skeleton_cases.npz"), transform=T, transform_offsets=off, joint_offset=joff, joint_rotation=jrot,
+             parents=rig.parents.astype(np.int32), skin_indices=idx.astype(np.int32), skin_weights=w, rest=rest, template=template,
+             lbs_scale=lbs_scale, global_scaling=global_scaling, poses=poses.detach().numpy(), scales=scales.detach().numpy(),
+             verts=verts.detach().numpy(), param=param.detach().numpy(), bind_state=lbs.bind_state.numpy(),
+             states=states.detach().numpy(), mat=mat.detach().numpy(), out=out.detach().numpy(), grad_out=gout.numpy(),
+             grad_poses=g_poses.numpy(), grad_scales=g_scales.numpy(), grad_verts=g_verts.numpy(),
+             t_root=t_root.detach().numpy(), R_root=R_root.detach().numpy(), grad_t_root=gt.numpy(), grad_R_root=gR.numpy(),
+             grad_poses_root=poses.grad.numpy(), posed=posed.detach().numpy(),
+             state_dict_keys=np.asarray(list(mod.state_dict().keys())))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_harness()
+    if sys.argv[1:] == ["skeleton"]:            # one section only (the other fixtures are left untouched)
+        import lbsmodel.body_model as bm
+        gen_skeleton(bm)
+        return
     if sys.argv[1:] == ["blur"]:                # one section only (the other fixtures are left untouched)
         import models.learnable_blur as lb_mod
         gen_blur(lb_mod)
