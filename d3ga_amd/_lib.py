@@ -11,7 +11,7 @@ ACC_STRIDE = 16          # D3GA_ACC_STRIDE (include/d3ga.h): floats per Gaussian
 # touching their `_version`, so host-side caches keyed by (data_ptr, _version) -- the packed weight panels of mlp.py --
 # carry this epoch in their key as well (eager forward -> replays with in-graph Adam -> eager forward used stale panels).
 replay_epoch = [0]
-ABI_VERSION = 111       # D3GA_VERSION (include/d3ga.h)
+ABI_VERSION = 112       # D3GA_VERSION (include/d3ga.h)
 # D3GA_KNOB_* (include/d3ga.h), in key order
 KNOBS = ("composite_variant", "merge_slots", "tile_assign", "bwd_split", "sort_merge", "ssim_impl", "wgrad_ws", "chain_abl", "chain_grid")
 CAMERA_SLOT_WINDOWED = -1.0    # D3GA_CAMERA_SLOT_WINDOWED (include/d3ga.h): tanfovx of a windowed camera slot, 9 floats per view in campos
@@ -66,6 +66,32 @@ class LbsPoseGrad(ctypes.Structure):
                                                "g_Rh", "g_Th")]
 
 
+DEFORM_ROUTE_CORNERS, DEFORM_ROUTE_MERGE = 1, 2    # D3GA_DEFORM_ROUTE_* (include/d3ga.h)
+
+
+class CageDeformIn(ctypes.Structure):
+    """struct d3ga_cage_deform_in (include/d3ga.h): sizes, flags and inputs of the fused cage deformation."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("P", "V", "flags", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("tetpoints", "tetras", "tetra_id", "barys", "canon_grad", "scales", "rots", "delta_barys")]
+
+
+class CageDeformGrads(ctypes.Structure):
+    """struct d3ga_cage_deform_grads: the two incoming and the four outgoing gradients of its backward."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("g_means", "g_cov6", "g_tetpoints", "g_barys", "g_scales", "g_rots")]
+
+
+class CageDeformRoute(ctypes.Structure):
+    """struct d3ga_cage_deform_route: how the backward sums the vertex gradient (per-corner records | block-merge plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "n_segments")] + \
+               [(n, ctypes.c_void_p) for n in ("item_pos", "seg_begin", "seg_ptr", "vert_start", "vert_items", "records")]
+
+
+class CageDeformSkin(ctypes.Structure):
+    """struct d3ga_cage_deform_skin: the skinning backward in the vertex-gather launch of the merge route."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("K", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("joint_mats", "skin_idx", "skin_w", "Rh", "g_tetpoints_extra", "g_delta")]
+
+
 SKEL_MAX_JOINTS = 512    # D3GA_SKEL_MAX_JOINTS (include/d3ga.h)
 SKEL_SAVED_FLOATS = 12   # D3GA_SKEL_SAVED_FLOATS: floats per joint of the skeleton forward's `saved` buffer
 
@@ -91,16 +117,10 @@ _SIGNATURES = {
     "d3ga_debug_set": ([ctypes.c_int32, ctypes.c_int32], _i),
     "d3ga_debug_defaults": ([ctypes.POINTER(ctypes.c_int32), ctypes.c_int32], _i),
     "d3ga_lbs_cage_fwd": ([_i, _i] + [_vp] * 8 + [_vp], _i),
-    "d3ga_lbs_cage_bwd": ([_i, _i] + [_vp] * 6 + [_vp], _i),
+    "d3ga_lbs_cage_bwd": ([_i, _i] + [_vp] * 6 + [_lpg, _vp], _i),
     "d3ga_lbs_pose_scratch_bytes": ([_i, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
-    "d3ga_lbs_cage_bwd_pose": ([_i, _i] + [_vp] * 6 + [_lpg, _vp], _i),
-    "d3ga_cage_deform_fwd": ([_i] + [_vp] * 9 + [_vp], _i),
-    "d3ga_cage_deform_bwd": ([_i, _i] + [_vp] * 16 + [_vp], _i),
-    "d3ga_cage_deform_fwd_ex": ([_i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 2 + [_vp], _i),
-    "d3ga_cage_deform_bwd_ex": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [_vp], _i),
-    "d3ga_cage_deform_bwd_merged": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_vp], _i),
-    "d3ga_cage_deform_bwd_merged_lbs": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_i] + [_vp] * 6 + [_vp], _i),
-    "d3ga_cage_deform_bwd_merged_lbs_pose": ([_i, _i] + [_vp] * 8 + [ctypes.c_int32] + [_vp] * 9 + [ctypes.c_int32] + [_vp] * 3 + [_i] + [_vp] * 6 + [_lpg, _vp], _i),
+    "d3ga_cage_deform_fwd": ([ctypes.POINTER(CageDeformIn), _vp, _vp, _vp], _i),
+    "d3ga_cage_deform_bwd": ([ctypes.POINTER(c) for c in (CageDeformIn, CageDeformGrads, CageDeformRoute, CageDeformSkin)] + [_lpg, _vp], _i),
     "d3ga_fem_energy_fwd": ([_i] + [_vp] * 4 + [_vp], _i),
     "d3ga_fem_energy_bwd": ([_i, _i] + [_vp] * 5 + [_vp], _i),
     "d3ga_raster_scratch_bytes": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.POINTER(_i64)], _i),

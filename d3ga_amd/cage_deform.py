@@ -8,7 +8,7 @@ Host-side mirror of the reference's per-frame tensor program (SURVEY.md sec. 8a 
 All three call hand-written gfx950 kernels through the C ABI (include/d3ga.h); GPU tensors only.
 """
 import ctypes
-import os
+import warnings
 
 import torch
 
@@ -24,62 +24,62 @@ def _f32c(t):
     return t.contiguous()
 
 
-_i32_cache = {}
+class StorageCache:
+    """Values derived from tensors that stay put (index buffers, templates), built once: keyed by every source's (data_ptr,
+    _version, shape, dtype) and `extra`.  An entry pins its sources, so their addresses cannot be recycled while it lives;
+    beyond `limit` entries the cache is emptied."""
+
+    def __init__(self, limit=64):
+        self.limit, self.entries = limit, {}
+
+    def get(self, sources, extra, build):
+        key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in sources) + (extra,)
+        hit = self.entries.get(key)
+        if hit is None:
+            value = build()
+            if len(self.entries) > self.limit:
+                self.entries.clear()
+            hit = self.entries[key] = (value, sources)
+        return hit[0]
+
+
+_i32_cache, _adjacency_cache, _plan_cache, _pose_plan_cache = StorageCache(), StorageCache(), StorageCache(), StorageCache()
 
 
 def _i32c(t):
     """int32 contiguous view of an index buffer.  The reference registers int64 buffers (lib/cage.py:331-337); their
-    int32 copies are cached (keyed on storage + version, holding the source alive) so that per-frame calls neither
-    convert again nor defeat the adjacency cache below."""
+    int32 copies are cached so that per-frame calls neither convert again nor defeat the adjacency cache below."""
     if t.dtype == torch.int32 and t.is_contiguous():
         return t
-    key = (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
-    hit = _i32_cache.get(key)
-    if hit is None:
-        if len(_i32_cache) > 64:
-            _i32_cache.clear()
-        hit = (t, t.to(torch.int32).contiguous())
-        _i32_cache[key] = hit
-    return hit[1]
-
-
-_adjacency_cache = {}
+    return _i32_cache.get((t,), None, lambda: t.to(torch.int32).contiguous())
 
 
 def vertex_adjacency(tetras, tetra_id, n_vertices):
     """Static CSR adjacency vertex -> items (4*gaussian + corner) of a cage binding; built once and cached.
     (tetra_id / tetras are buffers fixed at initialisation, lib/cage.py:331-337.)"""
-    key = (tetras.data_ptr(), tetra_id.data_ptr(), tetras._version, tetra_id._version, tetra_id.shape[0], n_vertices)
-    hit = _adjacency_cache.get(key)
-    if hit is None:
+    def build():
         with torch.no_grad():
             vid = tetras.long()[tetra_id.long()].reshape(-1)                    # (4P,) vertex of item 4*i + corner
             order = torch.sort(vid, stable=True)[1]
             counts = torch.bincount(vid, minlength=n_vertices)
             start = torch.zeros(n_vertices + 1, dtype=torch.int64, device=vid.device)
             start[1:] = torch.cumsum(counts, 0)
-            hit = (start.to(torch.int32).contiguous(), order.to(torch.int32).contiguous(), tetras, tetra_id)
-        if len(_adjacency_cache) > 64:
-            _adjacency_cache.clear()
-        _adjacency_cache[key] = hit          # holds tetras / tetra_id alive: their addresses cannot be recycled
-    return hit[0], hit[1]
+            return start.to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+    return _adjacency_cache.get((tetras, tetra_id), n_vertices, build)
 
 
-_plan_cache = {}
 _MERGE_BLOCK = 256        # = kBlock of csrc/deform.hip: the Gaussians of one workgroup
-# D3GA_DEFORM_MERGE=0: per-corner gradient records + a gather over all 4P items (rounds 1-3; kept for A/B runs)
-_merge_policy = {"enabled": os.environ.get("D3GA_DEFORM_MERGE", "1") != "0"}
+# enabled = False: per-corner gradient records + a gather over all 4P items (rounds 1-3; kept for A/B runs and tests)
+_merge_policy = {"enabled": True}
 
 
 def merge_plan(tetras, tetra_id, n_vertices):
-    """Static plan of the block-merged backward (d3ga_cage_deform_bwd_merged), built once per binding and cached:
+    """Static plan of the block-merged backward (D3GA_DEFORM_ROUTE_MERGE), built once per binding and cached:
     -> dict(item_pos (P,4) int16-as-uint16, seg_ptr (blocks+1) int32, seg_begin (segments) uint16 stored as int16,
             vert_start (V+1) int32, vert_parts (segments) int32, n_segments).
     Items are (Gaussian, corner) pairs, 1024 per workgroup of 256 consecutive Gaussians; inside a workgroup they are ordered
     by cage vertex (stable), a SEGMENT is a run of equal vertex, and every segment's sum becomes one partial."""
-    key = (tetras.data_ptr(), tetra_id.data_ptr(), tetras._version, tetra_id._version, tetra_id.shape[0], n_vertices)
-    hit = _plan_cache.get(key)
-    if hit is None:
+    def build():
         with torch.no_grad():
             dev = tetra_id.device
             P = tetra_id.shape[0]
@@ -101,17 +101,77 @@ def merge_plan(tetras, tetra_id, n_vertices):
             seg_ptr = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
             seg_ptr[1:] = torch.cumsum(torch.bincount(seg_blk, minlength=nb), 0)
             seg_begin = (seg_first - seg_blk * per).to(torch.int16).contiguous()
-            nseg = int(seg_first.numel())
             order2 = torch.sort(seg_vid, stable=True)[1]
             vstart = torch.zeros(n_vertices + 1, dtype=torch.int64, device=dev)
             vstart[1:] = torch.cumsum(torch.bincount(seg_vid, minlength=n_vertices), 0)
-            hit = dict(item_pos=item_pos, seg_ptr=seg_ptr.to(torch.int32).contiguous(), seg_begin=seg_begin,
-                       vert_start=vstart.to(torch.int32).contiguous(), vert_parts=order2.to(torch.int32).contiguous(),
-                       n_segments=nseg, pins=(tetras, tetra_id))
-        if len(_plan_cache) > 64:
-            _plan_cache.clear()
-        _plan_cache[key] = hit               # holds tetras / tetra_id alive: their addresses cannot be recycled
-    return hit
+            return dict(item_pos=item_pos, seg_ptr=seg_ptr.to(torch.int32).contiguous(), seg_begin=seg_begin,
+                        vert_start=vstart.to(torch.int32).contiguous(), vert_parts=order2.to(torch.int32).contiguous(),
+                        n_segments=int(seg_first.numel()))
+    return _plan_cache.get((tetras, tetra_id), n_vertices, build)
+
+
+def _deform_in(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, flags):
+    """struct d3ga_cage_deform_in (delta_barys None -> NULL)."""
+    return _lib.CageDeformIn(P=barys.shape[0], V=tetpoints.shape[0], flags=flags, tetpoints=dptr(tetpoints), tetras=dptr(tetras),
+                             tetra_id=dptr(tetra_id), barys=dptr(barys), canon_grad=dptr(canon_grad), scales=dptr(scales),
+                             rots=dptr(rotations), delta_barys=dptr(delta_barys))
+
+
+def _deform_fwd(st, dev):
+    means = torch.empty((st.P, 3), dtype=torch.float32, device=dev)
+    cov6 = torch.empty((st.P, 6), dtype=torch.float32, device=dev)
+    check(_lib.lib().d3ga_cage_deform_fwd(ctypes.byref(st), dptr(means), dptr(cov6), stream_handle()), "d3ga_cage_deform_fwd")
+    return means, cov6
+
+
+def _deform_saved(saved, has_delta_barys):
+    """The eight tensors both nodes save first, by name (an empty tensor stands for a missing delta_barys)."""
+    names = ("tetpoints", "tetras", "tetra_id", "barys", "canon_grad", "scales", "rotations", "delta_barys")
+    inputs = dict(zip(names, saved[:8]))
+    if not has_delta_barys:
+        inputs["delta_barys"] = None
+    return inputs
+
+
+def _deform_bwd(inputs, flags, g_means, g_cov6, *, want_tetpoints=False, want_barys, want_scales, want_rotations, skin=None, pose=None):
+    """The one call of d3ga_cage_deform_bwd.  inputs: _deform_saved(...); want_*: which gradients to form.
+    skin = dict(joint_mats, skin_idx, skin_w, Rh | None, g_extra | None): the skinning tail, whose g_delta stands in for the vertex
+    gradient; pose = dict(template, delta | None) adds the pose gradients to it.
+    -> dict(vertices = g_tetpoints | g_delta, barys, scales, rotations, pose = (gA, gRh, gTh)), None where not wanted."""
+    tetras, tetra_id = inputs["tetras"], inputs["tetra_id"]
+    st = _deform_in(flags=flags, **inputs)
+    P, V, dev = st.P, st.V, inputs["barys"].device
+
+    def new(n, c, on=True):
+        return torch.empty((n, c), dtype=torch.float32, device=dev) if on else None
+    g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
+    g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
+    g_v, g_b, g_s, g_r = new(V, 3, want_tetpoints or skin is not None), new(P, 4, want_barys), new(P, 3, want_scales), new(P, 4, want_rotations)
+    grads = _lib.CageDeformGrads(g_means=dptr(g_means), g_cov6=dptr(g_cov6), g_tetpoints=dptr(None if skin is not None else g_v),
+                                 g_barys=dptr(g_b), g_scales=dptr(g_s), g_rots=dptr(g_r))
+    route = tail = pose_st = pose_out = None
+    if skin is not None or (g_v is not None and P > 0 and _merge_policy["enabled"]):
+        plan = merge_plan(tetras, tetra_id, V)
+        records = new(max(plan["n_segments"], 1), 3)
+        route = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=plan["n_segments"], item_pos=dptr(plan["item_pos"]),
+                                     seg_ptr=dptr(plan["seg_ptr"]), seg_begin=dptr(plan["seg_begin"]),
+                                     vert_start=dptr(plan["vert_start"]), vert_items=dptr(plan["vert_parts"]), records=dptr(records))
+    elif g_v is not None and P > 0:          # (P == 0: the library zeroes g_tetpoints without a route)
+        vstart, vitems = vertex_adjacency(tetras, tetra_id, V)
+        records = new(4 * P, 3)
+        route = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_CORNERS, vert_start=dptr(vstart), vert_items=dptr(vitems),
+                                     records=dptr(records))
+    if skin is not None:
+        g_extra = _f32c(skin["g_extra"])
+        tail = _lib.CageDeformSkin(K=skin["skin_w"].shape[1], joint_mats=dptr(skin["joint_mats"]), skin_idx=dptr(skin["skin_idx"]),
+                                   skin_w=dptr(skin["skin_w"]), Rh=dptr(skin["Rh"]), g_tetpoints_extra=dptr(g_extra), g_delta=dptr(g_v))
+        if pose is not None:
+            plan_p = lbs_pose_plan(skin["skin_idx"], skin["joint_mats"].shape[0])
+            pose_st, pose_out, scratch = _pose_grad_struct(plan_p, V, 1, pose["template"], pose["delta"], dev)
+    ref = lambda x: None if x is None else ctypes.byref(x)
+    check(_lib.lib().d3ga_cage_deform_bwd(ctypes.byref(st), ctypes.byref(grads), ref(route), ref(tail), ref(pose_st),
+                                          stream_handle()), "d3ga_cage_deform_bwd")
+    return dict(vertices=g_v, barys=g_b, scales=g_s, rotations=g_r, pose=pose_out)
 
 
 class _CageDeform(torch.autograd.Function):
@@ -120,15 +180,10 @@ class _CageDeform(torch.autograd.Function):
         require_cuda(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations)
         tetpoints, barys, canon_grad, scales, rotations, delta_barys = map(
             _f32c, (tetpoints, barys, canon_grad, scales, rotations, delta_barys))
-        P = barys.shape[0]
-        means = torch.empty((P, 3), dtype=torch.float32, device=barys.device)
-        cov6 = torch.empty((P, 6), dtype=torch.float32, device=barys.device)
-        check(_lib.lib().d3ga_cage_deform_fwd_ex(P, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys),
-                                                 dptr(canon_grad), dptr(scales), dptr(rotations), dptr(delta_barys),
-                                                 flags, dptr(means), dptr(cov6), stream_handle()),
-              "d3ga_cage_deform_fwd_ex")
         ctx.flags = flags
         ctx.has_delta = delta_barys is not None
+        means, cov6 = _deform_fwd(_deform_in(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, flags),
+                                  barys.device)
         ctx.set_materialize_grads(False)                 # backward() fills in the gradient of an unused output itself
         ctx.save_for_backward(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations,
                               delta_barys if delta_barys is not None else torch.empty(0, device=barys.device))
@@ -136,37 +191,28 @@ class _CageDeform(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_means, g_cov6):
-        tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys = ctx.saved_tensors
-        if not ctx.has_delta:
-            delta_barys = None
-        P, V = barys.shape[0], tetpoints.shape[0]
-        dev = barys.device
-        g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
-        g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
         need = ctx.needs_input_grad
-        g_tp = torch.empty((V, 3), dtype=torch.float32, device=dev) if need[0] else None
-        g_b = torch.empty((P, 4), dtype=torch.float32, device=dev) if (need[3] or need[7]) else None
-        g_s = torch.empty((P, 3), dtype=torch.float32, device=dev) if need[5] else None
-        g_r = torch.empty((P, 4), dtype=torch.float32, device=dev) if need[6] else None
-        vstart = vitems = corner = None
-        if need[0] and P > 0 and _merge_policy["enabled"]:
-            plan = merge_plan(tetras, tetra_id, V)
-            partials = torch.empty((plan["n_segments"], 3), dtype=torch.float32, device=dev)
-            check(_lib.lib().d3ga_cage_deform_bwd_merged(
-                P, V, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys), dptr(canon_grad), dptr(scales),
-                dptr(rotations), dptr(delta_barys), ctx.flags, dptr(g_means), dptr(g_cov6), dptr(g_tp), dptr(g_b), dptr(g_s),
-                dptr(g_r), dptr(plan["item_pos"]), dptr(plan["seg_ptr"]), dptr(plan["seg_begin"]), plan["n_segments"],
-                dptr(plan["vert_start"]), dptr(plan["vert_parts"]), dptr(partials), stream_handle()), "d3ga_cage_deform_bwd_merged")
-            return (g_tp, None, None, g_b if need[3] else None, None, g_s, g_r, g_b if need[7] else None, None)
-        if need[0] and P > 0:
-            vstart, vitems = vertex_adjacency(tetras, tetra_id, V)
-            corner = torch.empty((P, 4, 3), dtype=torch.float32, device=dev)
-        check(_lib.lib().d3ga_cage_deform_bwd_ex(P, V, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys),
-                                                 dptr(canon_grad), dptr(scales), dptr(rotations), dptr(delta_barys),
-                                                 ctx.flags, dptr(g_means), dptr(g_cov6), dptr(g_tp), dptr(g_b),
-                                                 dptr(g_s), dptr(g_r), dptr(vstart), dptr(vitems), dptr(corner),
-                                                 stream_handle()), "d3ga_cage_deform_bwd_ex")
-        return (g_tp, None, None, g_b if need[3] else None, None, g_s, g_r, g_b if need[7] else None, None)
+        g = _deform_bwd(_deform_saved(ctx.saved_tensors, ctx.has_delta), ctx.flags, g_means, g_cov6, want_tetpoints=need[0],
+                        want_barys=need[3] or need[7], want_scales=need[5], want_rotations=need[6])
+        return (g["vertices"], None, None, g["barys"] if need[3] else None, None, g["scales"], g["rotations"],
+                g["barys"] if need[7] else None, None)
+
+
+def _deform_flags(op, barys, tetras, canonical_gradient, scale_activation, gradient_per_tet, say_which):
+    """The argument checks cage_deform and lbs_cage_deform share -> the D3GA_DEFORM_* flags.  op: the caller's name, for its
+    warning (raised at ITS caller: stacklevel 3); say_which: name the expected layout in the error."""
+    if scale_activation not in (None, "exp"):
+        raise ValueError(f"scale_activation must be None or 'exp', got {scale_activation!r}")
+    P, T = barys.shape[0], tetras.shape[0]
+    if gradient_per_tet is None:             # (T,3,3) is recognised by its length unless T == P (then say which)
+        if canonical_gradient.shape[0] == T and T == P:
+            warnings.warn(f"{op}: as many tetrahedra as Gaussians -- canonical_gradient is read per GAUSSIAN (the reference's "
+                          "layout, lib/cage.py:329); pass gradient_per_tet=True if it is the per-tetrahedron table", stacklevel=3)
+        gradient_per_tet = canonical_gradient.shape[0] == T and T != P
+    if canonical_gradient.shape[0] != (T if gradient_per_tet else P):
+        which = f" ({'one per tetrahedron' if gradient_per_tet else 'one per Gaussian'})" if say_which else ""
+        raise ValueError(f"canonical_gradient has {canonical_gradient.shape[0]} matrices, expected {T if gradient_per_tet else P}{which}")
+    return (1 if scale_activation == "exp" else 0) | (2 if gradient_per_tet else 0)
 
 
 def cage_deform(tetpoints, tetras, tetra_id, barys, canonical_gradient, scales, rotations, delta_barys=None,
@@ -184,24 +230,11 @@ def cage_deform(tetpoints, tetras, tetra_id, barys, canonical_gradient, scales, 
     `canonical_gradient` may also be ONE matrix per tetrahedron, (T,3,3) = `canonical_gradient_per_tet(...)` (round 4): the
     reference gathers the same matrices per Gaussian at init (lib/cage.py:329), which makes the op stream 36 B x P per pass;
     the per-tet table is read through `tetra_id` and stays in L2."""
-    if scale_activation not in (None, "exp"):
-        raise ValueError(f"scale_activation must be None or 'exp', got {scale_activation!r}")
-    P, T = barys.shape[0], tetras.shape[0]
-    if gradient_per_tet is None:             # (T,3,3) is recognised by its length unless T == P (then say which)
-        if canonical_gradient.shape[0] == T and T == P:
-            import warnings
-            warnings.warn("cage_deform: as many tetrahedra as Gaussians -- canonical_gradient is read per GAUSSIAN (the reference's "
-                          "layout, lib/cage.py:329); pass gradient_per_tet=True if it is the per-tetrahedron table", stacklevel=2)
-        gradient_per_tet = canonical_gradient.shape[0] == T and T != P
-    if canonical_gradient.shape[0] != (T if gradient_per_tet else P):
-        raise ValueError(f"canonical_gradient has {canonical_gradient.shape[0]} matrices, expected "
-                         f"{T if gradient_per_tet else P} ({'one per tetrahedron' if gradient_per_tet else 'one per Gaussian'})")
-    flags = (1 if scale_activation == "exp" else 0) | (2 if gradient_per_tet else 0)
+    flags = _deform_flags("cage_deform", barys, tetras, canonical_gradient, scale_activation, gradient_per_tet, True)
     return _CageDeform.apply(tetpoints, _i32c(tetras), _i32c(tetra_id), barys, canonical_gradient, scales, rotations,
                              delta_barys, flags)
 
 
-_pose_plan_cache = {}
 _POSE_CHUNK = 256         # = kBlock of csrc/deform.hip: the entries of one workgroup of the by-joint reduction
 
 
@@ -218,9 +251,7 @@ def lbs_pose_plan(skin_idx, J):
         raise ValueError(f"skin_idx must be (V,K), got {tuple(skin_idx.shape)}")
     if J <= 0:
         raise ValueError(f"joint_mats must hold at least one joint, got J = {J}")
-    key = (skin_idx.data_ptr(), skin_idx._version, tuple(skin_idx.shape), skin_idx.dtype, J)
-    hit = _pose_plan_cache.get(key)
-    if hit is None:
+    def build():
         with torch.no_grad():
             dev = skin_idx.device
             V, K = skin_idx.shape
@@ -243,13 +274,10 @@ def lbs_pose_plan(skin_idx, J):
             q = torch.arange(cj.numel(), device=dev) - chunk_ptr[cj]
             beg = start[cj] + q * _POSE_CHUNK
             end = torch.minimum(beg + _POSE_CHUNK, start[cj + 1])
-            hit = dict(entries=order.to(torch.int32).contiguous(), chunk_range=torch.stack([beg, end], 1).to(torch.int32).contiguous(),
-                       chunk_ptr=chunk_ptr.to(torch.int32).contiguous(), n_chunks=int(cj.numel()), n_entries=V * K, J=J,
-                       counter=torch.zeros(1, dtype=torch.int32, device=dev), pins=skin_idx)
-        if len(_pose_plan_cache) > 64:
-            _pose_plan_cache.clear()
-        _pose_plan_cache[key] = hit          # holds skin_idx alive: its address cannot be recycled
-    return hit
+            return dict(entries=order.to(torch.int32).contiguous(), chunk_range=torch.stack([beg, end], 1).to(torch.int32).contiguous(),
+                        chunk_ptr=chunk_ptr.to(torch.int32).contiguous(), n_chunks=int(cj.numel()), n_entries=V * K, J=J,
+                        counter=torch.zeros(1, dtype=torch.int32, device=dev))
+    return _pose_plan_cache.get((skin_idx,), J, build)
 
 
 def sparse_skin_weights(dense_w, rows=None, K=None):
@@ -280,8 +308,7 @@ def sparse_skin_weights(dense_w, rows=None, K=None):
     return idx.to(torch.int32).contiguous(), w.contiguous()
 
 
-def _pose_needed(need, i_A, i_Rh, i_Th):
-    return bool(need[i_A] or need[i_Rh] or need[i_Th])
+_POSE_INPUTS = (2, 5, 6)     # joint_mats, Rh, Th among the inputs of _LbsCage and _LbsCageDeform, which both start with lbs_cage's seven
 
 
 def _check_pose_plan(skin_idx, joint_mats, Rh, Th):
@@ -306,66 +333,75 @@ def _pose_grad_struct(plan, V, fused, template, delta, dev):
     return st, (gA, gRh, gTh), scratch
 
 
-def _pose_returns(ctx, need, i_A, i_Rh, i_Th, gA, gRh, gTh):
-    return (gA.view(ctx.shape_A) if need[i_A] else None, gRh.view(ctx.shape_Rh) if (ctx.has_Rh and need[i_Rh]) else None,
-            gTh.view(ctx.shape_Th) if (ctx.has_Th and need[i_Th]) else None)
+def _pose_zeros(J, dev):
+    """The pose gradients of a cage without vertices (the C ABI takes `pose` with V > 0 only)."""
+    return torch.zeros((J, 4, 4), device=dev), torch.zeros((3, 3), device=dev), torch.zeros((3,), device=dev)
+
+
+def _lbs_fwd(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th):
+    """The skinning launch of both nodes and what their backward keeps of it
+    -> (posed vertices (V,3), tensors to save: joint_mats, skin_idx, skin_w, Rh, then template, delta when a pose gradient is wanted)."""
+    ctx.pose = any(ctx.needs_input_grad[i] for i in _POSE_INPUTS)
+    if ctx.pose:
+        ctx.shape_A, ctx.shape_Rh, ctx.shape_Th = (joint_mats.shape, None if Rh is None else Rh.shape,
+                                                   None if Th is None else Th.shape)
+    template, delta, joint_mats, skin_w, Rh, Th = map(_f32c, (template, delta, joint_mats, skin_w, Rh, Th))
+    V, K = skin_w.shape
+    out = torch.empty((V, 3), dtype=torch.float32, device=template.device)
+    check(_lib.lib().d3ga_lbs_cage_fwd(V, K, dptr(template), dptr(delta), dptr(joint_mats), dptr(skin_idx),
+                                       dptr(skin_w), dptr(Rh), dptr(Th), dptr(out), stream_handle()),
+          "d3ga_lbs_cage_fwd")
+    ctx.has_Rh, ctx.has_Th, ctx.has_delta = Rh is not None, Th is not None, delta is not None
+    none = torch.empty(0, device=out.device)
+    pose = (template, delta if delta is not None else none) if ctx.pose else ()     # the pose gradients read p~ = template + delta
+    return out, (joint_mats, skin_idx, skin_w, Rh if Rh is not None else none) + pose
+
+
+def _lbs_saved(ctx, saved):
+    """What _lbs_fwd saved, by name -> dict(joint_mats, skin_idx, skin_w, Rh | None), and dict(template, delta | None) when this
+    backward owes a pose gradient, else None."""
+    skin = dict(zip(("joint_mats", "skin_idx", "skin_w", "Rh"), saved[:4]))
+    if not ctx.has_Rh:
+        skin["Rh"] = None
+    pose = None
+    if ctx.pose and any(ctx.needs_input_grad[i] for i in _POSE_INPUTS):
+        pose = dict(template=saved[4], delta=saved[5] if ctx.has_delta else None)
+    return skin, pose
+
+
+def _lbs_returns(ctx, g_d, pose_out):
+    """The gradients of lbs_cage's seven inputs from dL/d(delta) and the (gA, gRh, gTh) | None of the pose backward."""
+    need = ctx.needs_input_grad
+    gA, gRh, gTh = (None, None, None) if pose_out is None else (
+        pose_out[0].view(ctx.shape_A) if need[2] else None, pose_out[1].view(ctx.shape_Rh) if (ctx.has_Rh and need[5]) else None,
+        pose_out[2].view(ctx.shape_Th) if (ctx.has_Th and need[6]) else None)
+    return g_d if need[0] else None, g_d if (ctx.has_delta and need[1]) else None, gA, None, None, gRh, gTh
 
 
 class _LbsCage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th):
         require_cuda(template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
-        ctx.pose = _pose_needed(ctx.needs_input_grad, 2, 5, 6)
-        if ctx.pose:
-            ctx.shape_A, ctx.shape_Rh, ctx.shape_Th = (joint_mats.shape, None if Rh is None else Rh.shape,
-                                                       None if Th is None else Th.shape)
-        template, delta, joint_mats, skin_w, Rh, Th = map(_f32c, (template, delta, joint_mats, skin_w, Rh, Th))
-        V, K = skin_w.shape
-        out = torch.empty((V, 3), dtype=torch.float32, device=template.device)
-        check(_lib.lib().d3ga_lbs_cage_fwd(V, K, dptr(template), dptr(delta), dptr(joint_mats), dptr(skin_idx),
-                                           dptr(skin_w), dptr(Rh), dptr(Th), dptr(out), stream_handle()),
-              "d3ga_lbs_cage_fwd")
-        none = torch.empty(0, device=out.device)
-        if ctx.pose:                         # the pose gradients read p~ = template + delta
-            ctx.save_for_backward(joint_mats, skin_idx, skin_w, Rh if Rh is not None else none, template,
-                                  delta if delta is not None else none)
-        else:
-            ctx.save_for_backward(joint_mats, skin_idx, skin_w, Rh if Rh is not None else none)
-        ctx.has_Rh = Rh is not None
-        ctx.has_Th = Th is not None
-        ctx.has_delta = delta is not None
+        out, saved = _lbs_fwd(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
+        ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        need = ctx.needs_input_grad
-        if not ctx.pose or not _pose_needed(need, 2, 5, 6):
-            joint_mats, skin_idx, skin_w, Rh = ctx.saved_tensors[:4]
-            V, K = skin_w.shape
-            gd = torch.empty((V, 3), dtype=torch.float32, device=g.device)
-            check(_lib.lib().d3ga_lbs_cage_bwd(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
-                                               dptr(Rh if ctx.has_Rh else None), dptr(_f32c(g)), dptr(gd),
-                                               stream_handle()), "d3ga_lbs_cage_bwd")
-            g_t = gd if ctx.needs_input_grad[0] else None
-            g_d = gd if (ctx.has_delta and ctx.needs_input_grad[1]) else None
-            return g_t, g_d, None, None, None, None, None
-        joint_mats, skin_idx, skin_w, Rh, template, delta = ctx.saved_tensors
+        skin, pose = _lbs_saved(ctx, ctx.saved_tensors)
+        joint_mats, skin_idx, skin_w, Rh = skin["joint_mats"], skin["skin_idx"], skin["skin_w"], skin["Rh"]
         V, K = skin_w.shape
-        dev = g.device
+        J, dev, g = joint_mats.shape[0], g.device, _f32c(g)
         gd = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        if V == 0:
-            gA, gRh, gTh = (torch.zeros((joint_mats.shape[0], 4, 4), device=dev), torch.zeros((3, 3), device=dev),
-                            torch.zeros((3,), device=dev))
+        st = pose_out = None
+        if pose is not None and V == 0:
+            pose_out = _pose_zeros(J, dev)
         else:
-            plan = lbs_pose_plan(skin_idx, joint_mats.shape[0])
-            st, (gA, gRh, gTh), scratch = _pose_grad_struct(plan, V, 0, template, delta if ctx.has_delta else None, dev)
-            check(_lib.lib().d3ga_lbs_cage_bwd_pose(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
-                                                    dptr(Rh if ctx.has_Rh else None), dptr(_f32c(g)), dptr(gd), ctypes.byref(st),
-                                                    stream_handle()), "d3ga_lbs_cage_bwd_pose")
-        g_t = gd if need[0] else None
-        g_d = gd if (ctx.has_delta and need[1]) else None
-        g_A, g_Rh, g_Th = _pose_returns(ctx, need, 2, 5, 6, gA, gRh, gTh)
-        return g_t, g_d, g_A, None, None, g_Rh, g_Th
+            if pose is not None:
+                st, pose_out, scratch = _pose_grad_struct(lbs_pose_plan(skin_idx, J), V, 0, pose["template"], pose["delta"], dev)
+            check(_lib.lib().d3ga_lbs_cage_bwd(V, K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w), dptr(Rh), dptr(g), dptr(gd),
+                                               None if st is None else ctypes.byref(st), stream_handle()), "d3ga_lbs_cage_bwd")
+        return _lbs_returns(ctx, gd, pose_out)
 
 
 def skeleton_matrices(bind_state, target_states):
@@ -416,97 +452,37 @@ def lbs_cage(template, delta, joint_mats, skin_idx, skin_w, Rh=None, Th=None):
 class _LbsCageDeform(torch.autograd.Function):
     """lbs_cage + cage_deform as ONE autograd node (round 5): the forward is the two launches of the separate operators; the
     backward merges the corner gradients per workgroup (merge_plan) and forms dL/d(delta) in the vertex-gather launch
-    (d3ga_cage_deform_bwd_merged_lbs) -- one launch instead of the gather + d3ga_lbs_cage_bwd."""
+    (struct d3ga_cage_deform_skin) -- one launch instead of the gather + d3ga_lbs_cage_bwd; the pose gradients take one more."""
 
     @staticmethod
     def forward(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th, tetras, tetra_id, barys, canon_grad, scales, rotations,
                 delta_barys, flags):
         require_cuda(template, delta, joint_mats, skin_idx, skin_w, Rh, Th, tetras, tetra_id, barys, canon_grad, scales, rotations)
-        ctx.pose = _pose_needed(ctx.needs_input_grad, 2, 5, 6)
-        if ctx.pose:
-            ctx.shape_A, ctx.shape_Rh, ctx.shape_Th = (joint_mats.shape, None if Rh is None else Rh.shape,
-                                                       None if Th is None else Th.shape)
-        template, delta, joint_mats, skin_w, Rh, Th = map(_f32c, (template, delta, joint_mats, skin_w, Rh, Th))
+        tetpoints, lbs_saved = _lbs_fwd(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
         barys, canon_grad, scales, rotations, delta_barys = map(_f32c, (barys, canon_grad, scales, rotations, delta_barys))
-        V, K = skin_w.shape
-        P, dev = barys.shape[0], barys.device
-        L = _lib.lib()
-        tetpoints = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        check(L.d3ga_lbs_cage_fwd(V, K, dptr(template), dptr(delta), dptr(joint_mats), dptr(skin_idx), dptr(skin_w), dptr(Rh),
-                                  dptr(Th), dptr(tetpoints), stream_handle()), "d3ga_lbs_cage_fwd")
-        means = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        cov6 = torch.empty((P, 6), dtype=torch.float32, device=dev)
-        check(L.d3ga_cage_deform_fwd_ex(P, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys), dptr(canon_grad),
-                                        dptr(scales), dptr(rotations), dptr(delta_barys), flags, dptr(means), dptr(cov6),
-                                        stream_handle()), "d3ga_cage_deform_fwd_ex")
-        ctx.flags, ctx.has_dbary, ctx.has_Rh, ctx.has_delta = flags, delta_barys is not None, Rh is not None, delta is not None
-        ctx.has_Th = Th is not None
+        ctx.flags, ctx.has_dbary = flags, delta_barys is not None
+        means, cov6 = _deform_fwd(_deform_in(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, flags),
+                                  barys.device)
         ctx.set_materialize_grads(False)
-        none = torch.empty(0, device=dev)
-        pose = (template, delta if delta is not None else none) if ctx.pose else ()      # the pose gradients read p~ = template + delta
         ctx.save_for_backward(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations,
-                              delta_barys if delta_barys is not None else none, joint_mats, skin_idx, skin_w,
-                              Rh if Rh is not None else none, *pose)
+                              delta_barys if delta_barys is not None else torch.empty(0, device=barys.device), *lbs_saved)
         return means, cov6, tetpoints
 
     @staticmethod
     def backward(ctx, g_means, g_cov6, g_tp_extra):
-        (tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, joint_mats, skin_idx, skin_w,
-         Rh) = ctx.saved_tensors[:12]
-        P, V, K, dev = barys.shape[0], tetpoints.shape[0], skin_w.shape[1], barys.device
-        if ctx.pose and _pose_needed(ctx.needs_input_grad, 2, 5, 6):
-            return _LbsCageDeform._backward_pose(ctx, g_means, g_cov6, g_tp_extra)
-        g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
-        g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
         need = ctx.needs_input_grad
-        g_b = torch.empty((P, 4), dtype=torch.float32, device=dev) if (need[9] or need[13]) else None
-        g_s = torch.empty((P, 3), dtype=torch.float32, device=dev) if need[11] else None
-        g_r = torch.empty((P, 4), dtype=torch.float32, device=dev) if need[12] else None
-        g_d = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        plan = merge_plan(tetras, tetra_id, V)
-        partials = torch.empty((max(plan["n_segments"], 1), 3), dtype=torch.float32, device=dev)
-        check(_lib.lib().d3ga_cage_deform_bwd_merged_lbs(
-            P, V, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys), dptr(canon_grad), dptr(scales), dptr(rotations),
-            dptr(delta_barys if ctx.has_dbary else None), ctx.flags, dptr(g_means), dptr(g_cov6), None, dptr(g_b), dptr(g_s),
-            dptr(g_r), dptr(plan["item_pos"]), dptr(plan["seg_ptr"]), dptr(plan["seg_begin"]), plan["n_segments"],
-            dptr(plan["vert_start"]), dptr(plan["vert_parts"]), dptr(partials), K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
-            dptr(Rh if ctx.has_Rh else None), dptr(None if g_tp_extra is None else _f32c(g_tp_extra)), dptr(g_d),
-            stream_handle()), "d3ga_cage_deform_bwd_merged_lbs")
-        return (g_d if need[0] else None, g_d if (ctx.has_delta and need[1]) else None, None, None, None, None, None, None, None,
-                g_b if need[9] else None, None, g_s, g_r, g_b if need[13] else None, None)
-
-    @staticmethod
-    def _backward_pose(ctx, g_means, g_cov6, g_tp_extra):
-        """The backward with dL/d(joint_mats, Rh, Th): d3ga_cage_deform_bwd_merged_lbs_pose (one launch more than the one above)."""
-        (tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, joint_mats, skin_idx, skin_w,
-         Rh, template, delta) = ctx.saved_tensors
-        P, V, K, dev = barys.shape[0], tetpoints.shape[0], skin_w.shape[1], barys.device
-        g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
-        g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
-        need = ctx.needs_input_grad
-        g_b = torch.empty((P, 4), dtype=torch.float32, device=dev) if (need[9] or need[13]) else None
-        g_s = torch.empty((P, 3), dtype=torch.float32, device=dev) if need[11] else None
-        g_r = torch.empty((P, 4), dtype=torch.float32, device=dev) if need[12] else None
-        g_d = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        if V == 0:
-            gA, gRh, gTh = (torch.zeros((joint_mats.shape[0], 4, 4), device=dev), torch.zeros((3, 3), device=dev),
-                            torch.zeros((3,), device=dev))
-            g_b, g_s, g_r = (None if t is None else t.zero_() for t in (g_b, g_s, g_r))     # no cage: no Gaussian either
+        inputs = _deform_saved(ctx.saved_tensors, ctx.has_dbary)
+        skin, pose = _lbs_saved(ctx, ctx.saved_tensors[8:])
+        P, V, dev = inputs["barys"].shape[0], inputs["tetpoints"].shape[0], inputs["barys"].device
+        want = dict(want_barys=need[9] or need[13], want_scales=need[11], want_rotations=need[12])
+        if pose is not None and V == 0:                  # no cage: no Gaussian either
+            zeros = lambda c, on: torch.zeros((P, c), device=dev) if on else None
+            g = dict(vertices=torch.empty((0, 3), device=dev), pose=_pose_zeros(skin["joint_mats"].shape[0], dev),
+                     barys=zeros(4, want["want_barys"]), scales=zeros(3, want["want_scales"]), rotations=zeros(4, want["want_rotations"]))
         else:
-            mplan = merge_plan(tetras, tetra_id, V)
-            partials = torch.empty((max(mplan["n_segments"], 1), 3), dtype=torch.float32, device=dev)
-            plan = lbs_pose_plan(skin_idx, joint_mats.shape[0])
-            st, (gA, gRh, gTh), scratch = _pose_grad_struct(plan, V, 1, template, delta if ctx.has_delta else None, dev)
-            check(_lib.lib().d3ga_cage_deform_bwd_merged_lbs_pose(
-                P, V, dptr(tetpoints), dptr(tetras), dptr(tetra_id), dptr(barys), dptr(canon_grad), dptr(scales), dptr(rotations),
-                dptr(delta_barys if ctx.has_dbary else None), ctx.flags, dptr(g_means), dptr(g_cov6), None, dptr(g_b), dptr(g_s),
-                dptr(g_r), dptr(mplan["item_pos"]), dptr(mplan["seg_ptr"]), dptr(mplan["seg_begin"]), mplan["n_segments"],
-                dptr(mplan["vert_start"]), dptr(mplan["vert_parts"]), dptr(partials), K, dptr(joint_mats), dptr(skin_idx), dptr(skin_w),
-                dptr(Rh if ctx.has_Rh else None), dptr(None if g_tp_extra is None else _f32c(g_tp_extra)), dptr(g_d),
-                ctypes.byref(st), stream_handle()), "d3ga_cage_deform_bwd_merged_lbs_pose")
-        g_A, g_Rh, g_Th = _pose_returns(ctx, need, 2, 5, 6, gA, gRh, gTh)
-        return (g_d if need[0] else None, g_d if (ctx.has_delta and need[1]) else None, g_A, None, None, g_Rh, g_Th, None, None,
-                g_b if need[9] else None, None, g_s, g_r, g_b if need[13] else None, None)
+            g = _deform_bwd(inputs, ctx.flags, g_means, g_cov6, skin=dict(skin, g_extra=g_tp_extra), pose=pose, **want)
+        return _lbs_returns(ctx, g["vertices"], g["pose"]) + (None, None, g["barys"] if need[9] else None, None, g["scales"],
+                                                              g["rotations"], g["barys"] if need[13] else None, None)
 
 
 def lbs_cage_deform(template, delta, joint_mats, skin_idx, skin_w, tetras, tetra_id, barys, canonical_gradient, scales, rotations,
@@ -517,18 +493,7 @@ def lbs_cage_deform(template, delta, joint_mats, skin_idx, skin_w, tetras, tetra
     for the terms that read them directly (the FEM regulariser, lib/cage.py:349-361) -- their gradient joins the skinning backward.
     Differentiable in joint_mats, Rh and Th as lbs_cage is (the pose gradients take one launch more in the backward, and only
     when one of the three requires a gradient)."""
-    if scale_activation not in (None, "exp"):
-        raise ValueError(f"scale_activation must be None or 'exp', got {scale_activation!r}")
-    P, T = barys.shape[0], tetras.shape[0]
-    if gradient_per_tet is None:
-        if canonical_gradient.shape[0] == T and T == P:
-            import warnings
-            warnings.warn("lbs_cage_deform: as many tetrahedra as Gaussians -- canonical_gradient is read per GAUSSIAN (the reference's "
-                          "layout, lib/cage.py:329); pass gradient_per_tet=True if it is the per-tetrahedron table", stacklevel=2)
-        gradient_per_tet = canonical_gradient.shape[0] == T and T != P
-    if canonical_gradient.shape[0] != (T if gradient_per_tet else P):
-        raise ValueError(f"canonical_gradient has {canonical_gradient.shape[0]} matrices, expected {T if gradient_per_tet else P}")
-    flags = (1 if scale_activation == "exp" else 0) | (2 if gradient_per_tet else 0)
+    flags = _deform_flags("lbs_cage_deform", barys, tetras, canonical_gradient, scale_activation, gradient_per_tet, False)
     skin_idx = _i32c(skin_idx)
     _check_pose_plan(skin_idx, joint_mats, Rh, Th)
     return _LbsCageDeform.apply(template, delta, joint_mats, skin_idx, skin_w, Rh, Th, _i32c(tetras), _i32c(tetra_id), barys,

@@ -5,8 +5,7 @@
 // Cage vertices (V*12 B, a few hundred KB) and tets (T*16 B) are gathered through L2; the per-Gaussian streams
 // (tet id, barycentrics, canonical gradient, scale, rotation -> mean, covariance) are read/written once with
 // lane-contiguous addresses.  Gaussians are expected sorted by tet id (static during training), so the four
-// corner gathers of neighbouring lanes hit the same cache lines and the backward's vertex-gradient atomics
-// of a wavefront collapse onto few addresses.
+// corner gathers of neighbouring lanes hit the same cache lines.
 #include "d3ga_internal.h"
 
 namespace d3ga {
@@ -34,6 +33,29 @@ __device__ __forceinline__ float row_sum_(float v) {
 // ---------------------------------------------------------------------------------------------------------
 // D0: v' = Rh (sum_k w_k A[idx_k]) [v + delta; 1] + Th
 // ---------------------------------------------------------------------------------------------------------
+// T = sum_k w_k A[idx_k] (rows 0..2 of the 4x4), k ascending
+__device__ __forceinline__ void skin_blend(int v, int K, const float *__restrict__ A, const int32_t *__restrict__ idx,
+                                           const float *__restrict__ w, float (&T)[12]) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float wk = w[(size_t)v * K + k];
+        const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) T[i] += wk * a[i];
+    }
+}
+__device__ __forceinline__ V3 skin_apply(const float (&T)[12], V3 p) {
+    return v3(T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
+              T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]);
+}
+// Rh^T g (g itself without a global rotation)
+__device__ __forceinline__ V3 rot_transposed(const float *__restrict__ Rh, V3 g) {
+    if (!Rh) return g;
+    return v3(Rh[0] * g.x + Rh[3] * g.y + Rh[6] * g.z, Rh[1] * g.x + Rh[4] * g.y + Rh[7] * g.z,
+              Rh[2] * g.x + Rh[5] * g.y + Rh[8] * g.z);
+}
+
 __global__ __launch_bounds__(kBlock) void lbs_fwd_kernel(int V, int K, const float *__restrict__ tmpl,
                                                          const float *__restrict__ delta,
                                                          const float *__restrict__ A,
@@ -45,16 +67,8 @@ __global__ __launch_bounds__(kBlock) void lbs_fwd_kernel(int V, int K, const flo
     V3 p = load3(tmpl, v);
     if (delta) p = p + load3(delta, v);
     float T[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float wk = w[(size_t)v * K + k];
-        const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) T[i] += wk * a[i];
-    }
-    V3 o = v3(T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
-              T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]);
+    skin_blend(v, K, A, idx, w, T);
+    V3 o = skin_apply(T, p);
     if (Rh) o = v3(Rh[0] * o.x + Rh[1] * o.y + Rh[2] * o.z, Rh[3] * o.x + Rh[4] * o.y + Rh[5] * o.z,
                    Rh[6] * o.x + Rh[7] * o.y + Rh[8] * o.z);
     if (Th) o = o + v3(Th[0], Th[1], Th[2]);
@@ -67,24 +81,15 @@ __global__ __launch_bounds__(kBlock) void lbs_bwd_kernel(int V, int K, const flo
                                                          float *__restrict__ gdelta) {
     const int v = blockIdx.x * kBlock + threadIdx.x;
     if (v >= V) return;
-    V3 go = load3(g, v);
-    if (Rh) go = v3(Rh[0] * go.x + Rh[3] * go.y + Rh[6] * go.z, Rh[1] * go.x + Rh[4] * go.y + Rh[7] * go.z,
-                    Rh[2] * go.x + Rh[5] * go.y + Rh[8] * go.z);
+    const V3 go = rot_transposed(Rh, load3(g, v));
     float T[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float wk = w[(size_t)v * K + k];
-        const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) T[i] += wk * a[i];
-    }
+    skin_blend(v, K, A, idx, w, T);
     gdelta[3 * v] = T[0] * go.x + T[4] * go.y + T[8] * go.z;
     gdelta[3 * v + 1] = T[1] * go.x + T[5] * go.y + T[9] * go.z;
     gdelta[3 * v + 2] = T[2] * go.x + T[6] * go.y + T[10] * go.z;
 }
 
-// Pose gradients of D0 (dL/dA, dL/dRh, dL/dTh; d3ga_lbs_cage_bwd_pose, d3ga_cage_deform_bwd_merged_lbs_pose).  With
+// Pose gradients of D0 (dL/dA, dL/dRh, dL/dTh; the `pose` argument of d3ga_lbs_cage_bwd and d3ga_cage_deform_bwd).  With
 // p~ = [tmpl + delta; 1], T = sum_k w_k A[idx_k], o = T p~ (before Rh), g = dL/dout and g' = Rh^T g:
 //   dA_j[0:3,0:4] = sum over the (v,k) with idx = j of w_vk g'_v p~_v^T   (row 3 is never read: exact zeros)
 //   dRh = sum_v g_v o_v^T,  dTh = sum_v g_v.
@@ -130,9 +135,7 @@ __global__ __launch_bounds__(kBlock) void lbs_pose_reduce_kernel(
             const float wk = w[q];
             V3 p = load3(tmpl, v);
             if (delta) p = p + load3(delta, v);
-            V3 go = load3(g, v);
-            if (Rh) go = v3(Rh[0] * go.x + Rh[3] * go.y + Rh[6] * go.z, Rh[1] * go.x + Rh[4] * go.y + Rh[7] * go.z,
-                            Rh[2] * go.x + Rh[5] * go.y + Rh[8] * go.z);
+            const V3 go = rot_transposed(Rh, load3(g, v));
             const V3 wg = v3(wk * go.x, wk * go.y, wk * go.z);
             ps[0] = wg.x * p.x; ps[1] = wg.x * p.y; ps[2] = wg.x * p.z; ps[3] = wg.x;
             ps[4] = wg.y * p.x; ps[5] = wg.y * p.y; ps[6] = wg.y * p.z; ps[7] = wg.y;
@@ -144,16 +147,8 @@ __global__ __launch_bounds__(kBlock) void lbs_pose_reduce_kernel(
             V3 p = load3(tmpl, v);
             if (delta) p = p + load3(delta, v);
             float T[12];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) T[i] = 0.f;
-            for (int k = 0; k < K; ++k) {
-                const float wk = w[(size_t)v * K + k];
-                const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
-#pragma unroll
-                for (int i = 0; i < 12; ++i) T[i] += wk * a[i];
-            }
-            const V3 o = v3(T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
-                            T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]);
+            skin_blend(v, K, A, idx, w, T);
+            const V3 o = skin_apply(T, p);
             const V3 gv = load3(g, v);
             ps[0] = gv.x * o.x; ps[1] = gv.x * o.y; ps[2] = gv.x * o.z;
             ps[3] = gv.y * o.x; ps[4] = gv.y * o.y; ps[5] = gv.y * o.z;
@@ -251,13 +246,7 @@ __global__ __launch_bounds__(kBlock) void cage_deform_fwd_kernel(int P, const fl
     for (int k = 0; k < 6; ++k) cov6[6 * (size_t)i + k] = c[k];
 }
 
-__device__ __forceinline__ void atomic_add3(float *base, int v, V3 g) {
-    atomicAdd(base + 3 * (size_t)v, g.x);
-    atomicAdd(base + 3 * (size_t)v + 1, g.y);
-    atomicAdd(base + 3 * (size_t)v + 2, g.z);
-}
-
-// Block-level merge of the corner gradients (round 4; d3ga_cage_deform_bwd_merged).  The binding is static, so for every
+// Block-level merge of the corner gradients (round 4; D3GA_DEFORM_ROUTE_MERGE).  The binding is static, so for every
 // workgroup of 256 consecutive Gaussians the positions of its 1024 (Gaussian, corner) items in vertex-sorted order
 // (item_pos), the segments of equal vertex (seg_ptr / seg_begin) and where each segment's sum goes (partial g = global
 // segment index) are built ONCE (cage_deform.py: merge_plan).  The kernel drops its corner gradients into LDS at those
@@ -276,8 +265,8 @@ __global__ __launch_bounds__(kBlock) void cage_deform_bwd_kernel(
     const float *__restrict__ barys, const float *__restrict__ canon_grad, const float *__restrict__ scales,
     const float *__restrict__ rots, const float *__restrict__ delta_barys, int flags,
     const float *__restrict__ g_means, const float *__restrict__ g_cov6,
-    float *__restrict__ g_tetpoints, float *__restrict__ g_barys, float *__restrict__ g_scales,
-    float *__restrict__ g_rots, float *__restrict__ corner_grads, DeformMerge mg) {
+    float *__restrict__ g_barys, float *__restrict__ g_scales, float *__restrict__ g_rots, float *__restrict__ corner_grads,
+    DeformMerge mg) {
     __shared__ float s_val[3][4 * kBlock];                 // merged path: the workgroup's corner gradients in vertex order
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= P && !mg.item_pos) return;
@@ -317,14 +306,11 @@ __global__ __launch_bounds__(kBlock) void cage_deform_bwd_kernel(
             for (int k = b; k < e; ++k) { sx += s_val[0][k]; sy += s_val[1][k]; sz += s_val[2][k]; }
             mg.partials[3 * (size_t)g] = sx; mg.partials[3 * (size_t)g + 1] = sy; mg.partials[3 * (size_t)g + 2] = sz;
         }
-    } else if (corner_grads) {            // deterministic path: per-corner gradients, summed per vertex by vertex_gather_kernel
+    } else if (corner_grads) {            // per-corner gradients, summed per vertex by vertex_gather_kernel
         float4 *c = reinterpret_cast<float4 *>(corner_grads + 12 * (size_t)i);
         c[0] = make_float4(o.gx0.x, o.gx0.y, o.gx0.z, o.gx1.x);
         c[1] = make_float4(o.gx1.y, o.gx1.z, o.gx2.x, o.gx2.y);
         c[2] = make_float4(o.gx2.z, o.gx3.x, o.gx3.y, o.gx3.z);
-    } else if (g_tetpoints) {
-        atomic_add3(g_tetpoints, vid.x, o.gx0); atomic_add3(g_tetpoints, vid.y, o.gx1);
-        atomic_add3(g_tetpoints, vid.z, o.gx2); atomic_add3(g_tetpoints, vid.w, o.gx3);
     }
 }
 
@@ -351,10 +337,18 @@ __global__ __launch_bounds__(kBlock) void vertex_gather_kernel(int V, const int3
 // The same with ONE DPP ROW (16 lanes) per vertex, four vertices per wavefront: for short item lists -- the partials of the
 // block-merged backward, two to four per vertex with coherent numbering -- a whole wavefront per vertex leaves 60 lanes idle
 // and the launch is 4x the wavefronts (7.3 -> .. us at C3).
-__global__ __launch_bounds__(kBlock) void vertex_gather_row_kernel(int V, const int32_t *__restrict__ vert_start,
+// LBS (round 5): the LBS backward of D0 behind the gather -- the posed cage vertices came from d3ga_lbs_cage_fwd, so
+// dL/d(delta) = (sum_k w_k A_k[:3,:3])^T Rh^T dL/d(tetpoint) is formed while the vertex gradient sits in the row's registers: one
+// launch instead of two for ~24 k vertices.  Lane k of the row takes joint k of the vertex.  g_extra: a gradient that reaches
+// the vertices by another route (the FEM regulariser), added before the skinning; g_tetpoints is then optional.
+template <bool LBS>
+__global__ __launch_bounds__(kBlock) void vertex_gather_row_kernel(int V, int K, const int32_t *__restrict__ vert_start,
                                                                    const int32_t *__restrict__ vert_items,
                                                                    const float *__restrict__ values,
-                                                                   float *__restrict__ g_tetpoints) {
+                                                                   const float *__restrict__ g_extra,
+                                                                   const float *__restrict__ A, const int32_t *__restrict__ idx,
+                                                                   const float *__restrict__ w, const float *__restrict__ Rh,
+                                                                   float *__restrict__ g_tetpoints, float *__restrict__ gdelta) {
     const int v = blockIdx.x * (kBlock / 16) + (threadIdx.x >> 4);
     const int l16 = threadIdx.x & 15;
     const bool live = v < V;
@@ -364,53 +358,35 @@ __global__ __launch_bounds__(kBlock) void vertex_gather_row_kernel(int V, const 
         const float *c = values + 3 * (size_t)vert_items[k];
         sx += c[0]; sy += c[1]; sz += c[2];
     }
+    if (LBS && g_extra && live && l16 == 0) { sx += g_extra[3 * (size_t)v]; sy += g_extra[3 * (size_t)v + 1]; sz += g_extra[3 * (size_t)v + 2]; }
     sx = row_sum_(sx); sy = row_sum_(sy); sz = row_sum_(sz);
-    if (live && l16 == 0) { g_tetpoints[3 * (size_t)v] = sx; g_tetpoints[3 * (size_t)v + 1] = sy; g_tetpoints[3 * (size_t)v + 2] = sz; }
-}
-// The same gather with the LBS backward of D0 behind it (round 5: d3ga_cage_deform_bwd_merged_lbs -- the posed cage vertices came
-// from d3ga_lbs_cage_fwd, so dL/d(delta) = (sum_k w_k A_k[:3,:3])^T Rh^T dL/d(tetpoint) can be formed while the vertex gradient sits
-// in the row's registers: one launch instead of two for ~24 k vertices).  Lane k of the row takes joint k of the vertex.
-// g_extra: a gradient that reaches the vertices by another route (the FEM regulariser), added before the skinning; g_tetpoints
-// (optional): the vertex gradient itself.
-__global__ __launch_bounds__(kBlock) void vertex_gather_lbs_row_kernel(int V, int K, const int32_t *__restrict__ vert_start,
-                                                                       const int32_t *__restrict__ vert_items,
-                                                                       const float *__restrict__ values,
-                                                                       const float *__restrict__ g_extra,
-                                                                       const float *__restrict__ A, const int32_t *__restrict__ idx,
-                                                                       const float *__restrict__ w, const float *__restrict__ Rh,
-                                                                       float *__restrict__ g_tetpoints, float *__restrict__ gdelta) {
-    const int v = blockIdx.x * (kBlock / 16) + (threadIdx.x >> 4);
-    const int l16 = threadIdx.x & 15;
-    const bool live = v < V;
-    const int b = live ? vert_start[v] : 0, e = live ? vert_start[v + 1] : 0;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int k = b + l16; k < e; k += 16) {
-        const float *c = values + 3 * (size_t)vert_items[k];
-        sx += c[0]; sy += c[1]; sz += c[2];
-    }
-    if (g_extra && live && l16 == 0) { sx += g_extra[3 * (size_t)v]; sy += g_extra[3 * (size_t)v + 1]; sz += g_extra[3 * (size_t)v + 2]; }
-    sx = row_sum_(sx); sy = row_sum_(sy); sz = row_sum_(sz);
-    if (g_tetpoints && live && l16 == 0) { g_tetpoints[3 * (size_t)v] = sx; g_tetpoints[3 * (size_t)v + 1] = sy; g_tetpoints[3 * (size_t)v + 2] = sz; }
-    V3 go = v3(sx, sy, sz);
-    if (Rh) go = v3(Rh[0] * go.x + Rh[3] * go.y + Rh[6] * go.z, Rh[1] * go.x + Rh[4] * go.y + Rh[7] * go.z,
-                    Rh[2] * go.x + Rh[5] * go.y + Rh[8] * go.z);
-    float dx = 0.f, dy = 0.f, dz = 0.f;
-    if (live) {
-        for (int k = l16; k < K; k += 16) {
-            const float wk = w[(size_t)v * K + k];
-            const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
-            dx += wk * (a[0] * go.x + a[4] * go.y + a[8] * go.z);
-            dy += wk * (a[1] * go.x + a[5] * go.y + a[9] * go.z);
-            dz += wk * (a[2] * go.x + a[6] * go.y + a[10] * go.z);
+    if ((!LBS || g_tetpoints) && live && l16 == 0) { g_tetpoints[3 * (size_t)v] = sx; g_tetpoints[3 * (size_t)v + 1] = sy; g_tetpoints[3 * (size_t)v + 2] = sz; }
+    if constexpr (LBS) {
+        const V3 go = rot_transposed(Rh, v3(sx, sy, sz));
+        float dx = 0.f, dy = 0.f, dz = 0.f;
+        if (live) {
+            for (int k = l16; k < K; k += 16) {
+                const float wk = w[(size_t)v * K + k];
+                const float *a = A + 16 * (size_t)idx[(size_t)v * K + k];
+                dx += wk * (a[0] * go.x + a[4] * go.y + a[8] * go.z);
+                dy += wk * (a[1] * go.x + a[5] * go.y + a[9] * go.z);
+                dz += wk * (a[2] * go.x + a[6] * go.y + a[10] * go.z);
+            }
         }
+        dx = row_sum_(dx); dy = row_sum_(dy); dz = row_sum_(dz);
+        if (live && l16 == 0) { gdelta[3 * (size_t)v] = dx; gdelta[3 * (size_t)v + 1] = dy; gdelta[3 * (size_t)v + 2] = dz; }
     }
-    dx = row_sum_(dx); dy = row_sum_(dy); dz = row_sum_(dz);
-    if (live && l16 == 0) { gdelta[3 * (size_t)v] = dx; gdelta[3 * (size_t)v + 1] = dy; gdelta[3 * (size_t)v + 2] = dz; }
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // D6
 // ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void atomic_add3(float *base, int v, V3 g) {
+    atomicAdd(base + 3 * (size_t)v, g.x);
+    atomicAdd(base + 3 * (size_t)v + 1, g.y);
+    atomicAdd(base + 3 * (size_t)v + 2, g.z);
+}
+
 __global__ __launch_bounds__(kBlock) void fem_fwd_kernel(int T, const float *__restrict__ tetpoints,
                                                          const int32_t *__restrict__ tetras,
                                                          const float *__restrict__ Dn_inv, float *__restrict__ energy) {
@@ -457,16 +433,6 @@ extern "C" int d3ga_lbs_cage_fwd(int V, int K, const float *tmpl, const float *d
     return check_launch((hipStream_t)stream, 0);
 }
 
-extern "C" int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
-                                 const float *Rh, const float *grad_out, float *grad_delta, d3ga_stream_t stream) {
-    if (V < 0 || K <= 0) return D3GA_E_SIZE;
-    if (V == 0) return D3GA_OK;
-    if (!joint_mats || !skin_idx || !skin_w || !grad_out || !grad_delta) return D3GA_E_NULL;
-    hipLaunchKernelGGL(lbs_bwd_kernel, dim3(nblocks(V)), dim3(kBlock), 0, (hipStream_t)stream, V, K, joint_mats,
-                       skin_idx, skin_w, Rh, grad_out, grad_delta);
-    return check_launch((hipStream_t)stream, 0);
-}
-
 // scratch of the pose backward: partials (12 per workgroup of the reduction) | the fused operator's vertex gradient (3V)
 static int64_t pose_groups(int V, int n_chunks) { return (int64_t)n_chunks + (V + kBlock - 1) / kBlock; }
 
@@ -478,7 +444,6 @@ extern "C" int d3ga_lbs_pose_scratch_bytes(int V, int32_t n_chunks, int32_t fuse
 }
 
 static int pose_check(int V, int K, const d3ga_lbs_pose_grad *pg) {
-    if (!pg) return D3GA_E_NULL;
     if (pg->J <= 0 || pg->n_chunks <= 0 || (int64_t)V * K != pg->n_entries) return D3GA_E_SIZE;
     if (!pg->tmpl || !pg->chunk_ptr || !pg->chunk_range || !pg->entries || !pg->counter || !pg->scratch || !pg->g_joint_mats ||
         !pg->g_Rh || !pg->g_Th)
@@ -496,160 +461,95 @@ static int pose_reduce(int V, int K, const float *joint_mats, const int32_t *ski
     return check_launch(s, 0);
 }
 
-extern "C" int d3ga_lbs_cage_bwd_pose(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
-                                      const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
-                                      d3ga_stream_t stream) {
-    if (V <= 0 || K <= 0) return D3GA_E_SIZE;
-    D3GA_TRY(pose_check(V, K, pose));
-    D3GA_TRY(d3ga_lbs_cage_bwd(V, K, joint_mats, skin_idx, skin_w, Rh, grad_out, grad_delta, stream));
-    return pose_reduce(V, K, joint_mats, skin_idx, skin_w, Rh, grad_out, pose, (hipStream_t)stream);
+extern "C" int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
+                                 const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
+                                 d3ga_stream_t stream) {
+    if (V < 0 || K <= 0 || (pose && V == 0)) return D3GA_E_SIZE;
+    if (V == 0) return D3GA_OK;
+    if (pose) D3GA_TRY(pose_check(V, K, pose));
+    if (!joint_mats || !skin_idx || !skin_w || !grad_out || !grad_delta) return D3GA_E_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(lbs_bwd_kernel, dim3(nblocks(V)), dim3(kBlock), 0, s, V, K, joint_mats, skin_idx, skin_w, Rh, grad_out,
+                       grad_delta);
+    D3GA_TRY(check_launch(s, 0));
+    return pose ? pose_reduce(V, K, joint_mats, skin_idx, skin_w, Rh, grad_out, pose, s) : D3GA_OK;
 }
 
-extern "C" int d3ga_cage_deform_fwd_ex(int P, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                                       const float *barys, const float *canon_grad, const float *scales,
-                                       const float *rots, const float *delta_barys, int32_t flags, float *means3D,
-                                       float *cov6, d3ga_stream_t stream) {
-    if (flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) return D3GA_E_CONFIG;
-    if (P < 0) return D3GA_E_SIZE;
-    if (P == 0) return D3GA_OK;
-    if (!tetpoints || !tetras || !tetra_id || !barys || !canon_grad || !scales || !rots || !means3D || !cov6)
-        return D3GA_E_NULL;
-    hipLaunchKernelGGL(cage_deform_fwd_kernel, dim3(nblocks(P)), dim3(kBlock), 0, (hipStream_t)stream, P, tetpoints,
-                       tetras, tetra_id, barys, canon_grad, scales, rots, delta_barys, (int)flags, means3D, cov6);
+// what the forward and the backward kernel both read
+static int deform_in_check(const d3ga_cage_deform_in *in) {
+    return (!in->tetpoints || !in->tetras || !in->tetra_id || !in->barys || !in->canon_grad || !in->scales || !in->rots)
+               ? D3GA_E_NULL : D3GA_OK;
+}
+
+extern "C" int d3ga_cage_deform_fwd(const d3ga_cage_deform_in *in, float *means3D, float *cov6, d3ga_stream_t stream) {
+    if (!in) return D3GA_E_NULL;
+    if (in->flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) return D3GA_E_CONFIG;
+    if (in->P < 0) return D3GA_E_SIZE;
+    if (in->P == 0) return D3GA_OK;
+    D3GA_TRY(deform_in_check(in));
+    if (!means3D || !cov6) return D3GA_E_NULL;
+    hipLaunchKernelGGL(cage_deform_fwd_kernel, dim3(nblocks(in->P)), dim3(kBlock), 0, (hipStream_t)stream, in->P, in->tetpoints,
+                       in->tetras, in->tetra_id, in->barys, in->canon_grad, in->scales, in->rots, in->delta_barys, (int)in->flags,
+                       means3D, cov6);
     return check_launch((hipStream_t)stream, 0);
 }
 
-extern "C" int d3ga_cage_deform_fwd(int P, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                                    const float *barys, const float *canon_grad, const float *scales,
-                                    const float *rots, float *means3D, float *cov6, d3ga_stream_t stream) {
-    return d3ga_cage_deform_fwd_ex(P, tetpoints, tetras, tetra_id, barys, canon_grad, scales, rots, nullptr, 0, means3D,
-                                   cov6, stream);
-}
-
-extern "C" int d3ga_cage_deform_bwd_ex(int P, int V, const float *tetpoints, const int32_t *tetras,
-                                       const int32_t *tetra_id, const float *barys, const float *canon_grad,
-                                       const float *scales, const float *rots, const float *delta_barys, int32_t flags,
-                                       const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
-                                       float *g_scales, float *g_rots, const int32_t *vert_start,
-                                       const int32_t *vert_items, float *corner_grads, d3ga_stream_t stream) {
-    if (P < 0 || V < 0) return D3GA_E_SIZE;
-    if (flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) return D3GA_E_CONFIG;
-    hipStream_t s = (hipStream_t)stream;
-    const bool csr = g_tetpoints && vert_start && vert_items && corner_grads;
-    if (g_tetpoints && V > 0 && (!csr || P == 0)) D3GA_HIP(zero_async(g_tetpoints, sizeof(float) * 3 * (size_t)V, s));
-    if (P == 0) return D3GA_OK;
-    if (!tetpoints || !tetras || !tetra_id || !barys || !canon_grad || !scales || !rots || !g_means || !g_cov6)
-        return D3GA_E_NULL;
-    hipLaunchKernelGGL(cage_deform_bwd_kernel, dim3(nblocks(P)), dim3(kBlock), 0, s, P, tetpoints, tetras, tetra_id,
-                       barys, canon_grad, scales, rots, delta_barys, (int)flags, g_means, g_cov6, g_tetpoints, g_barys,
-                       g_scales, g_rots, csr ? corner_grads : nullptr, DeformMerge{nullptr, nullptr, nullptr, nullptr});
-    D3GA_TRY(check_launch(s, 0));
-    if (csr && V > 0) {
-        hipLaunchKernelGGL(vertex_gather_kernel, dim3((V + 3) / 4), dim3(kBlock), 0, s, V, vert_start, vert_items,
-                           corner_grads, g_tetpoints);
-        return check_launch(s, 0);
+// One validation, one launch of cage_deform_bwd_kernel, then the vertex gather the route asks for (with the skinning backward in
+// it when `skin` is given) and the by-joint reduction of `pose`.
+extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr,
+                                    const d3ga_cage_deform_route *route, const d3ga_cage_deform_skin *skin,
+                                    const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream) {
+    if (!in || !gr) return D3GA_E_NULL;
+    const int P = in->P, V = in->V;
+    const bool merge = route && route->kind == D3GA_DEFORM_ROUTE_MERGE, corners = route && route->kind == D3GA_DEFORM_ROUTE_CORNERS;
+    if (P < 0 || V < 0 || (merge && route->n_segments < 0) || (skin && skin->K <= 0) || (pose && V == 0)) return D3GA_E_SIZE;
+    if ((in->flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) || (route && !merge && !corners) || (skin && !merge) ||
+        (pose && !skin))
+        return D3GA_E_CONFIG;
+    if (pose) D3GA_TRY(pose_check(V, skin->K, pose));
+    if (skin) {
+        if (!skin->g_delta || !skin->joint_mats || !skin->skin_idx || !skin->skin_w) return D3GA_E_NULL;
+        if (V == 0) return D3GA_OK;
+    } else if (P > 0 && (route != nullptr) != (gr->g_tetpoints != nullptr)) {
+        return D3GA_E_NULL;              // a route needs its output, and g_tetpoints has no other way (no float atomics)
     }
-    return D3GA_OK;
-}
-
-extern "C" int d3ga_cage_deform_bwd_merged(int P, int V, const float *tetpoints, const int32_t *tetras,
-                                           const int32_t *tetra_id, const float *barys, const float *canon_grad,
-                                           const float *scales, const float *rots, const float *delta_barys, int32_t flags,
-                                           const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
-                                           float *g_scales, float *g_rots, const uint16_t *item_pos, const int32_t *seg_ptr,
-                                           const uint16_t *seg_begin, int32_t n_segments, const int32_t *vert_start,
-                                           const int32_t *vert_parts, float *partials, d3ga_stream_t stream) {
-    if (P < 0 || V < 0 || n_segments < 0) return D3GA_E_SIZE;
-    if (flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) return D3GA_E_CONFIG;
-    if (!g_tetpoints) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
+    // the vertex gradient: the caller's g_tetpoints, or (pose) the scratch behind the partials of the reduction
+    float *gv = (pose && !gr->g_tetpoints) ? (float *)pose->scratch + 12 * pose_groups(V, pose->n_chunks) : gr->g_tetpoints;
     if (P == 0) {
-        if (V > 0) D3GA_HIP(zero_async(g_tetpoints, sizeof(float) * 3 * (size_t)V, s));
-        return D3GA_OK;
-    }
-    if (!tetpoints || !tetras || !tetra_id || !barys || !canon_grad || !scales || !rots || !g_means || !g_cov6 || !item_pos ||
-        !seg_ptr || !seg_begin || !vert_start || !vert_parts || !partials)
-        return D3GA_E_NULL;
-    if ((uintptr_t)item_pos & 7) return D3GA_E_CONFIG;                       // read 8 bytes per Gaussian
-    hipLaunchKernelGGL(cage_deform_bwd_kernel, dim3(nblocks(P)), dim3(kBlock), 0, s, P, tetpoints, tetras, tetra_id,
-                       barys, canon_grad, scales, rots, delta_barys, (int)flags, g_means, g_cov6, g_tetpoints, g_barys,
-                       g_scales, g_rots, (float *)nullptr, DeformMerge{item_pos, seg_ptr, seg_begin, partials});
-    D3GA_TRY(check_launch(s, 0));
-    if (V > 0) {
-        if ((int64_t)n_segments <= 24 * (int64_t)V)          // short lists (the usual case): a DPP row per vertex
-            hipLaunchKernelGGL(vertex_gather_row_kernel, dim3((V + kBlock / 16 - 1) / (kBlock / 16)), dim3(kBlock), 0, s, V,
-                               vert_start, vert_parts, (const float *)partials, g_tetpoints);
-        else
-            hipLaunchKernelGGL(vertex_gather_kernel, dim3((V + 3) / 4), dim3(kBlock), 0, s, V, vert_start, vert_parts,
-                               (const float *)partials, g_tetpoints);
-        return check_launch(s, 0);
-    }
-    return D3GA_OK;
-}
-
-extern "C" int d3ga_cage_deform_bwd_merged_lbs(int P, int V, const float *tetpoints, const int32_t *tetras,
-                                               const int32_t *tetra_id, const float *barys, const float *canon_grad,
-                                               const float *scales, const float *rots, const float *delta_barys, int32_t flags,
-                                               const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
-                                               float *g_scales, float *g_rots, const uint16_t *item_pos, const int32_t *seg_ptr,
-                                               const uint16_t *seg_begin, int32_t n_segments, const int32_t *vert_start,
-                                               const int32_t *vert_parts, float *partials, int K, const float *joint_mats,
-                                               const int32_t *skin_idx, const float *skin_w, const float *Rh,
-                                               const float *g_tetpoints_extra, float *g_delta, d3ga_stream_t stream) {
-    if (P < 0 || V < 0 || n_segments < 0 || K <= 0) return D3GA_E_SIZE;
-    if (flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) return D3GA_E_CONFIG;
-    if (!g_delta || !joint_mats || !skin_idx || !skin_w) return D3GA_E_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    if (V == 0) return D3GA_OK;
-    if (P > 0) {
-        if (!tetpoints || !tetras || !tetra_id || !barys || !canon_grad || !scales || !rots || !g_means || !g_cov6 || !item_pos ||
-            !seg_ptr || !seg_begin || !vert_start || !vert_parts || !partials)
+        if (!skin) {
+            if (gv && V > 0) D3GA_HIP(zero_async(gv, sizeof(float) * 3 * (size_t)V, s));
+            return D3GA_OK;
+        }
+        if (!route->vert_start || !route->vert_items) return D3GA_E_NULL;   // (an all-empty CSR is still read)
+    } else {
+        D3GA_TRY(deform_in_check(in));
+        if (!gr->g_means || !gr->g_cov6 || (route && (!route->vert_start || !route->vert_items || !route->records)) ||
+            (merge && (!route->item_pos || !route->seg_ptr || !route->seg_begin)))
             return D3GA_E_NULL;
-        if ((uintptr_t)item_pos & 7) return D3GA_E_CONFIG;                   // read 8 bytes per Gaussian
-        // (g_tetpoints of the corner kernel is unused on the merged path: the partials carry the corner gradients)
-        hipLaunchKernelGGL(cage_deform_bwd_kernel, dim3(nblocks(P)), dim3(kBlock), 0, s, P, tetpoints, tetras, tetra_id,
-                           barys, canon_grad, scales, rots, delta_barys, (int)flags, g_means, g_cov6, g_tetpoints, g_barys,
-                           g_scales, g_rots, (float *)nullptr, DeformMerge{item_pos, seg_ptr, seg_begin, partials});
+        if (merge && ((uintptr_t)route->item_pos & 7)) return D3GA_E_CONFIG;  // read 8 bytes per Gaussian
+        hipLaunchKernelGGL(cage_deform_bwd_kernel, dim3(nblocks(P)), dim3(kBlock), 0, s, P, in->tetpoints, in->tetras, in->tetra_id,
+                           in->barys, in->canon_grad, in->scales, in->rots, in->delta_barys, (int)in->flags, gr->g_means, gr->g_cov6,
+                           gr->g_barys, gr->g_scales, gr->g_rots, corners ? route->records : nullptr,
+                           merge ? DeformMerge{route->item_pos, route->seg_ptr, route->seg_begin, route->records}
+                                 : DeformMerge{nullptr, nullptr, nullptr, nullptr});
         D3GA_TRY(check_launch(s, 0));
-    } else if (!vert_start || !vert_parts) {
-        return D3GA_E_NULL;                                                  // (P == 0: an all-empty CSR is still read)
     }
-    hipLaunchKernelGGL(vertex_gather_lbs_row_kernel, dim3((V + kBlock / 16 - 1) / (kBlock / 16)), dim3(kBlock), 0, s, V, K,
-                       vert_start, vert_parts, (const float *)partials, g_tetpoints_extra, joint_mats, skin_idx, skin_w, Rh,
-                       g_tetpoints, g_delta);
-    return check_launch(s, 0);
-}
-
-extern "C" int d3ga_cage_deform_bwd_merged_lbs_pose(int P, int V, const float *tetpoints, const int32_t *tetras,
-                                                    const int32_t *tetra_id, const float *barys, const float *canon_grad,
-                                                    const float *scales, const float *rots, const float *delta_barys, int32_t flags,
-                                                    const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
-                                                    float *g_scales, float *g_rots, const uint16_t *item_pos, const int32_t *seg_ptr,
-                                                    const uint16_t *seg_begin, int32_t n_segments, const int32_t *vert_start,
-                                                    const int32_t *vert_parts, float *partials, int K, const float *joint_mats,
-                                                    const int32_t *skin_idx, const float *skin_w, const float *Rh,
-                                                    const float *g_tetpoints_extra, float *g_delta, const d3ga_lbs_pose_grad *pose,
-                                                    d3ga_stream_t stream) {
-    if (V <= 0 || K <= 0) return D3GA_E_SIZE;
-    D3GA_TRY(pose_check(V, K, pose));
-    // the vertex gradient g: the caller's g_tetpoints, or the scratch behind the partials
-    float *gv = g_tetpoints ? g_tetpoints : (float *)pose->scratch + 12 * pose_groups(V, pose->n_chunks);
-    D3GA_TRY(d3ga_cage_deform_bwd_merged_lbs(P, V, tetpoints, tetras, tetra_id, barys, canon_grad, scales, rots, delta_barys, flags,
-                                             g_means, g_cov6, gv, g_barys, g_scales, g_rots, item_pos, seg_ptr, seg_begin, n_segments,
-                                             vert_start, vert_parts, partials, K, joint_mats, skin_idx, skin_w, Rh, g_tetpoints_extra,
-                                             g_delta, stream));
-    return pose_reduce(V, K, joint_mats, skin_idx, skin_w, Rh, gv, pose, (hipStream_t)stream);
-}
-
-extern "C" int d3ga_cage_deform_bwd(int P, int V, const float *tetpoints, const int32_t *tetras,
-                                    const int32_t *tetra_id, const float *barys, const float *canon_grad,
-                                    const float *scales, const float *rots, const float *g_means, const float *g_cov6,
-                                    float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
-                                    const int32_t *vert_start, const int32_t *vert_items, float *corner_grads,
-                                    d3ga_stream_t stream) {
-    return d3ga_cage_deform_bwd_ex(P, V, tetpoints, tetras, tetra_id, barys, canon_grad, scales, rots, nullptr, 0, g_means,
-                                   g_cov6, g_tetpoints, g_barys, g_scales, g_rots, vert_start, vert_items, corner_grads,
-                                   stream);
+    if (!route || V == 0) return D3GA_OK;
+    const dim3 rows((V + kBlock / 16 - 1) / (kBlock / 16));
+    if (skin)
+        hipLaunchKernelGGL(vertex_gather_row_kernel<true>, rows, dim3(kBlock), 0, s, V, skin->K, route->vert_start, route->vert_items,
+                           (const float *)route->records, skin->g_tetpoints_extra, skin->joint_mats, skin->skin_idx, skin->skin_w,
+                           skin->Rh, gv, skin->g_delta);
+    else if (merge && (int64_t)route->n_segments <= 24 * (int64_t)V)      // short lists (the usual case): a DPP row per vertex
+        hipLaunchKernelGGL(vertex_gather_row_kernel<false>, rows, dim3(kBlock), 0, s, V, 0, route->vert_start, route->vert_items,
+                           (const float *)route->records, (const float *)nullptr, (const float *)nullptr, (const int32_t *)nullptr,
+                           (const float *)nullptr, (const float *)nullptr, gv, (float *)nullptr);
+    else
+        hipLaunchKernelGGL(vertex_gather_kernel, dim3((V + 3) / 4), dim3(kBlock), 0, s, V, route->vert_start, route->vert_items,
+                           (const float *)route->records, gv);
+    D3GA_TRY(check_launch(s, 0));
+    return pose ? pose_reduce(V, skin->K, skin->joint_mats, skin->skin_idx, skin->skin_w, skin->Rh, gv, pose, s) : D3GA_OK;
 }
 
 extern "C" int d3ga_fem_energy_fwd(int T, const float *tetpoints, const int32_t *tetras, const float *Dn_inv,

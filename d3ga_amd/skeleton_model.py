@@ -33,7 +33,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, dptr, require_cuda, stream_handle
 from .body_model import tree_tables
-from .cage_deform import _i32c, lbs_cage
+from .cage_deform import StorageCache, _i32c, lbs_cage
 
 ROOT_JOINT = 1
 
@@ -538,19 +538,12 @@ def affine_inverse(M):
     return torch.cat([torch.cat([Ai, ti], 2), bottom], 1)
 
 
-_template_cache = {}
+_template_cache = StorageCache(limit=16)
 
 
 def _template_dm(t):
     """lbs_template_verts / 100 (the unit of `delta`), cached by the template's storage."""
-    key = (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
-    hit = _template_cache.get(key)
-    if hit is None:
-        if len(_template_cache) > 16:
-            _template_cache.clear()
-        hit = (t, (t.detach().float() / 100.0).reshape(-1, 3).contiguous())
-        _template_cache[key] = hit
-    return hit[1]
+    return _template_cache.get((t,), None, lambda: (t.detach().float() / 100.0).reshape(-1, 3).contiguous())
 
 
 _rot180_cache = {}

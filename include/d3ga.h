@@ -27,7 +27,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 111 /* per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -68,21 +68,16 @@ int d3ga_debug_defaults(int32_t *out, int32_t n);
  *   tmpl (V,3), delta (V,3)|NULL, joint_mats (J,4,4), skin_idx (V,K) int32, skin_w (V,K),
  *   Rh (3,3)|NULL, Th (3)|NULL  ->  out (V,3).
  * bwd: grad_out (V,3) -> grad_delta (V,3)  (= gradient w.r.t. the template offset / deformation_field output).
- * bwd_pose: the same plus the pose gradients (the body pose reaches the cage through joint_mats, Rh and Th).  With
+ * bwd with pose != NULL: the same plus the pose gradients (the body pose reaches the cage through joint_mats, Rh and Th).  With
  *   p~ = [tmpl + delta; 1], o = (sum_k w_k A[idx_k]) p~, g = grad_out and g' = Rh^T g:
  *     g_joint_mats[j][0:3][0:4] = sum over the (v,k) with idx = j of w_vk g'_v p~_v^T, row 3 = 0 (the forward never reads it);
  *     g_Rh = sum_v g_v o_v^T (3,3);  g_Th = sum_v g_v (3).
  *   A joint listed twice in a row counts twice; a joint with no entry gets exact zeros.  The sums follow a static by-joint
  *   plan (struct d3ga_lbs_pose_grad, built once per binding: d3ga_amd/cage_deform.py lbs_pose_plan) in a fixed order, with no
- *   float atomics: repeated calls are bit-identical.  One launch after d3ga_lbs_cage_bwd's own (which runs unchanged, so
- *   grad_delta is bit-identical to it): a by-joint reduction whose last workgroup forms the totals.  No host synchronisation,
- *   capturable.
+ *   float atomics: repeated calls are bit-identical.  One launch after the per-vertex one (which runs unchanged, so grad_delta
+ *   is bit-identical with and without pose): a by-joint reduction whose last workgroup forms the totals.  No host
+ *   synchronisation, capturable.  pose needs V > 0 (else D3GA_E_SIZE).
  * ------------------------------------------------------------------------------------------------------- */
-int d3ga_lbs_cage_fwd(int V, int K, const float *tmpl, const float *delta, const float *joint_mats,
-                      const int32_t *skin_idx, const float *skin_w, const float *Rh, const float *Th, float *out,
-                      d3ga_stream_t stream);
-int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
-                      const float *Rh, const float *grad_out, float *grad_delta, d3ga_stream_t stream);
 /* The by-joint plan and the outputs of the pose backward.  entries (n_entries = V*K): the flat indices v*K + k of skin_idx
  * sorted by joint (stable); chunk_range (n_chunks, 2; 8-byte aligned): [begin, end) of each chunk of entries, at most 256
  * entries, never straddling a joint; chunk_ptr (J + 1): the first chunk of each joint.  Every skin_idx must lie in [0, J).
@@ -105,91 +100,88 @@ typedef struct d3ga_lbs_pose_grad {
     float *g_Rh;
     float *g_Th;
 } d3ga_lbs_pose_grad;
-/* bytes of scratch for V vertices and n_chunks chunks; fused = 1 for d3ga_cage_deform_bwd_merged_lbs_pose, 0 otherwise */
+/* bytes of scratch for V vertices and n_chunks chunks; fused = 1 for d3ga_cage_deform_bwd, 0 for d3ga_lbs_cage_bwd */
 int d3ga_lbs_pose_scratch_bytes(int V, int32_t n_chunks, int32_t fused, int64_t *bytes);
-int d3ga_lbs_cage_bwd_pose(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
-                           const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
-                           d3ga_stream_t stream);
+int d3ga_lbs_cage_fwd(int V, int K, const float *tmpl, const float *delta, const float *joint_mats,
+                      const int32_t *skin_idx, const float *skin_w, const float *Rh, const float *Th, float *out,
+                      d3ga_stream_t stream);
+int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w,
+                      const float *Rh, const float *grad_out, float *grad_delta, const d3ga_lbs_pose_grad *pose,
+                      d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * D1-D5  Fused tetrahedral-cage deformation.
  * Replaces: models/cage_net.py:218-230 (tetpoints[tetra_faces], compute_def_grad, J S J^T, strip_symmetric,
  *           einsum bary means) with lib/cage.py:339-342 and utils/general_utils.py:24-35,58-90.
- *   tetpoints (V,3) posed cage vertices; tetras (T,4) int32; tetra_id (P) int32; barys (P,4) (= barys+delta_bary);
- *   canon_grad (P,3,3) = inv(Dm) (lib/cage.py:329); scales (P,3) activated; rots (P,4) wxyz (normalised inside)
- *   -> means3D (P,3), cov6 (P,6) in order xx,xy,xz,yy,yz,zz.
- * bwd: g_means (P,3), g_cov6 (P,6) -> g_tetpoints (V,3), g_barys (P,4), g_scales (P,3), g_rots (P,4).  Any of the
- *      four outputs may be NULL (skipped).  The vertex gradient is a scatter-add over 4 corners x P Gaussians:
- *      - with the static adjacency of the cage given -- vert_start (V+1) int32, vert_items (4P) int32 listing, per
- *        vertex, the items 4*gaussian+corner incident to it, plus corner_grads (P,4,3) float scratch -- it is
- *        computed WITHOUT atomics (one wavefront per vertex gathers and sums; deterministic);
- *      - with those three NULL it falls back to float atomics into g_tetpoints (zeroed by the call).
+ * fwd: (inputs) -> means3D (P,3), cov6 (P,6) in order xx,xy,xz,yy,yz,zz.
+ * bwd: (inputs, grads, route | NULL, skin | NULL, pose | NULL).  The vertex gradient is a scatter-add over 4 corners x P
+ *   Gaussians; the route says how it is summed.  Both routes add in a fixed order without float atomics: repeated calls are
+ *   bit-identical.  There is no other way to it (the float-atomic fallback of ABI <= 111 is gone).  Without skin and with
+ *   P > 0, g_tetpoints and route come together: g_tetpoints without a route, and a route without g_tetpoints, both return
+ *   D3GA_E_NULL; with neither, the per-Gaussian gradients alone are computed.
+ *   P == 0 without skin: g_tetpoints | NULL is zeroed, the route is not looked at, nothing is launched.  P == 0 with skin: no
+ *   Gaussian kernel runs, but the gather does, over the route's vert_start / vert_items (all-empty lists; both pointers still non-NULL, else
+ *   D3GA_E_NULL -- d3ga_amd/cage_deform.py hands over the NULL of an empty tensor and is refused so), and
+ *   writes g_delta (from g_tetpoints_extra alone) and the vertex gradient as described at d3ga_cage_deform_skin.
+ *   Status: a NULL inputs / grads struct or a missing required pointer D3GA_E_NULL; a negative size, K <= 0 or pose with
+ *   V == 0 D3GA_E_SIZE; an unknown flag or route kind, a misaligned item_pos, skin without the merge route or pose without
+ *   skin D3GA_E_CONFIG.
  * ------------------------------------------------------------------------------------------------------- */
 #define D3GA_DEFORM_LOG_SCALES 1 /* `scales` holds log-scales: exp() applied inside, g_scales is d/d(log-scale) */
 #define D3GA_DEFORM_GRAD_PER_TET 2 /* `canon_grad` is (T,3,3), one matrix per tetrahedron, read through tetra_id (the reference
                                     * stores the same matrices gathered per Gaussian, lib/cage.py:329: 36 B x P per pass) */
-int d3ga_cage_deform_fwd(int P, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                         const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                         float *means3D, float *cov6, d3ga_stream_t stream);
-int d3ga_cage_deform_bwd(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                         const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                         const float *g_means, const float *g_cov6, float *g_tetpoints, float *g_barys,
-                         float *g_scales, float *g_rots, const int32_t *vert_start, const int32_t *vert_items,
-                         float *corner_grads, d3ga_stream_t stream);
-/* Same ops with the two activations of models/cage_net.py:213-214 fused: delta_barys (P,4) or NULL is added to barys
- * (g_barys is then the gradient of both), and flags & D3GA_DEFORM_LOG_SCALES applies scales = exp(.) on load. */
-int d3ga_cage_deform_fwd_ex(int P, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                            const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                            const float *delta_barys, int32_t flags, float *means3D, float *cov6, d3ga_stream_t stream);
-int d3ga_cage_deform_bwd_ex(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                            const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                            const float *delta_barys, int32_t flags, const float *g_means, const float *g_cov6,
-                            float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
-                            const int32_t *vert_start, const int32_t *vert_items, float *corner_grads,
-                            d3ga_stream_t stream);
-
-/* The same backward with the corner gradients merged per WORKGROUP before they leave the CU (round 4).  The binding
- * (tetras, tetra_id) is static, so a plan is built once (d3ga_amd/cage_deform.py: merge_plan): for every block of 256
- * consecutive Gaussians, item_pos (P,4 u16; 8-byte aligned) = position of item 4 i + corner among the block's items sorted by
- * cage vertex, seg_ptr (blocks + 1) / seg_begin (segments, u16) = the runs of equal vertex, and a second-level CSR
- * vert_start (V + 1) / vert_parts (segments) from vertices to segments.  The kernel sums every run in a fixed order in LDS
- * and writes one partial per run (partials: (segments,3) scratch); the vertex gather then adds a vertex's partials.
- * No atomics, bit-reproducible; with spatially coherent numbering (tetra.spatial_order) a block has a few hundred runs
- * instead of 1024 items.  g_tetpoints is required. */
-int d3ga_cage_deform_bwd_merged(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                                const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                                const float *delta_barys, int32_t flags, const float *g_means, const float *g_cov6,
-                                float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
-                                const uint16_t *item_pos, const int32_t *seg_ptr, const uint16_t *seg_begin,
-                                int32_t n_segments, const int32_t *vert_start, const int32_t *vert_parts, float *partials,
-                                d3ga_stream_t stream);
-
-/* ... with the LBS backward of D0 in the vertex-gather launch (round 5): when the posed cage vertices came from d3ga_lbs_cage_fwd
- * (lib/smplman.py:155-171 feeding models/cage_net.py:218), dL/d(delta) = (sum_k w_k A_k[:3,:3])^T Rh^T dL/d(tetpoint) is formed while
- * the gathered vertex gradient sits in registers: one launch instead of d3ga_cage_deform_bwd_merged's gather + d3ga_lbs_cage_bwd.
- * K, joint_mats, skin_idx, skin_w, Rh: as d3ga_lbs_cage_bwd.  g_tetpoints_extra (V,3) | NULL: a gradient that reaches the posed
- * vertices by another route (the FEM regulariser), added before the skinning.  g_tetpoints (V,3) | NULL: also write the vertex
- * gradient itself.  g_delta (V,3): required. */
-int d3ga_cage_deform_bwd_merged_lbs(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                                    const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                                    const float *delta_barys, int32_t flags, const float *g_means, const float *g_cov6,
-                                    float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
-                                    const uint16_t *item_pos, const int32_t *seg_ptr, const uint16_t *seg_begin,
-                                    int32_t n_segments, const int32_t *vert_start, const int32_t *vert_parts, float *partials,
-                                    int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w, const float *Rh,
-                                    const float *g_tetpoints_extra, float *g_delta, d3ga_stream_t stream);
-/* ... and the pose gradients of D0 (as d3ga_lbs_cage_bwd_pose, with g = the gathered vertex gradient plus g_tetpoints_extra):
- * d3ga_cage_deform_bwd_merged_lbs runs unchanged (its other outputs bit-identical), its vertex gradient kept in g_tetpoints or,
- * when that is NULL, in the scratch; one by-joint reduction launch follows.  V > 0. */
-int d3ga_cage_deform_bwd_merged_lbs_pose(int P, int V, const float *tetpoints, const int32_t *tetras, const int32_t *tetra_id,
-                                         const float *barys, const float *canon_grad, const float *scales, const float *rots,
-                                         const float *delta_barys, int32_t flags, const float *g_means, const float *g_cov6,
-                                         float *g_tetpoints, float *g_barys, float *g_scales, float *g_rots,
-                                         const uint16_t *item_pos, const int32_t *seg_ptr, const uint16_t *seg_begin,
-                                         int32_t n_segments, const int32_t *vert_start, const int32_t *vert_parts, float *partials,
-                                         int K, const float *joint_mats, const int32_t *skin_idx, const float *skin_w, const float *Rh,
-                                         const float *g_tetpoints_extra, float *g_delta, const d3ga_lbs_pose_grad *pose,
-                                         d3ga_stream_t stream);
+/* Inputs.  P Gaussians, V cage vertices (read by the backward only), flags = D3GA_DEFORM_*.  tetpoints (V,3) posed cage
+ * vertices; tetras (T,4) int32; tetra_id (P) int32; barys (P,4); canon_grad (P,3,3) | (T,3,3) = inv(Dm) (lib/cage.py:329);
+ * scales (P,3) activated, or log-scales under D3GA_DEFORM_LOG_SCALES; rots (P,4) wxyz (normalised inside); delta_barys (P,4)
+ * | NULL is added to barys (models/cage_net.py:213-214 fused; g_barys is then the gradient of both). */
+typedef struct d3ga_cage_deform_in {
+    int32_t P, V, flags, reserved;
+    const float *tetpoints;
+    const int32_t *tetras, *tetra_id;
+    const float *barys, *canon_grad, *scales, *rots, *delta_barys;
+} d3ga_cage_deform_in;
+/* Gradients.  In: g_means (P,3), g_cov6 (P,6).  Out, each | NULL (skipped): g_tetpoints (V,3), g_barys (P,4), g_scales (P,3),
+ * g_rots (P,4). */
+typedef struct d3ga_cage_deform_grads {
+    const float *g_means, *g_cov6;
+    float *g_tetpoints, *g_barys, *g_scales, *g_rots;
+} d3ga_cage_deform_grads;
+/* Vertex-gradient route over the static binding (tetras, tetra_id); built once (d3ga_amd/cage_deform.py).
+ * D3GA_DEFORM_ROUTE_CORNERS (vertex_adjacency): the kernel writes its corner gradients to records (P,4,3); vert_start (V+1) /
+ *   vert_items (4P) list, per vertex, the items 4*gaussian + corner incident to it; one wavefront per vertex adds them.
+ *   item_pos, seg_ptr, seg_begin, n_segments are not read.
+ * D3GA_DEFORM_ROUTE_MERGE (merge_plan; round 4): the corner gradients are merged per WORKGROUP before they leave the CU.  For
+ *   every block of 256 consecutive Gaussians, item_pos (P,4 u16; 8-byte aligned) = position of item 4 i + corner among the
+ *   block's items sorted by cage vertex, seg_ptr (blocks + 1) / seg_begin (n_segments, u16) = the runs of equal vertex; the
+ *   kernel sums every run in LDS and writes one partial per run to records (n_segments,3); vert_start (V+1) / vert_items
+ *   (n_segments) list each vertex's partials, which the vertex gather adds.  With spatially coherent numbering
+ *   (tetra.spatial_order) a block has a few hundred runs instead of 1024 items. */
+#define D3GA_DEFORM_ROUTE_CORNERS 1
+#define D3GA_DEFORM_ROUTE_MERGE 2
+typedef struct d3ga_cage_deform_route {
+    int32_t kind, n_segments;
+    const uint16_t *item_pos, *seg_begin;
+    const int32_t *seg_ptr, *vert_start, *vert_items;
+    float *records;
+} d3ga_cage_deform_route;
+/* Skinning tail (round 5; merge route only): the posed cage vertices came from d3ga_lbs_cage_fwd (lib/smplman.py:155-171 feeding
+ * models/cage_net.py:218), so the LBS backward of D0 runs in the vertex-gather launch, on the gathered vertex gradient while
+ * it sits in registers: g_delta (V,3; required) = (sum_k w_k A_k[:3,:3])^T Rh^T dL/d(tetpoint).  K, joint_mats, skin_idx, skin_w,
+ * Rh | NULL: as d3ga_lbs_cage_bwd.  g_tetpoints_extra (V,3) | NULL: a gradient that reaches the posed vertices by another route
+ * (the FEM regulariser), added before the skinning.  g_tetpoints is optional here and V == 0 launches nothing.
+ * With pose (V > 0) one by-joint reduction launch follows, as in d3ga_lbs_cage_bwd, with g = the gathered vertex gradient
+ * plus g_tetpoints_extra, kept in g_tetpoints or, when that is NULL, in pose->scratch; every other output is bit-identical
+ * with and without pose. */
+typedef struct d3ga_cage_deform_skin {
+    int32_t K, reserved;
+    const float *joint_mats;
+    const int32_t *skin_idx;
+    const float *skin_w, *Rh, *g_tetpoints_extra;
+    float *g_delta;
+} d3ga_cage_deform_skin;
+int d3ga_cage_deform_fwd(const d3ga_cage_deform_in *in, float *means3D, float *cov6, d3ga_stream_t stream);
+int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *grads, const d3ga_cage_deform_route *route,
+                         const d3ga_cage_deform_skin *skin, const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream);
 
 /* D6  FEM regulariser (lib/cage.py:349-361): per-tet energy 0.5(det F-1)^2 + 0.5(|F|_F^2-3), F = Ds Dn^-1.
  *   fwd: energy (T).  bwd: g_energy (T) -> g_tetpoints (V,3) [zeroed by the call]. */

@@ -109,6 +109,75 @@ def test_scratch_sizing_and_layout_no_gpu_needed():
     assert L.d3ga_raster_scratch_bytes(1, 10, 10, 1, None) == -1        # D3GA_E_NULL
 
 
+def test_cage_deform_entry_points_refuse_bad_arguments_no_gpu_needed():
+    """The status table of d3ga_cage_deform_{fwd,bwd} and d3ga_lbs_cage_bwd (include/d3ga.h) for the arguments that are refused
+    before any HIP call: every pointer below is a made-up non-NULL address that is never read."""
+    import d3ga_amd
+    from d3ga_amd import _lib
+    L = d3ga_amd.lib()
+    OK, E_NULL, E_SIZE, E_CONFIG = 0, -1, -2, -3
+    p = ctypes.c_void_p(0x1000)
+    ref = lambda st: None if st is None else ctypes.byref(st)
+
+    def inputs(**kw):
+        f = dict(P=4, V=3, flags=0, **{n: p for n, t in _lib.CageDeformIn._fields_ if t is ctypes.c_void_p})
+        f.update(kw)
+        return _lib.CageDeformIn(**f)
+    grads = lambda **kw: _lib.CageDeformGrads(**dict(dict(g_means=p, g_cov6=p, g_barys=p), **kw))
+    merge = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=5, **{n: p for n, t in _lib.CageDeformRoute._fields_ if t is ctypes.c_void_p})
+    corners = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_CORNERS, vert_start=p, vert_items=p, records=p)
+    skin = _lib.CageDeformSkin(K=4, joint_mats=p, skin_idx=p, skin_w=p, g_delta=p)
+    pose = _lib.LbsPoseGrad(J=2, n_chunks=1, n_entries=12, **{n: p for n, t in _lib.LbsPoseGrad._fields_ if t is ctypes.c_void_p})
+    bwd = lambda i, g, r, s, q: L.d3ga_cage_deform_bwd(ref(i), ref(g), ref(r), ref(s), ref(q), None)
+    # a NULL struct
+    assert L.d3ga_cage_deform_fwd(None, p, p, None) == E_NULL
+    assert bwd(None, grads(), None, None, None) == E_NULL and bwd(inputs(), None, None, None, None) == E_NULL
+    # a bad flag
+    assert L.d3ga_cage_deform_fwd(ref(inputs(flags=4)), p, p, None) == E_CONFIG
+    assert bwd(inputs(flags=8), grads(), None, None, None) == E_CONFIG
+    # negative sizes
+    assert L.d3ga_cage_deform_fwd(ref(inputs(P=-1)), p, p, None) == E_SIZE
+    assert bwd(inputs(P=-1), grads(), None, None, None) == E_SIZE
+    assert bwd(inputs(V=-1), grads(g_tetpoints=p), merge, None, None) == E_SIZE
+    assert bwd(inputs(), grads(g_tetpoints=p), _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=-1), None, None) == E_SIZE
+    assert bwd(inputs(), grads(), merge, _lib.CageDeformSkin(K=0, joint_mats=p, skin_idx=p, skin_w=p, g_delta=p), None) == E_SIZE
+    # invalid combinations: a skinning tail needs the merge route, pose needs the skinning tail, an unknown route kind
+    assert bwd(inputs(), grads(g_tetpoints=p), corners, skin, None) == E_CONFIG
+    assert bwd(inputs(), grads(), None, skin, None) == E_CONFIG
+    assert bwd(inputs(), grads(g_tetpoints=p), merge, None, pose) == E_CONFIG
+    assert bwd(inputs(), grads(g_tetpoints=p), _lib.CageDeformRoute(kind=3), None, None) == E_CONFIG
+    # pose with V == 0
+    assert bwd(inputs(V=0), grads(), merge, skin, pose) == E_SIZE
+    assert L.d3ga_lbs_cage_bwd(0, 4, p, p, p, None, p, p, ref(pose), None) == E_SIZE
+    # g_tetpoints without a route (there is no float-atomic fallback), a route without it, missing pointers
+    assert bwd(inputs(), grads(g_tetpoints=p), None, None, None) == E_NULL
+    assert bwd(inputs(), grads(), merge, None, None) == E_NULL
+    assert bwd(inputs(), grads(), merge, _lib.CageDeformSkin(K=4, joint_mats=p, skin_idx=p, skin_w=p), None) == E_NULL
+    assert bwd(inputs(tetras=None), grads(), None, None, None) == E_NULL
+    assert bwd(inputs(), grads(g_means=None), None, None, None) == E_NULL
+    assert bwd(inputs(), grads(g_tetpoints=p), _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_CORNERS, vert_start=p, vert_items=p), None, None) == E_NULL
+    assert L.d3ga_cage_deform_fwd(ref(inputs(rots=None)), p, p, None) == E_NULL
+    assert L.d3ga_cage_deform_fwd(ref(inputs()), p, None, None) == E_NULL
+    # a misaligned item_pos (8 bytes are read per Gaussian)
+    odd = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=5, **{n: ctypes.c_void_p(0x1004) if n == "item_pos" else p
+                                                                               for n, t in _lib.CageDeformRoute._fields_ if t is ctypes.c_void_p})
+    assert bwd(inputs(), grads(g_tetpoints=p), odd, None, None) == E_CONFIG
+    # the pose plan is checked before anything is launched: sizes, pointers, alignment
+    assert bwd(inputs(), grads(), merge, skin, _lib.LbsPoseGrad(J=2, n_chunks=1, n_entries=11)) == E_SIZE      # != V * K
+    assert bwd(inputs(), grads(), merge, skin, _lib.LbsPoseGrad(J=2, n_chunks=1, n_entries=12)) == E_NULL
+    assert L.d3ga_lbs_cage_bwd(3, 4, p, p, p, None, p, p, ref(_lib.LbsPoseGrad(J=0, n_chunks=1, n_entries=12)), None) == E_SIZE
+    assert L.d3ga_lbs_cage_bwd(3, 4, p, p, p, None, p, p, ref(_lib.LbsPoseGrad(J=2, n_chunks=1, n_entries=12)), None) == E_NULL
+    # d3ga_lbs_cage_bwd itself: sizes, V == 0, a missing pointer
+    assert L.d3ga_lbs_cage_bwd(-1, 4, p, p, p, None, p, p, None, None) == E_SIZE
+    assert L.d3ga_lbs_cage_bwd(3, 0, p, p, p, None, p, p, None, None) == E_SIZE
+    assert L.d3ga_lbs_cage_bwd(0, 4, None, None, None, None, None, None, None, None) == OK
+    assert L.d3ga_lbs_cage_bwd(3, 4, p, p, p, None, p, None, None, None) == E_NULL
+    # nothing to do: P == 0 in the forward, and in the backward without a vertex gradient; V == 0 with a skinning tail
+    assert L.d3ga_cage_deform_fwd(ref(inputs(P=0)), None, None, None) == OK
+    assert bwd(inputs(P=0), grads(), None, None, None) == OK
+    assert bwd(inputs(V=0), grads(), merge, skin, None) == OK
+
+
 def test_ops_refuse_cpu_tensors():
     from d3ga_amd import D3GAError
     from d3ga_amd.cage_deform import cage_deform

@@ -149,7 +149,7 @@ def test_new_abi_surface_and_module():
         assert name in _lib.EXPORTS
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert hasattr(_lib.lib(), name)
-    assert _lib.ABI_VERSION == 111 and re.search(r"#define\s+D3GA_VERSION\s+111\b", src)
+    assert _lib.ABI_VERSION == 112 and re.search(r"#define\s+D3GA_VERSION\s+112\b", src)
     assert _lib.BLUR_PARTIALS == int(re.search(r"#define\s+D3GA_BLUR_PARTIALS\s+(\d+)", src).group(1))
     m = LearnableBlur(["a", "b"])
     sd = m.state_dict()

@@ -105,14 +105,43 @@ def test_pose_plan_refuses_out_of_range_indices():
         lbs_pose_plan(torch.zeros(2, 2, dtype=torch.int32), 0)
 
 
+def _header_struct(hdr, name):
+    """(field names, sizeof) of `typedef struct name {...} name;` as the C compiler lays it out: int32 4 bytes, int64 and
+    pointers 8, each aligned to its size, the total to 8."""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
+    names, off = [], 0
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = decl.split(",")                       # `type a, *b`: the `*` belongs to each declarator
+        ctype = first[:re.search(r"\*?\s*\w+$", first).start()].strip()
+        for item in [first[len(ctype):]] + more:
+            size = 8 if ("*" in item or "int64_t" in ctype) else 4
+            assert size == 8 or "int32_t" in ctype, decl
+            off = (off + size - 1) // size * size + size
+            names.append(re.search(r"(\w+)$", item.strip()).group(1))
+    return names, (off + 7) // 8 * 8
+
+
 def test_pose_struct_matches_the_header():
-    """struct d3ga_lbs_pose_grad: the ctypes mirror has the header's fields in order, 8-byte pointers after two int32 and an int64."""
+    """struct d3ga_lbs_pose_grad: the ctypes mirror has the header's fields in order, 8-byte pointers after two int32 and an int64;
+    the descriptor structs of d3ga_cage_deform_{fwd,bwd} are held to the same."""
     with open(os.path.join(ROOT, "include", "d3ga.h")) as f:
         hdr = f.read()
     body = re.search(r"typedef struct d3ga_lbs_pose_grad \{(.*?)\} d3ga_lbs_pose_grad;", hdr, re.S).group(1)
     names = re.findall(r"\*?(\w+);", body)
     assert names == [n for n, _ in _lib.LbsPoseGrad._fields_]
     assert ctypes.sizeof(_lib.LbsPoseGrad) == 16 + 10 * 8
-    for name in ("d3ga_lbs_pose_scratch_bytes", "d3ga_lbs_cage_bwd_pose", "d3ga_cage_deform_bwd_merged_lbs_pose"):
+    assert _header_struct(hdr, "d3ga_lbs_pose_grad") == (names, 16 + 10 * 8)
+    for cname, mirror, size in (("d3ga_cage_deform_in", _lib.CageDeformIn, 16 + 8 * 8), ("d3ga_cage_deform_grads", _lib.CageDeformGrads, 6 * 8),
+                                ("d3ga_cage_deform_route", _lib.CageDeformRoute, 8 + 6 * 8), ("d3ga_cage_deform_skin", _lib.CageDeformSkin, 8 + 6 * 8)):
+        names, sizeof = _header_struct(hdr, cname)
+        assert names == [n for n, _ in mirror._fields_], cname
+        assert ctypes.sizeof(mirror) == sizeof == size, cname
+    for key in ("CORNERS", "MERGE"):
+        assert int(re.search(r"#define\s+D3GA_DEFORM_ROUTE_%s\s+(\d+)" % key, hdr).group(1)) == getattr(_lib, "DEFORM_ROUTE_" + key)
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    for name in ("d3ga_lbs_pose_scratch_bytes", "d3ga_lbs_cage_bwd", "d3ga_cage_deform_fwd", "d3ga_cage_deform_bwd"):
         assert name in _lib.EXPORTS and re.search(r"int " + name + r"\(", hdr)
-    assert np.int32(_lib.ABI_VERSION) == 111
+    for name in ("d3ga_lbs_cage_bwd_pose", "d3ga_cage_deform_fwd_ex", "d3ga_cage_deform_bwd_ex", "d3ga_cage_deform_bwd_merged",
+                 "d3ga_cage_deform_bwd_merged_lbs", "d3ga_cage_deform_bwd_merged_lbs_pose"):
+        assert name not in _lib.EXPORTS and not re.search(r"\b" + name + r"\b", code)
+    assert np.int32(_lib.ABI_VERSION) == 112

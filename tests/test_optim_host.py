@@ -85,7 +85,7 @@ def test_new_abi_surface():
         assert name in _lib.EXPORTS
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert hasattr(_lib.lib(), name)
-    assert _lib.ABI_VERSION == 111 and re.search(r"#define\s+D3GA_VERSION\s+111\b", src)
+    assert _lib.ABI_VERSION == 112 and re.search(r"#define\s+D3GA_VERSION\s+112\b", src)
     assert _lib.OPTIM_CHUNK == int(re.search(r"#define\s+D3GA_OPTIM_CHUNK\s+(\d+)", src).group(1))
     assert _lib.OPTIM_ALIGNED16 == int(re.search(r"#define\s+D3GA_OPTIM_ALIGNED16\s+(\d+)", src).group(1))
     L = _lib.lib()

@@ -314,13 +314,13 @@ def test_setup_paths_in_plain_torch(golden):
 
 def test_header_declares_the_skeleton_entry_points():
     src = open(os.path.join(ROOT, "include", "d3ga.h")).read()
-    assert int(re.search(r"#define\s+D3GA_VERSION\s+(\d+)", src).group(1)) == 111
+    assert int(re.search(r"#define\s+D3GA_VERSION\s+(\d+)", src).group(1)) == 112
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     from d3ga_amd import _lib
     for name in ("d3ga_skeleton_check", "d3ga_skeleton_fwd", "d3ga_skeleton_bwd", "d3ga_skeleton_mats_fwd", "d3ga_skeleton_mats_bwd"):
         assert re.search(r"\b" + name + r"\s*\(", code), name
         assert name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 111
+    assert _lib.ABI_VERSION == 112
     assert int(re.search(r"#define\s+D3GA_SKEL_MAX_JOINTS\s+(\d+)", src).group(1)) == _lib.SKEL_MAX_JOINTS >= 512
     assert int(re.search(r"#define\s+D3GA_SKEL_SAVED_FLOATS\s+(\d+)", src).group(1)) == _lib.SKEL_SAVED_FLOATS
 

@@ -33,11 +33,11 @@ def test_raster_params_mirror_the_header_in_order():
     assert names[-3] == "factor_rows"
 
 
-def test_abi_version_is_111():
+def test_abi_version_is_112():
     from d3ga_amd._lib import ABI_VERSION
-    assert ABI_VERSION == 111
+    assert ABI_VERSION == 112
     ver = int(re.search(r"#define\s+D3GA_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "d3ga.h")).read()).group(1))
-    assert ver == 111
+    assert ver == 112
 
 
 def test_appearance_and_background_shape_rules():
