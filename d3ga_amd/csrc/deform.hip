@@ -521,7 +521,10 @@ extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_ca
             if (gv && V > 0) D3GA_HIP(zero_async(gv, sizeof(float) * 3 * (size_t)V, s));
             return D3GA_OK;
         }
-        if (!route->vert_start || !route->vert_items) return D3GA_E_NULL;   // (an all-empty CSR is still read)
+        // no Gaussian, no segment: the gather reads vert_start (V+1 zeros) alone, vert_items / records may be the NULL of an
+        // empty tensor
+        if (route->n_segments != 0) return D3GA_E_SIZE;
+        if (!route->vert_start) return D3GA_E_NULL;
     } else {
         D3GA_TRY(deform_in_check(in));
         if (!gr->g_means || !gr->g_cov6 || (route && (!route->vert_start || !route->vert_items || !route->records)) ||

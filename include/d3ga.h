@@ -120,9 +120,10 @@ int d3ga_lbs_cage_bwd(int V, int K, const float *joint_mats, const int32_t *skin
  *   P > 0, g_tetpoints and route come together: g_tetpoints without a route, and a route without g_tetpoints, both return
  *   D3GA_E_NULL; with neither, the per-Gaussian gradients alone are computed.
  *   P == 0 without skin: g_tetpoints | NULL is zeroed, the route is not looked at, nothing is launched.  P == 0 with skin: no
- *   Gaussian kernel runs, but the gather does, over the route's vert_start / vert_items (all-empty lists; both pointers still non-NULL, else
- *   D3GA_E_NULL -- d3ga_amd/cage_deform.py hands over the NULL of an empty tensor and is refused so), and
- *   writes g_delta (from g_tetpoints_extra alone) and the vertex gradient as described at d3ga_cage_deform_skin.
+ *   Gaussian kernel runs, but the gather does, over the route's vert_start (V+1 zeros: all-empty lists; required, else
+ *   D3GA_E_NULL), and writes g_delta (from g_tetpoints_extra alone) and the vertex gradient as described at
+ *   d3ga_cage_deform_skin.  n_segments must be 0 then (else D3GA_E_SIZE) and no other pointer of the route is read: vert_items,
+ *   records and the block plan may be NULL, as the pointers of empty tensors are.
  *   Status: a NULL inputs / grads struct or a missing required pointer D3GA_E_NULL; a negative size, K <= 0 or pose with
  *   V == 0 D3GA_E_SIZE; an unknown flag or route kind, a misaligned item_pos, skin without the merge route or pose without
  *   skin D3GA_E_CONFIG.
@@ -155,7 +156,9 @@ typedef struct d3ga_cage_deform_grads {
  *   block's items sorted by cage vertex, seg_ptr (blocks + 1) / seg_begin (n_segments, u16) = the runs of equal vertex; the
  *   kernel sums every run in LDS and writes one partial per run to records (n_segments,3); vert_start (V+1) / vert_items
  *   (n_segments) list each vertex's partials, which the vertex gather adds.  With spatially coherent numbering
- *   (tetra.spatial_order) a block has a few hundred runs instead of 1024 items. */
+ *   (tetra.spatial_order) a block has a few hundred runs instead of 1024 items.
+ *   A binding without Gaussians (P == 0, with the skinning tail) has n_segments == 0 and needs vert_start (V+1 zeros) only:
+ *   vert_items, records, item_pos, seg_ptr and seg_begin may be NULL. */
 #define D3GA_DEFORM_ROUTE_CORNERS 1
 #define D3GA_DEFORM_ROUTE_MERGE 2
 typedef struct d3ga_cage_deform_route {
