@@ -590,6 +590,50 @@ int d3ga_compose_target(int32_t C, int32_t H, int32_t W, const float *image, con
                         float *gt_silhouette, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Per-camera colour calibration of the Goliath configuration (configs/goliath_axe184.yml: use_color_calib),
+ * lib/calibration.py:39-56 (called at models/garment_net.py:265-266):
+ *     (w, b) = corrections[cam][:3], corrections[cam][3:];   out = rgb * w + b   per channel,
+ * the product and the sum rounded separately (bit-equal to the float32 torch expression of lines 48-50); a view whose
+ * camera is identity_idx is copied through unchanged (line 42-43; identity_idx < 0: no such camera).
+ *   rgb, out, grad_out, grad_rgb: k views of n elements, f32, 16-byte aligned (else D3GA_E_CONFIG);
+ *       planar == 0  (k,n,3) interleaved, the layout of pkg["rgb"] (line 50);
+ *       planar == 1  (k,3,n) planes, the reference's image branch with n = H W (line 48).
+ *   corrections, grad_corrections (n_cameras,6) f32; cam: k int32 in DEVICE memory, read when the kernels run and clamped
+ *   to [0, n_cameras).  k >= 1, 3 k <= D3GA_CALIB_PARTIALS / 6, n >= 0, 3 k n <= INT32_MAX, n_cameras >= 1 (else
+ *   D3GA_E_SIZE, nothing launched).  n == 0 is valid: no launch over elements, the element pointers may be NULL, and
+ *   grad_corrections is still written (zeros).
+ *   fwd: one launch.
+ *   bwd: one pass over grad_out (and rgb, with grad_corrections != NULL): grad_rgb = g * w, or g for the identity camera
+ *        (NULL: skipped), and per-workgroup partials of the six sums per view (sum g rgb and sum g per channel) in `partials`
+ *        (>= D3GA_CALIB_PARTIALS floats, contents irrelevant).  A second, one-workgroup launch adds them in index order,
+ *        multiplies by grad_scale (the reference's params.register_hook(... 1e-1) of lines 52-54: the parameter gradient only,
+ *        in training mode only; pass 1 otherwise), adds the views that share a camera in view order and writes the WHOLE
+ *        grad_corrections: zeros in every row whose camera is not in the batch and in the identity camera's row.  No atomics,
+ *        no zero fill, bit-identical from run to run.  grad_corrections == NULL: skipped; rgb and partials may then be NULL.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_CALIB_PARTIALS 12288
+int d3ga_color_calib_fwd(int32_t k, int32_t n, int32_t planar, int32_t n_cameras, int32_t identity_idx, const float *rgb,
+                         const float *corrections, const int32_t *cam, float *out, d3ga_stream_t stream);
+int d3ga_color_calib_bwd(int32_t k, int32_t n, int32_t planar, int32_t n_cameras, int32_t identity_idx, float grad_scale,
+                         const float *rgb, const float *corrections, const int32_t *cam, const float *grad_out,
+                         float *grad_rgb, float *grad_corrections, float *partials, d3ga_stream_t stream);
+/* Per-camera pixel bias (use_pixel_cal), models/color_calib.py:245-258 (added to the prediction at models/trainer.py:128-131):
+ * up = F.interpolate(bias[cam], size=(H,W), mode='bilinear'), i.e. align_corners=False; per axis
+ *     src = max(0, (dst + 0.5) n_in / n_out - 0.5),  i0 = floor(src),  i1 = min(i0 + 1, n_in - 1),  lambda = src - i0,
+ * with src formed as the ratio of integers ((2 dst + 1) n_in - n_out) / (2 n_out): i0 exact, lambda one rounded quotient.
+ *   bias, grad_bias (n_cameras,1,bh,bw) f32 (bh along H); cam: ONE int32 in device memory, clamped to [0, n_cameras).
+ *   fwd: image != NULL: out (C,H,W) = image + up, up broadcast over the channels; image == NULL: out (1,H,W) = up (C is
+ *        ignored beyond the size check).  One launch.
+ *   bwd: grad_out (C,H,W) -> grad_bias[cam] = U_h^T (sum_c grad_out_c) U_w, gathered per low-resolution cell over the
+ *        contiguous range of pixels that touch it (no atomics, bit-identical from run to run); the same launch writes zeros to
+ *        every other camera's map.  dL/dimage is grad_out itself: there is no launch for it.
+ *   All sizes >= 1, C H W and n_cameras bh bw <= INT32_MAX, H bh and W bw < 2^30 (else D3GA_E_SIZE, nothing launched). */
+int d3ga_pixel_bias_fwd(int32_t C, int32_t H, int32_t W, int32_t n_cameras, int32_t bh, int32_t bw, const float *bias,
+                        const int32_t *cam, const float *image, float *out, d3ga_stream_t stream);
+int d3ga_pixel_bias_bwd(int32_t C, int32_t H, int32_t W, int32_t n_cameras, int32_t bh, int32_t bw, const int32_t *cam,
+                        const float *grad_out, float *grad_bias, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
  * parameter in THREE launches whatever the number of tensors (two with clipping off).  The tensors are described by tables
  * that the caller builds once per set of addresses, in device memory or in pinned host memory mapped to the device (read by

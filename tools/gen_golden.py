@@ -23,6 +23,9 @@ called as they are:
               gaussian_blur bound to tests/image_tail_ref.py (only with the argument `blur`, or a full run) -> blur_cases.npz
   G11 skeleton  lbsmodel.body_model.LBSModule on a synthetic rig: parameter transform, skeleton solve, joint matrices, skinning,
               root transform, autograd gradients (only with the argument `skeleton`)   -> skeleton_cases.npz
+  G12 calib   lib.calibration.CameraCalibration (training mode: both branches, identity and non-identity camera) and
+              models.color_calib.CameraPixelBias, outputs and autograd gradients (only with the argument `calib`, or a full run)
+              -> calib_cases.npz
 The only stand-in with numerical content besides that blur is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
@@ -611,6 +614,53 @@ def gen_blur(lb_mod):
     np.savez(os.path.join(OUT, "blur_cases.npz"), **out)
 
 
+def gen_calib(cal_mod, cc_mod):
+    """G12: lib.calibration.CameraCalibration and models.color_calib.CameraPixelBias as they are, float64, in TRAINING mode
+    (the register_hook of lib/calibration.py:52-54 fires), with autograd gradients for a fixed upstream gradient: the (P,3)
+    branch and the (3,H,W) branch, each for a non-identity and for the identity camera (whose `corrections` gradient autograd
+    reports as None: recorded as a flag); the pixel bias with a seeded-noise parameter, its upsampled maps for two indices and
+    the parameter gradient.  Arrays only, plus the state_dict key names and shapes of both modules."""
+    g = torch.Generator().manual_seed(53)
+    names = ["cam_a", "cam_b", "cam_c", "cam_d"]
+    P, H, W = 301, 40, 24
+    out = {"names": np.array(names), "identity_camera": np.array("cam_b")}
+    cases = [("pts", (P, 3), "cam_c"), ("pts", (P, 3), "cam_b"), ("img", (3, H, W), "cam_d"), ("img", (3, H, W), "cam_b"),
+             ("pts", (P, 3), "cam_a")]
+    out["n"] = np.array(len(cases))
+    for i, (kind, shape, cam) in enumerate(cases):
+        m = cal_mod.CameraCalibration(names, "cam_b")
+        m.corrections = torch.nn.Parameter(torch.cat([1.0 + 0.2 * torch.randn(len(names), 3, generator=g, dtype=torch.float64),
+                                                      0.1 * torch.randn(len(names), 3, generator=g, dtype=torch.float64)], 1))
+        m.train()
+        x = torch.rand(*shape, generator=g, dtype=torch.float64).requires_grad_(True)
+        up = torch.randn(*shape, generator=g, dtype=torch.float64)
+        res = m(x, cam)
+        g_x, g_c = torch.autograd.grad(res, [x, m.corrections], up, allow_unused=True)
+        out.update({f"kind{i}": np.array(kind), f"cam{i}": np.array(cam), f"x{i}": x.detach().numpy(),
+                    f"corr{i}": m.corrections.detach().numpy(), f"up{i}": up.numpy(), f"out{i}": res.detach().numpy(),
+                    f"g_x{i}": g_x.numpy(), f"g_corr_none{i}": np.array(g_c is None),
+                    f"g_corr{i}": (torch.zeros_like(m.corrections) if g_c is None else g_c).numpy()})
+    m = cal_mod.CameraCalibration(names)                     # constructor defaults
+    out["calib_state_keys"] = np.array(list(m.state_dict().keys()))
+    out["calib_state_shape"] = np.array(m.state_dict()["corrections"].shape)
+    out["calib_default_identity"] = np.array(m.identity_camera)
+    out["calib_init"] = m.corrections.detach().numpy().astype(np.float64)
+    # pixel bias: image 40 x 24, ds_rate 8 -> parameter (4,1,24 // 8,40 // 8) = (4,1,3,5), the reference's swapped sizes
+    pb = cc_mod.CameraPixelBias(H, W, 8, names).double()
+    out["bias_state_keys"] = np.array(list(pb.state_dict().keys()))
+    out["bias_init_shape"] = np.array(pb.bias.shape)
+    assert not pb.bias.detach().any()
+    with torch.no_grad():
+        pb.bias.copy_(torch.randn(pb.bias.shape, generator=g, dtype=torch.float64))
+    idxs = torch.tensor([2, 0])
+    res = pb(idxs)
+    up = torch.randn(res.shape, generator=g, dtype=torch.float64)
+    (g_b,) = torch.autograd.grad(res, [pb.bias], up)
+    out.update({"bias": pb.bias.detach().numpy(), "bias_idxs": idxs.numpy(), "bias_up": res.detach().numpy(), "bias_gout": up.numpy(),
+                "bias_grad": g_b.numpy(), "bias_hw": np.array([H, W]), "bias_ds_rate": np.array(8)})
+    np.savez(os.path.join(OUT, "calib_cases.npz"), **out)
+
+
 def gen_skeleton(bm):
     """lbsmodel/body_model.py on a small synthetic rig of our own (tests/goliath_ref.py: random_rig, rig_json): 24 joints in a
     random parent-first tree, a sparse parameter transform (10 pose + 4 scale parameters), pre-rotations of which two have norm
@@ -674,6 +724,11 @@ def main():
         import models.learnable_blur as lb_mod
         gen_blur(lb_mod)
         return
+    if sys.argv[1:] == ["calib"]:               # one section only (the other fixtures are left untouched)
+        import lib.calibration as cal_mod
+        import models.color_calib as cc_mod
+        gen_calib(cal_mod, cc_mod)
+        return
     import models.cage_net as cn
     from lib.cage import CageBase
     import lib.cameras as cameras_mod
@@ -709,6 +764,9 @@ def main():
     gen_lbs_goliath(bm)
     import models.learnable_blur as lb_mod
     gen_blur(lb_mod)
+    import lib.calibration as cal_mod
+    import models.color_calib as cc_mod
+    gen_calib(cal_mod, cc_mod)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
