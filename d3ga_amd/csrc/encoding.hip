@@ -155,8 +155,10 @@ __global__ __launch_bounds__(kBlock) void field_heads_bwd_kernel(int P, int N, H
     if (g) {                                               // a head nobody used has no gradient
         d = g[o];
         const float y = out[(size_t)P * hs.start[h] + o], a = hs.a[h];
-        if (hs.act[h] == 1) d *= a - y * y / a;            // d/dx a tanh(x) = a (1 - tanh^2)
-        else if (hs.act[h] == 2) d *= y * (1.0f - y);
+        if (hs.act[h] == 1) {                              // d/dx a tanh(x) = a (1 - tanh^2), tanh = y / a: |t| <= 1, so the slope
+            const float t = y / a;                         // keeps a's sign (a - y * y / a rounds through zero at saturation)
+            d *= a * fmaxf(1.0f - t * t, 0.0f);
+        } else if (hs.act[h] == 2) d *= y * (1.0f - y);
     }
     d_pred[i] = d;
 }

@@ -536,7 +536,8 @@ class _Sh4Encoding(torch.autograd.Function):
         d = f32c16(d)
         P = d.shape[0]
         enc = torch.empty((P, 16), dtype=torch.float32, device=d.device)
-        check(_lib.lib().d3ga_sh4_encoding_fwd(P, dptr(d), dptr(enc), stream_handle()), "d3ga_sh4_encoding_fwd")
+        if P:                                                  # (the entry points of encoding.hip refuse P == 0: an empty set launches nothing)
+            check(_lib.lib().d3ga_sh4_encoding_fwd(P, dptr(d), dptr(enc), stream_handle()), "d3ga_sh4_encoding_fwd")
         ctx.save_for_backward(d)
         return enc
 
@@ -544,8 +545,9 @@ class _Sh4Encoding(torch.autograd.Function):
     def backward(ctx, g):
         (d,) = ctx.saved_tensors
         gd = torch.empty_like(d)
-        check(_lib.lib().d3ga_sh4_encoding_bwd(d.shape[0], dptr(d), dptr(f32c16(g)), dptr(gd), stream_handle()),
-              "d3ga_sh4_encoding_bwd")
+        if d.shape[0]:
+            check(_lib.lib().d3ga_sh4_encoding_bwd(d.shape[0], dptr(d), dptr(f32c16(g)), dptr(gd), stream_handle()),
+                  "d3ga_sh4_encoding_bwd")
         return gd
 
 
@@ -560,7 +562,8 @@ class _ColorRows(torch.autograd.Function):
         d, feats = f32c16(d), f32c16(feats)
         P, F_ = feats.shape
         x = torch.empty((P, 16 + F_), dtype=torch.float32, device=d.device)
-        check(_lib.lib().d3ga_color_rows_fwd(P, F_, dptr(d), dptr(feats), dptr(x), stream_handle()), "d3ga_color_rows_fwd")
+        if P:
+            check(_lib.lib().d3ga_color_rows_fwd(P, F_, dptr(d), dptr(feats), dptr(x), stream_handle()), "d3ga_color_rows_fwd")
         ctx.save_for_backward(d)
         ctx.n_feat = F_
         return x
@@ -571,7 +574,8 @@ class _ColorRows(torch.autograd.Function):
         P, F_ = d.shape[0], ctx.n_feat
         gd = torch.empty_like(d) if ctx.needs_input_grad[0] else None
         gf = torch.empty((P, F_), dtype=torch.float32, device=d.device) if ctx.needs_input_grad[1] else None
-        check(_lib.lib().d3ga_color_rows_bwd(P, F_, dptr(d), dptr(f32c16(g)), dptr(gd), dptr(gf), stream_handle()), "d3ga_color_rows_bwd")
+        if P:
+            check(_lib.lib().d3ga_color_rows_bwd(P, F_, dptr(d), dptr(f32c16(g)), dptr(gd), dptr(gf), stream_handle()), "d3ga_color_rows_bwd")
         return gd, gf
 
 
@@ -591,8 +595,9 @@ class _ViewDirs(torch.autograd.Function):
         require_cuda(means3D, campos)
         means3D, campos = means3D.float().contiguous(), campos.float().contiguous()
         v = torch.empty_like(means3D)
-        check(_lib.lib().d3ga_view_dirs_fwd(means3D.shape[0], dptr(means3D), dptr(campos), dptr(v), stream_handle()),
-              "d3ga_view_dirs_fwd")
+        if means3D.shape[0]:
+            check(_lib.lib().d3ga_view_dirs_fwd(means3D.shape[0], dptr(means3D), dptr(campos), dptr(v), stream_handle()),
+                  "d3ga_view_dirs_fwd")
         ctx.save_for_backward(means3D, campos)
         return v
 
@@ -600,8 +605,9 @@ class _ViewDirs(torch.autograd.Function):
     def backward(ctx, g):
         means3D, campos = ctx.saved_tensors
         gm = torch.empty_like(means3D)
-        check(_lib.lib().d3ga_view_dirs_bwd(means3D.shape[0], dptr(means3D), dptr(campos), dptr(g.float().contiguous()),
-                                            dptr(gm), stream_handle()), "d3ga_view_dirs_bwd")
+        if means3D.shape[0]:
+            check(_lib.lib().d3ga_view_dirs_bwd(means3D.shape[0], dptr(means3D), dptr(campos), dptr(g.float().contiguous()),
+                                                dptr(gm), stream_handle()), "d3ga_view_dirs_bwd")
         return gm, None
 
 
@@ -625,7 +631,7 @@ class ColorField(FieldMLP):
 
     def forward(self, shs, pose, view_dir, frame_encoding=None, camera_encoding=None, shadow=None):
         if (shadow is None and self.direction_encoding is sh4_direction_encoding and shs.dim() == 2 and shs.shape[1] % 4 == 0
-                and shs.shape[0] > 0 and view_dir.dim() == 2 and view_dir.shape[1] == 3):
+                and view_dir.dim() == 2 and view_dir.shape[1] == 3):
             # the two per-row groups (first and last columns of z) as one buffer, written in one pass; same layout as below
             bcs = [t.reshape(-1) for t in (pose, camera_encoding, frame_encoding) if t is not None]
             sig = [(False, 16)] + [(True, t.numel()) for t in bcs] + [(False, shs.shape[1])]

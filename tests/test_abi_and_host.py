@@ -536,3 +536,38 @@ def test_bench_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path, mon
     small = {"loss": torch.tensor(0.5), "grad_features": torch.randn(10, 16, 3, generator=g)}
     bench.dump_outputs(str(tmp_path / "small"), small, 10)
     assert sorted(os.listdir(tmp_path / "small")) == ["grad_features.npy", "loss.npy"]
+
+
+def test_field_glue_entry_points_refuse_bad_arguments_no_gpu_needed():
+    """The status table of d3ga_field_heads_{fwd,bwd} and the alignment / size refusals of d3ga_color_rows_* and
+    d3ga_sh4_encoding_* (tests/field_ref.py), all decided before any HIP call: every pointer is a made-up address that is never
+    read.  tests/test_gpu_field_glue.py runs the same table on device buffers and checks that they are left untouched."""
+    import d3ga_amd
+    import field_ref
+    codes = field_ref.status_codes(open(os.path.join(ROOT, "include", "d3ga.h")).read())
+    assert {"OK", "E_NULL", "E_SIZE", "E_CONFIG"} <= set(codes) and codes["OK"] == 0 and len(set(codes.values())) == len(codes)
+    L = d3ga_amd.lib()
+    field_ref.check_heads_refusals(L, codes, pred=0x1000, out=0x2000, g=0x3000, d_pred=0x4000)
+    field_ref.check_encoding_refusals(L, codes, dirs=0x1000, feats=0x2000, x=0x3000, enc=0x4000, d_dirs=0x5000, d_feats=0x6000)
+
+
+def test_field_ref_closed_forms_agree_with_autograd():
+    """tests/field_ref.py against torch autograd in float64: the slopes a (1 - tanh^2), s (1 - s) and 1 of the heads, and the
+    view directions' Jacobian (I - v v^T) / r applied to an upstream gradient."""
+    import field_ref
+    g = torch.Generator().manual_seed(11)
+    spec = ((2, "none", 0.0), (5, "sigmoid", 0.3), (1, "tanh", -0.5), (3, "tanh", 1e-3))
+    pred = (4.0 * torch.randn(37, 11, generator=g, dtype=torch.float64)).requires_grad_(True)
+    ups = [torch.randn(37, w, generator=g, dtype=torch.float64) for w, _, _ in spec]
+    out = field_ref.heads(pred, spec)
+    assert [tuple(o.shape) for o in out] == [(37, w) for w, _, _ in spec]
+    torch.autograd.backward(out, ups)
+    torch.testing.assert_close(pred.grad, field_ref.heads_slope(pred.detach(), spec) * torch.cat(ups, dim=1), rtol=1e-12, atol=1e-14)   # (1 - tanh^2 cancels: absolute)
+    with pytest.raises(ValueError):
+        field_ref.heads(pred, spec[:3])
+    means = torch.randn(50, 3, generator=g, dtype=torch.float64).requires_grad_(True)
+    cam, up = torch.tensor([0.3, -0.2, 4.0], dtype=torch.float64), torch.randn(50, 3, generator=g, dtype=torch.float64)
+    v = field_ref.view_dirs(means, cam)
+    torch.testing.assert_close(torch.linalg.norm(v, dim=-1), torch.ones(50, dtype=torch.float64), rtol=1e-14, atol=0)
+    v.backward(up)
+    torch.testing.assert_close(means.grad, field_ref.view_dirs_vjp(means.detach(), cam, up), rtol=1e-10, atol=1e-14)
