@@ -18,6 +18,8 @@ CAMERA_SLOT_WINDOWED = -1.0    # D3GA_CAMERA_SLOT_WINDOWED (include/d3ga.h): tan
 LOSS_PARTIALS = 2048     # D3GA_LOSS_PARTIALS (include/d3ga.h): floats of scratch behind a two-stage loss reduction
 BLUR_PARTIALS = 6144     # D3GA_BLUR_PARTIALS (include/d3ga.h): floats of scratch behind d3ga_blur_mix_bwd's three sums
 CALIB_PARTIALS = 12288   # D3GA_CALIB_PARTIALS (include/d3ga.h): floats of scratch behind d3ga_color_calib_bwd's six sums per view
+# D3GA_FRAME_* (include/d3ga.h): flags of d3ga_frame_prep
+FRAME_GAMMA, FRAME_BG_WHITE, FRAME_ERODE_MASK, FRAME_CLOSE_HOLES, FRAME_IMAGE_U8, FRAME_SEG_F32 = 1, 2, 4, 8, 16, 32
 OPTIM_CHUNK = 8192      # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
 OPTIM_ALIGNED16 = 1      # D3GA_OPTIM_ALIGNED16: flag of a chunk whose four pointers are 16-byte aligned
 
@@ -186,6 +188,7 @@ _SIGNATURES = {
     "d3ga_color_calib_bwd": ([ctypes.c_int32] * 5 + [_f] + [_vp] * 7 + [_vp], _i),
     "d3ga_pixel_bias_fwd": ([ctypes.c_int32] * 6 + [_vp] * 4 + [_vp], _i),
     "d3ga_pixel_bias_bwd": ([ctypes.c_int32] * 6 + [_vp] * 3 + [_vp], _i),
+    "d3ga_frame_prep": ([ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_int32] + [_vp] * 5 + [_vp], _i),
     "d3ga_optim_scratch_bytes":([ctypes.c_int32] * 3 + [ctypes.POINTER(_i64)], _i),
     "d3ga_optim_clip_adam_step": ([_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp], _i),
     "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),

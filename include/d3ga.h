@@ -634,6 +634,39 @@ int d3ga_pixel_bias_bwd(int32_t C, int32_t H, int32_t W, int32_t n_cameras, int3
                         const float *grad_out, float *grad_bias, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Frame preparation: the image path of Batcher.process (lib/batch.py:150-163, 180, 205-208, 236), one launch for B frames.
+ * Per pixel, with s = int(seg_part) and fg = (s > 0) | (seg_fg > 0):
+ *   orig        v / 255; with D3GA_FRAME_GAMMA linear2color_corr of it (utils/image_utils.py:92-113):
+ *                   x = v / 255 * scale_c / 1.1,   clamp(sqrt(k clamp(x - black, 0, 2)) - 15/255, 0, 2)
+ *               scale = (1.4, 1.1, 1.6), black = 3/255, k = float32((1 / (1 - black)) 0.95 in double); every operation
+ *               rounded to float32 on its own, in this order, divide and square root correctly rounded;
+ *   image       fg ? orig : bg, bg = 1 with D3GA_FRAME_BG_WHITE, else 0  (= orig fg + (1 - fg) resp. orig fg, fg being 0 or 1);
+ *   silhouette  s == 0: bg in all three channels; 0 < s < n_labels: label_rgb[s]; every other s (negative ones too): other_rgb;
+ *   alpha       1 iff at least 25 of the 49 pixels of the 7x7 window around the pixel are fg, pixels outside the image
+ *               counting as 0 (kornia's median_blur of a 0 / 1 image: zero padding, the 25th smallest of 49); then with
+ *               D3GA_FRAME_ERODE_MASK a 7x7 dilation and a 5x5 erosion, then with D3GA_FRAME_CLOSE_HOLES a 5x5 dilation and
+ *               a 5x5 erosion (utils/image_utils.py:49-70), both over the in-image part of the window (kornia's geodesic
+ *               border): dilation = some 1 in it, erosion = no 0 in it.
+ *   image     (B,3,H,W) f32, or uint8 with D3GA_FRAME_IMAGE_U8;  seg_part (B,1,H,W) int32, or f32 with D3GA_FRAME_SEG_F32
+ *   (truncated toward zero, as .int());  seg_fg (B,1,H,W) f32 or NULL (= zeros);  label_rgb (n_labels,3) f32, row 0 unused;
+ *   other_rgb (3) f32;  image_out, orig_out, sil_out (B,3,H,W), alpha_out (B,1,H,W) f32: each may be NULL (skipped; without
+ *   alpha_out no stage runs).  H and W may be smaller than any window.
+ *   Status, nothing launched: B, H, W <= 0, n_labels < 1, B > 65535 or H W > INT32_MAX D3GA_E_SIZE; an unknown flag, or image /
+ *   an output not 16-byte aligned D3GA_E_CONFIG; image, seg_part, label_rgb or other_rgb NULL, or every output NULL D3GA_E_NULL.
+ *   No scratch, no atomics; capturable.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_FRAME_GAMMA 1
+#define D3GA_FRAME_BG_WHITE 2
+#define D3GA_FRAME_ERODE_MASK 4
+#define D3GA_FRAME_CLOSE_HOLES 8
+#define D3GA_FRAME_IMAGE_U8 16
+#define D3GA_FRAME_SEG_F32 32
+#define D3GA_FRAME_ALL 63
+int d3ga_frame_prep(int32_t B, int32_t H, int32_t W, int32_t flags, const void *image, const void *seg_part,
+                    const float *seg_fg, const float *label_rgb, int32_t n_labels, const float *other_rgb, float *image_out,
+                    float *orig_out, float *alpha_out, float *sil_out, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
  * parameter in THREE launches whatever the number of tensors (two with clipping off).  The tensors are described by tables
  * that the caller builds once per set of addresses, in device memory or in pinned host memory mapped to the device (read by

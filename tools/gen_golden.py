@@ -26,6 +26,10 @@ called as they are:
   G12 calib   lib.calibration.CameraCalibration (training mode: both branches, identity and non-identity camera) and
               models.color_calib.CameraPixelBias, outputs and autograd gradients (only with the argument `calib`, or a full run)
               -> calib_cases.npz
+  G13 frames  utils.image_utils.linear2color_corr on an image whose values cover 0..255 and lib.batch.Batcher.get_silhouette
+              (unbound Batcher: object.__new__ plus config and bg_color) for five cage sets and both backgrounds (only with the
+              argument `frames`, or a full run).  kornia is not vendored: the median and the morphology of Batcher.process have
+              NO reference-held pin (tests/frame_ref.py restates them)                       -> frame_cases.npz
 The only stand-in with numerical content besides that blur is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
@@ -661,6 +665,39 @@ def gen_calib(cal_mod, cc_mod):
     np.savez(os.path.join(OUT, "calib_cases.npz"), **out)
 
 
+FRAME_CAGE_SETS = {                                          # name -> {cage: label_id}
+    "body": {"body": [1]},
+    "body_face": {"body": [1], "face": [3, 9]},
+    "goliath": {"body": [1], "upper": [27], "lower": [16]},
+    "shared": {"upper": [4, 5], "lower": [5, 6], "face": [6, -1, 2]},
+    "absent": {"body": [1], "upper": [2], "lower": [-1], "face": [7]},
+}
+
+
+def gen_frames(iu, batch_mod):
+    """G13: the two parts of Batcher.process's image path that the reference itself holds.
+    `linear2color_corr(img / 255.0, dim=0)` (lib/batch.py:86) on a float64 (3,24,40) image whose values cover 0..255 -- every
+    integer once per channel at least, the integers 0..8 (where the black clamp bites) in each channel, and fractions between
+    them.  `Batcher.get_silhouette` on a (1,20,31) label map holding every label 0..30 for the five cage sets of
+    FRAME_CAGE_SETS, white and black.  The median filter and the morphology (kornia, not vendored) are NOT recorded: they have
+    no reference-held pin."""
+    rng = np.random.default_rng(61)
+    vals = np.concatenate([np.arange(256.0), np.arange(9.0), np.arange(9.0) + 0.5, rng.uniform(0.0, 255.0, 960 - 256 - 18)])
+    img = np.stack([rng.permutation(vals) for _ in range(3)]).reshape(3, 24, 40)
+    out = {"color_in": img, "color_out": iu.linear2color_corr(torch.from_numpy(img) / 255.0, dim=0).numpy()}
+    seg = np.concatenate([np.arange(31), rng.integers(0, 31, 20 * 31 - 31)]).reshape(1, 20, 31).astype(np.int32)
+    out["sil_seg"] = seg
+    out["sil_sets"] = np.array(list(FRAME_CAGE_SETS))
+    for name, cages in FRAME_CAGE_SETS.items():
+        for bg in ("white", "black"):
+            b = object.__new__(batch_mod.Batcher)
+            b.config = SimpleNamespace(cages={k: SimpleNamespace(label_id=list(v)) for k, v in cages.items()})
+            b.bg_color = bg
+            out[f"sil_{name}_{bg}"] = b.get_silhouette(torch.from_numpy(seg)).numpy().astype(np.float64)
+        out[f"cages_{name}"] = np.array([f"{k}:{','.join(map(str, v))}" for k, v in cages.items()])
+    np.savez_compressed(os.path.join(OUT, "frame_cases.npz"), **out)
+
+
 def gen_skeleton(bm):
     """lbsmodel/body_model.py on a small synthetic rig of our own (tests/goliath_ref.py: random_rig, rig_json): 24 joints in a
     random parent-first tree, a sparse parameter transform (10 pose + 4 scale parameters), pre-rotations of which two have norm
@@ -729,6 +766,11 @@ def main():
         import models.color_calib as cc_mod
         gen_calib(cal_mod, cc_mod)
         return
+    if sys.argv[1:] == ["frames"]:              # one section only (the other fixtures are left untouched)
+        import utils.image_utils as iu
+        import lib.batch as batch_mod
+        gen_frames(iu, batch_mod)
+        return
     import models.cage_net as cn
     from lib.cage import CageBase
     import lib.cameras as cameras_mod
@@ -767,6 +809,9 @@ def main():
     import lib.calibration as cal_mod
     import models.color_calib as cc_mod
     gen_calib(cal_mod, cc_mod)
+    import utils.image_utils as iu
+    import lib.batch as batch_mod
+    gen_frames(iu, batch_mod)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
