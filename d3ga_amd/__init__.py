@@ -4,5 +4,6 @@ Python host layer over libd3ga_hip.so (hand-written gfx950 HIP kernels behind th
 There is NO CPU fallback: every op raises if the library is missing or the tensors are not on the GPU.
 """
 from ._lib import D3GAError, lib, library_path  # noqa: F401
+from .evaluation import Evaluator, compute_errors, compute_heatmap, error_heatmap, psnr  # noqa: F401
 
-__all__ = ["D3GAError", "lib", "library_path"]
+__all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr"]

@@ -20,6 +20,9 @@ BLUR_PARTIALS = 6144     # D3GA_BLUR_PARTIALS (include/d3ga.h): floats of scratc
 CALIB_PARTIALS = 12288   # D3GA_CALIB_PARTIALS (include/d3ga.h): floats of scratch behind d3ga_color_calib_bwd's six sums per view
 # D3GA_FRAME_* (include/d3ga.h): flags of d3ga_frame_prep
 FRAME_GAMMA, FRAME_BG_WHITE, FRAME_ERODE_MASK, FRAME_CLOSE_HOLES, FRAME_IMAGE_U8, FRAME_SEG_F32 = 1, 2, 4, 8, 16, 32
+# D3GA_EVAL_* (include/d3ga.h): flags of d3ga_eval_frames
+EVAL_BG_WHITE, EVAL_COMPOSED, EVAL_ALPHA3, EVAL_BOUNDARY_F32 = 1, 2, 4, 8
+EVAL_MAX_PARTIALS = 2048  # D3GA_EVAL_MAX_PARTIALS: d3ga_eval_partials(H, W) never exceeds it
 OPTIM_CHUNK = 8192      # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
 OPTIM_ALIGNED16 = 1      # D3GA_OPTIM_ALIGNED16: flag of a chunk whose four pointers are 16-byte aligned
 
@@ -189,6 +192,12 @@ _SIGNATURES = {
     "d3ga_pixel_bias_fwd": ([ctypes.c_int32] * 6 + [_vp] * 4 + [_vp], _i),
     "d3ga_pixel_bias_bwd": ([ctypes.c_int32] * 6 + [_vp] * 3 + [_vp], _i),
     "d3ga_frame_prep": ([ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_int32] + [_vp] * 5 + [_vp], _i),
+    "d3ga_eval_frames": ([ctypes.c_int32] * 4 + [_vp] * 8 + [_vp], _i),
+    "d3ga_eval_finish": ([ctypes.c_int32] * 3 + [_vp] * 5 + [_vp], _i),
+    "d3ga_eval_ssim": ([ctypes.c_int32] * 3 + [_vp] * 3 + [_vp], _i),
+    "d3ga_eval_partials": ([ctypes.c_int32] * 2, _i64),
+    "d3ga_eval_ssim_partials": ([ctypes.c_int32] * 2, _i64),
+    "d3ga_eval_jet_table": ([_vp], _i),
     "d3ga_optim_scratch_bytes":([ctypes.c_int32] * 3 + [ctypes.POINTER(_i64)], _i),
     "d3ga_optim_clip_adam_step": ([_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp], _i),
     "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),

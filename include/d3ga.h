@@ -667,6 +667,60 @@ int d3ga_frame_prep(int32_t B, int32_t H, int32_t W, int32_t flags, const void *
                     float *orig_out, float *alpha_out, float *sil_out, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Evaluation tail: what test.py does per frame between trainer.fit and the PNG writers (and train.py's progress report in
+ * miniature), for B frames, in three launches.  No gradient.
+ * d3ga_eval_frames, per pixel, every operation rounded to float32 on its own:
+ *   a            alpha[0] (1 - float(boundary_fg))                                         test.py:140-141
+ *   target       image a + (1 - a) bg,  bg = 1 with D3GA_EVAL_BG_WHITE, else 0             test.py:151
+ *   ground_truth [image a, a], four channels                                               test.py:186-187
+ *   heat         jet[bin],  e = sqrt(sum_c (target_c - pred_c)^2),  bin = min(int(min(e, 1) 256), 255), a NaN e: row 256;
+ *                jet: matplotlib's 256-entry "jet" table times 255 truncated to uint8, divided by 255 in float32, plus the
+ *                "bad" colour (0, 0, 0) as row 256                                          recorder/heatmap.py:16-34, 45-47
+ *   partials     sum of (target_c - pred_c)^2 over the workgroup's pixels: d3ga_eval_partials(H, W) floats per (frame,
+ *                channel), frame-major, stored plainly (contents irrelevant before the call)
+ *   With D3GA_EVAL_COMPOSED `image` IS the target (compute_errors(target, fake) and compute_heatmap, heatmap.py:37-61): alpha
+ *   and boundary_fg are not read and may be NULL; target_out and gt_out must be NULL then (D3GA_E_CONFIG).
+ *   pred, image, target_out, heat_out (B,3,H,W) f32;  gt_out (B,4,H,W) f32;  alpha (B,1,H,W) f32, or (B,3,H,W) with
+ *   D3GA_EVAL_ALPHA3 (channel 0 is read);  boundary_fg (B,1,H,W) uint8 / bool bytes, or f32 with D3GA_EVAL_BOUNDARY_F32.
+ *   Every output may be NULL (skipped), not all of them.  With H W % 4 == 0 and every tensor 16-byte aligned (boundary_fg
+ *   bytes: 4-byte) the planes are moved in 16-byte quads, otherwise pixel by pixel: same values either way.
+ * d3ga_eval_ssim: the forward of the 11x11 Gaussian-window SSIM described at d3ga_ssim_fwd, for B frames of three channels, one
+ *   plainly stored partial (the sum of ssim_map over a 16 x 16 tile) per tile: d3ga_eval_ssim_partials(H, W) floats per frame,
+ *   frame-major.  Unlike d3ga_ssim_fwd, whose sum over workgroups uses float atomics, its result does not depend on arrival
+ *   order.  pred, target (B,3,H,W) f32, element-aligned.
+ * d3ga_eval_finish, one workgroup per frame: adds the frame's partials in index order (bit-reproducible),
+ *   mse_c = sum_c / (H W),   psnr = mean_c 20 log10(1 / sqrt(mse_c))      the MEAN OF THE PER-CHANNEL PSNRs, as
+ *   psnr(fake, target).mean() of heatmap.py:39 is (utils/image_utils.py:20-22), not the PSNR of the pooled error; mse_c = 0
+ *   gives +inf.  metrics (B,2) f32 = [ssim, psnr]; ssim = the frame's d3ga_eval_ssim partials, added in index order in
+ *   double, / (3 H W) (ssim_partials NULL: NaN is written);  psnr_channels (B,3) f32, optional;  accum: 3 doubles, optional,
+ *   += [sum ssim, sum psnr, B] by float64 atomics (test.py:171-174 without a read-back per frame; needs ssim_partials, else
+ *   D3GA_E_CONFIG).
+ * d3ga_eval_partials: partials per (frame, channel) at this frame size, at most D3GA_EVAL_MAX_PARTIALS (< 0: D3GA_E_SIZE).
+ * d3ga_eval_jet_table: the 257 x 3 uint8 table into HOST memory (row 256: the bad colour).
+ *   Status, nothing launched: B, H, W <= 0, B > 65535 or H W > 2^26 D3GA_E_SIZE; an unknown flag, an output that has no
+ *   meaning in the mode, or a tensor not aligned to its element (accum: 8 bytes) D3GA_E_CONFIG; pred or image NULL, alpha or
+ *   boundary_fg NULL without D3GA_EVAL_COMPOSED, any pointer of d3ga_eval_ssim NULL, partials NULL in d3ga_eval_finish, or
+ *   every output NULL D3GA_E_NULL.
+ *   No scratch, no zero fill; capturable.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_EVAL_BG_WHITE 1
+#define D3GA_EVAL_COMPOSED 2
+#define D3GA_EVAL_ALPHA3 4
+#define D3GA_EVAL_BOUNDARY_F32 8
+#define D3GA_EVAL_ALL 15
+#define D3GA_EVAL_MAX_PARTIALS 2048
+int d3ga_eval_frames(int32_t B, int32_t H, int32_t W, int32_t flags, const float *pred, const float *image, const float *alpha,
+                     const void *boundary_fg, float *target_out, float *gt_out, float *heat_out, float *partials,
+                     d3ga_stream_t stream);
+int d3ga_eval_ssim(int32_t B, int32_t H, int32_t W, const float *pred, const float *target, float *ssim_partials,
+                   d3ga_stream_t stream);
+int d3ga_eval_finish(int32_t B, int32_t H, int32_t W, const float *partials, const float *ssim_partials, float *metrics,
+                     float *psnr_channels, double *accum, d3ga_stream_t stream);
+int64_t d3ga_eval_partials(int32_t H, int32_t W);
+int64_t d3ga_eval_ssim_partials(int32_t H, int32_t W);
+int d3ga_eval_jet_table(uint8_t *table);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
  * parameter in THREE launches whatever the number of tensors (two with clipping off).  The tensors are described by tables
  * that the caller builds once per set of addresses, in device memory or in pinned host memory mapped to the device (read by
