@@ -5,5 +5,8 @@ There is NO CPU fallback: every op raises if the library is missing or the tenso
 """
 from ._lib import D3GAError, lib, library_path  # noqa: F401
 from .evaluation import Evaluator, compute_errors, compute_heatmap, error_heatmap, psnr  # noqa: F401
+from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, rasterize_meshes, to_cameras,  # noqa: F401
+                          vertex_normals)
 
-__all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr"]
+__all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr",
+           "Fragments", "MeshCameras", "MeshScratch", "MeshTopology", "Renderer", "rasterize_meshes", "to_cameras", "vertex_normals"]

@@ -16,6 +16,7 @@
 #ifndef D3GA_H
 #define D3GA_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -719,6 +720,46 @@ int d3ga_eval_finish(int32_t B, int32_t H, int32_t W, const float *partials, con
 int64_t d3ga_eval_partials(int32_t H, int32_t W);
 int64_t d3ga_eval_ssim_partials(int32_t H, int32_t W);
 int d3ga_eval_jet_table(uint8_t *table);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Triangle-mesh rasterizer: the reference's recorder/mesh_renderer.py::Renderer (a pytorch3d MeshRasterizer with
+ * blur_radius 0, one face per pixel, both windings, perspective-correct barycentrics, and HardFlatShader) for B meshes that
+ * share one face list, one camera each.  Forward only.  Semantics: DESIGN.md 4.4f.
+ *   verts (B,V,3) f32 world space;  faces (F,3) int32 (a face with an index outside [0, V) is dropped);
+ *   cams (B,D3GA_MESH_CAM_FLOATS) f32: the world-to-camera rotation R row-major (9), t (3), fx, fy, cx, cy; OpenCV axes,
+ *   x_cam = R x + t, u = fx x/z + cx, v = fy y/z + cy, pixel (column i, row j) samples (i + 0.5, j + 0.5).
+ * d3ga_mesh_rasterize: a face with a vertex at z <= 0.01 or a doubled screen area below 1e-8 px^2 in magnitude is dropped.  Per
+ *   pixel the face with the smallest zbuf = 1 / sum_i b_i / z_i wins, ties go to the smaller face index (a 64-bit unsigned
+ *   atomic min over float_bits(zbuf) << 32 | face: bit-reproducible).  pix_to_face (B,H,W) int32, the index into `faces` or -1;
+ *   zbuf (B,H,W) f32 and bary (B,H,W,3) f32 (perspective-correct), -1 where no face covers the pixel; both optional.
+ *   scratch: d3ga_mesh_raster_scratch_bytes bytes, 16-byte aligned, contents irrelevant before the call (cleared by the call).
+ *   Launches: clear, face setup, scan, coverage (a grid-stride loop over chunks whose total is read on the device), resolve.
+ * d3ga_mesh_shade_flat: image (B,H,W,3) f32 from pix_to_face and bary: (0.45 + 0.35 max(n.l, 0)) texel + 0.05 [n.l > 0]
+ *   max(v.r, 0)^64 with texel the interpolated verts_rgb (B,V,3) f32 (NULL: ones), n the face normal (not flipped), the light
+ *   and the viewer at the camera centre; bg (3 floats, HOST memory, read by the call) where pix_to_face < 0.
+ * d3ga_mesh_vertex_normals: normals (B,V,3) f32, the incident faces' cross(x1 - x0, x2 - x0) added in the order of the vertex's
+ *   list, normalised with the norm clamped at 1e-6.  csr_offsets (V+1) int32, csr_faces (csr_offsets[V]) int32: the faces of
+ *   each vertex (built once per face list by the caller; an entry outside [0, F) is skipped).  No atomics.
+ * d3ga_mesh_maps: Renderer.map: position (B,H,W,3) f32 world, depth (B,H,W,1) f32 view z, normal (B,H,W,3) f32 =
+ *   normalize(n_v0 + n_v1 + n_v2) of the winning face (norm clamped at 1e-8), mask (B,H,W,1) f32 = pix_to_face > 0 (so
+ *   face 0 counts as background in the mask, as in the reference); all 0 where pix_to_face < 0.  Every output optional, not all.
+ *   Status, nothing launched: a negative size, H or W outside [1, D3GA_MESH_MAX_SIDE] or B F >= 2^31 D3GA_E_SIZE; a required
+ *   pointer NULL (verts with V > 0, faces with F > 0, ...) D3GA_E_NULL; a pointer not aligned to its element (scratch: 16 bytes)
+ *   D3GA_E_CONFIG.  B = 0, V = 0 and F = 0 are valid (F = 0: background only).  No host synchronisation; capturable.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_MESH_MAX_SIDE 16384
+#define D3GA_MESH_CAM_FLOATS 16
+int d3ga_mesh_raster_scratch_bytes(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, size_t *bytes);
+int d3ga_mesh_rasterize(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const float *verts, const int32_t *faces,
+                        const float *cams, void *scratch, int32_t *pix_to_face, float *zbuf, float *bary, d3ga_stream_t stream);
+int d3ga_mesh_shade_flat(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const float *verts, const int32_t *faces,
+                         const float *verts_rgb, const float *cams, const int32_t *pix_to_face, const float *bary, const float *bg,
+                         float *image, d3ga_stream_t stream);
+int d3ga_mesh_vertex_normals(int32_t B, int32_t V, int32_t F, const float *verts, const int32_t *faces, const int32_t *csr_offsets,
+                             const int32_t *csr_faces, float *normals, d3ga_stream_t stream);
+int d3ga_mesh_maps(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const float *verts, const int32_t *faces,
+                   const float *vertex_normals, const float *cams, const int32_t *pix_to_face, const float *bary, float *position,
+                   float *normal, float *depth, float *mask, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
