@@ -59,9 +59,11 @@ __host__ __device__ static inline GeomBuf geom_view(const GeomBuf &g, int64_t P,
 // Binning state.
 struct BinBuf {
     uint32_t *counters;     // 8  (D3GA_CNT_*)
-    uint32_t *tile_count;   // tiles
-    uint32_t *tile_start;   // tiles + 1   exclusive prefix of tile_count
-    uint32_t *tile_cursor;  // tiles
+    uint32_t *tile_count;   // tiles       duplicates in slots that preprocess reserved (wavefronts whose tile window fits a record)
+    uint32_t *tile_count2;  // tiles       duplicates of the other wavefronts: placed behind the reserved slots through tile_cursor
+    uint32_t *vis_part;     // kVisParts x kVisStride   partial counts of visible Gaussians, one per cache line: preprocess adds, the scan sums
+    uint32_t *tile_start;   // tiles + 1   exclusive prefix of tile_count + tile_count2
+    uint32_t *tile_cursor;  // tiles       tile_start + tile_count, written where tile_count2 is not zero
     uint64_t *keys;         // d_capacity  (depth bits << 32 | gaussian index), grouped by tile
     uint32_t *point_list;   // d_capacity  gaussian indices, per tile ascending (depth, index)
     uint32_t *big_tiles;    // tiles       tiles with 4097..8192 entries (counters[4] of them)
@@ -69,8 +71,11 @@ struct BinBuf {
     uint32_t *mid_tiles;    // tiles       tiles with 2049..4096 entries (counters[6])
     uint32_t *tile_order;   // tiles       tile indices by descending list length (work-ordered dispatch of compositing)
 };
+constexpr int kVisParts = 32, kVisStride = 32;      // 32 partial counters, 128 bytes apart
+constexpr int kUnresvWord = 1;                      // word of vis_part (between two partial counters): not zero if some wavefront of
+                                                    // the frame is unreserved -- only then does the scan read tile_count2
 static inline int64_t bin_bytes(int64_t tiles, int64_t dcap) {
-    return 256 + align256(4 * tiles) + align256(4 * (tiles + 1)) + align256(4 * tiles) + align256(8 * dcap) +
+    return 256 + 2 * align256(4 * tiles) + 4 * kVisParts * kVisStride + align256(4 * (tiles + 1)) + align256(4 * tiles) + align256(8 * dcap) +
            align256(4 * dcap) + 4 * align256(4 * tiles);
 }
 static inline BinBuf carve_bin(void *base, int64_t tiles, int64_t dcap) {
@@ -78,6 +83,8 @@ static inline BinBuf carve_bin(void *base, int64_t tiles, int64_t dcap) {
     BinBuf b;
     b.counters = (uint32_t *)p;    p += 256;
     b.tile_count = (uint32_t *)p;  p += align256(4 * tiles);
+    b.tile_count2 = (uint32_t *)p; p += align256(4 * tiles);
+    b.vis_part = (uint32_t *)p;    p += 4 * kVisParts * kVisStride;
     b.tile_start = (uint32_t *)p;  p += align256(4 * (tiles + 1));
     b.tile_cursor = (uint32_t *)p; p += align256(4 * tiles);
     b.keys = (uint64_t *)p;        p += align256(8 * dcap);
@@ -115,17 +122,31 @@ static inline ImgBuf carve_img(void *base, int64_t W, int64_t H, int64_t tiles, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Block-cooperative tile window.  The Gaussians of one 256-thread block are spatially coherent (they are stored in
-// tet order), so the union of their tile rectangles is small.  Counting / slot reservation is done with LDS atomics
-// inside that bounding window and only ONE global atomic per (block, touched tile) leaves the CU, instead of one per
-// (Gaussian, tile) -- which serialises badly because neighbouring lanes hit the same few tile counters.
+// Wavefront-private tile window and slot reservation.  The Gaussians are stored in tet order, so the union of the tile
+// rectangles of 64 consecutive ones is small (C3, over the bench's eight cameras: p50 9-12, p99 28-80, max 391 tiles).  A wavefront of preprocess counts its duplicates
+// with LDS atomics inside that window, in LDS nobody else touches (program order + wave_barrier, no workgroup barrier), and sends
+// ONE returning global atomic per touched tile to tile_count: the value it returns is the first slot, within the tile's list, of
+// the wavefront's duplicates there.  Box and bases are left in the wavefront's RESERVATION RECORD, and the scatter pass places
+// every key with one LDS atomic on  tile_start + base  -- it neither counts nor touches a global counter.
+//   record of (view v, wavefront w of the view's launch) = kResvStride words at  (v * resv_waves(P) + w) * kResvStride:
+//     [0] x0 | y0 << 16   [1] w | h << 16   (the window in tiles of the batch's grid; w * h == 0: nothing visible)   [2..3] unused
+//     [4 + k]  base of window tile k = (ty - y0) * w + (tx - x0), written for every k < w * h (0 where the wavefront has no
+//              duplicate): the scatter seeds all cursors of the window from it, so nothing of an earlier frame is ever read
+// A window of more than kResvTiles tiles (screen-filling splats) marks the wavefront as UNRESERVED: its duplicates are counted in
+// tile_count2 and placed one global atomic each through tile_cursor, behind the reserved slots of the tile.
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kWinTiles = 4096;   // LDS window capacity in tiles (16 KiB of u32); larger unions fall back to global atomics
+constexpr int kResvStride = 512;                     // words per record (2 KiB)
+constexpr int kResvHdr = 4;
+constexpr int kResvTiles = kResvStride - kResvHdr;   // window tiles a record holds: every wavefront of C3 fits (max 391 over the bench's eight cameras)
+constexpr int kResvSlots = (kResvTiles + 63) / 64;   // window tiles per lane
+static inline int64_t resv_waves(int64_t P) { return (kBlock / 64) * ((P + kBlock - 1) / kBlock); }   // records per view
+static inline int64_t resv_bytes(int64_t P, int64_t views) { return align256(4 * kResvStride * resv_waves(P) * views); }
 
 struct TileWindow {
-    int x0, y0, w, h;             // window origin and size in tiles; w*h == 0 -> nothing visible in the block
-    __device__ __forceinline__ int area() const { return w * h; }
-    __device__ __forceinline__ bool fits() const { return w * h <= kWinTiles; }
+    int x0, y0, w, h;             // window origin and size in tiles; w*h == 0 -> nothing visible in the wavefront
+    __device__ __forceinline__ bool empty() const { return w <= 0 || h <= 0; }
+    __device__ __forceinline__ bool fits() const { return w <= kResvTiles && h <= kResvTiles && w * h <= kResvTiles; }
+    __device__ __forceinline__ int area() const { return w * h; }      // (of a window that fits)
     // window slot k -> global tile index (exact for k < 4096: the fractional part of (k + 0.5) / w is >= 0.5 / w away from
     // an integer, the float error is < 5e-4 / w; a 32-bit integer division costs ~40 instructions)
     __device__ __forceinline__ int tile_of(int k, int gx, float inv_w) const {
@@ -135,28 +156,19 @@ struct TileWindow {
 };
 
 #ifdef __HIPCC__
-// s_box: 4 ints of LDS.  Every thread of the block must call this (contains barriers).
-__device__ __forceinline__ TileWindow block_tile_window(int *s_box, bool visible, int rx0, int ry0, int rx1, int ry1) {
-    if (threadIdx.x == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = 0; s_box[3] = 0; }
-    __syncthreads();
-    // wavefront-level min/max first (butterfly shuffles), then ONE lane per wavefront touches the four LDS words:
-    // 256 same-address LDS atomics per word serialise
+// the union of the wavefront's visible rectangles, by butterfly shuffles: the same in every lane
+__device__ __forceinline__ TileWindow wave_tile_window(bool visible, int rx0, int ry0, int rx1, int ry1) {
     int bx0 = visible ? rx0 : 0x7fffffff, by0 = visible ? ry0 : 0x7fffffff, bx1 = visible ? rx1 : 0, by1 = visible ? ry1 : 0;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         bx0 = min(bx0, __shfl_xor(bx0, off)); by0 = min(by0, __shfl_xor(by0, off));
         bx1 = max(bx1, __shfl_xor(bx1, off)); by1 = max(by1, __shfl_xor(by1, off));
     }
-    if ((threadIdx.x & 63) == 0 && bx1 > 0) {
-        atomicMin(&s_box[0], bx0); atomicMin(&s_box[1], by0);
-        atomicMax(&s_box[2], bx1); atomicMax(&s_box[3], by1);
-    }
-    __syncthreads();
     TileWindow win;
-    win.x0 = s_box[0]; win.y0 = s_box[1];
-    win.w = s_box[2] > s_box[0] ? s_box[2] - s_box[0] : 0;
-    win.h = s_box[3] > s_box[1] ? s_box[3] - s_box[1] : 0;
-    if (win.w == 0 || win.h == 0) { win.w = 0; win.h = 0; }
+    win.x0 = bx0; win.y0 = by0;
+    win.w = bx1 > bx0 ? bx1 - bx0 : 0;
+    win.h = by1 > by0 ? by1 - by0 : 0;
+    if (win.w == 0 || win.h == 0) { win.x0 = 0; win.y0 = 0; win.w = 0; win.h = 0; }
     return win;
 }
 #endif
@@ -172,6 +184,10 @@ static inline int grid_y(const d3ga_raster_params *prm) { return tiles_y(prm->H)
 // the window table behind the binning buffer's sections (one int4 {ox, oy, w, h} per view): null unless windowed
 static inline int4 *win_table(void *binning, int64_t tiles, int64_t dcap) { return (int4 *)((char *)binning + bin_bytes(tiles, dcap)); }
 static inline int64_t win_table_bytes(int64_t views) { return align256(16 * views); }
+// the reservation records (resv_bytes) are the last section: behind the window table where there is one
+static inline uint32_t *resv_records(void *binning, int64_t tiles, int64_t dcap, int64_t views, bool windowed) {
+    return (uint32_t *)((char *)binning + bin_bytes(tiles, dcap) + (windowed ? win_table_bytes(views) : 0));
+}
 
 // launch check: returns hipError (>0) or 0; in debug mode also synchronises
 static inline int check_launch(hipStream_t s, int debug) {

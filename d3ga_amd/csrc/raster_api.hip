@@ -62,7 +62,7 @@ extern "C" int d3ga_raster_scratch_bytes_views(int32_t P, int32_t W, int32_t H, 
     if ((int64_t)tiles_y(H) * k > 65535 || (int64_t)P * k >= (1ll << 31)) return D3GA_E_SIZE;     // tile rows are 16-bit fields of the rectangle records
     const int64_t tiles = (int64_t)tiles_x(W) * tiles_y(H) * k, cap = d_capacity > 0 ? d_capacity : 1;
     sizes[0] = geom_bytes(P > 0 ? P * k : 1);
-    sizes[1] = bin_bytes(tiles, cap);
+    sizes[1] = bin_bytes(tiles, cap) + resv_bytes(P, k);
     sizes[2] = forward_only ? 2 * align256(4 * (int64_t)W * H * k) : img_bytes(W, H, tiles, cap, k);
     return D3GA_OK;
 }
@@ -76,7 +76,7 @@ extern "C" int d3ga_raster_scratch_bytes_window(int32_t P, int32_t W, int32_t H,
     if (gy * k > 65535 || gx > 65535 || (int64_t)P * k >= (1ll << 31)) return D3GA_E_SIZE;
     const int64_t tiles = gx * gy * k, cap = d_capacity > 0 ? d_capacity : 1;
     sizes[0] = geom_bytes(P > 0 ? P * k : 1);
-    sizes[1] = bin_bytes(tiles, cap) + win_table_bytes(k);
+    sizes[1] = bin_bytes(tiles, cap) + win_table_bytes(k) + resv_bytes(P, k);
     sizes[2] = forward_only ? 2 * align256(4 * (int64_t)W * H * k) : img_bytes(W, H, tiles, cap, k);
     return D3GA_OK;
 }

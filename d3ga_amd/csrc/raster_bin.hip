@@ -1,16 +1,16 @@
 // raster_bin.hip -- binning and depth ordering for gfx950.
 //
 // Instead of one global 64-bit radix sort over all (tile, depth) duplicates (6 passes x 2 x 12 B per duplicate
-// of HBM traffic), the duplicates are first binned by tile with a counting sort (histogram in the preprocess
-// kernel -> exclusive scan -> atomic-cursor scatter: 8 B written per duplicate), and each tile's list is then
+// of HBM traffic), the duplicates are first binned by tile with a counting sort (histogram and slot reservation in the
+// preprocess kernel -> exclusive scan -> scatter into the reserved slots: 8 B written per duplicate), and each tile's list is then
 // sorted by (depth, Gaussian index) entirely inside the LDS of one workgroup with a bitonic network
 // (8 B read + 4 B written per duplicate).  The 64-bit key (depth bits << 32 | index) makes the order total, so
 // the result does not depend on the order in which the atomics of the scatter pass landed.
 //
 //   tile_scan_order_kernel  two workgroups: [0] exclusive prefix of the tile histogram, D, overflow flag;
 //                         [1] tile indices by descending list length (work-ordered dispatch)
-//   tile_scatter_kernel   one thread per Gaussian: emit its key into every tile of its rectangle; slots are reserved
-//                         per (block, tile) through an LDS window (d3ga_internal.h: TileWindow)
+//   tile_scatter_kernel   one thread per Gaussian: emit its key into every tile of its rectangle, into the slots its wavefront
+//                         reserved per tile in preprocess (d3ga_internal.h: reservation records): no counting, no barrier
 //   tile_sort_lds_kernel       one workgroup per tile: LDS bitonic sort, 8 keys per thread (lists up to 2048 entries)
 //   tile_sort_lds_list_kernel  longer lists (up to 8192): 64 KB LDS, persistent grid over a device-side work list
 //                              (+ in the same launch: even longer lists, same network on global memory)
@@ -22,8 +22,9 @@ namespace d3ga {
 
 constexpr int kScanBlock = 1024;
 
-__device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__restrict__ count,
-                                               uint32_t *__restrict__ start, uint32_t *__restrict__ cursor,
+// count: duplicates in reserved slots, count2: the others (d3ga_internal.h); a tile's list holds both, the reserved ones first
+__device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__restrict__ count, const uint32_t *__restrict__ count2,
+                                               const uint32_t *__restrict__ vis_part, uint32_t *__restrict__ start, uint32_t *__restrict__ cursor,
                                                uint32_t *__restrict__ counters, uint64_t dcap,
                                                uint32_t *__restrict__ big_tiles, uint32_t *__restrict__ huge_tiles,
                                                uint32_t *__restrict__ mid_tiles, uint32_t n_small, uint32_t n_mid,
@@ -36,18 +37,26 @@ __device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__rest
     __shared__ uint32_t s_max;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_max = 0;
+    const bool unresv = vis_part[kUnresvWord] != 0u;          // (uniform) some wavefront is unreserved: count2 is not all zero
+    uint32_t visible = wave == 0 && lane < kVisParts ? vis_part[lane * kVisStride] : 0u;     // preprocess's partial counts (wavefront 0 sums them)
     uint32_t carry = 0, mx = 0;
     int par = 0;
     for (int c0 = 0; c0 < tiles; c0 += kChunk, par ^= 1) {
         const int t0 = c0 + kPer * tid;
-        uint32_t c[kPer];
+        uint32_t c[kPer], u[kPer];                            // list length | its unreserved part
         if (t0 + kPer <= tiles) {
             const uint4 lo = reinterpret_cast<const uint4 *>(count + t0)[0], hi = reinterpret_cast<const uint4 *>(count + t0)[1];
+            uint4 lo2 = make_uint4(0u, 0u, 0u, 0u), hi2 = lo2;
+            if (unresv) { lo2 = reinterpret_cast<const uint4 *>(count2 + t0)[0]; hi2 = reinterpret_cast<const uint4 *>(count2 + t0)[1]; }
             c[0] = lo.x; c[1] = lo.y; c[2] = lo.z; c[3] = lo.w; c[4] = hi.x; c[5] = hi.y; c[6] = hi.z; c[7] = hi.w;
+            u[0] = lo2.x; u[1] = lo2.y; u[2] = lo2.z; u[3] = lo2.w; u[4] = hi2.x; u[5] = hi2.y; u[6] = hi2.z; u[7] = hi2.w;
         } else {
 #pragma unroll
-            for (int k = 0; k < kPer; ++k) c[k] = t0 + k < tiles ? count[t0 + k] : 0u;
+            for (int k = 0; k < kPer; ++k) { c[k] = t0 + k < tiles ? count[t0 + k] : 0u; u[k] = unresv && t0 + k < tiles ? count2[t0 + k] : 0u; }
         }
+        uint32_t any2 = 0;
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) { any2 |= u[k]; c[k] += u[k]; }
         uint32_t sum = 0;
 #pragma unroll
         for (int k = 0; k < kPer; ++k) { sum += c[k]; mx = max(mx, c[k]); }
@@ -103,16 +112,24 @@ __device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__rest
         if (t0 + kPer <= tiles) {
             const uint4 lo = make_uint4(e[0], e[1], e[2], e[3]), hi = make_uint4(e[4], e[5], e[6], e[7]);
             reinterpret_cast<uint4 *>(start + t0)[0] = lo; reinterpret_cast<uint4 *>(start + t0)[1] = hi;
-            reinterpret_cast<uint4 *>(cursor + t0)[0] = lo; reinterpret_cast<uint4 *>(cursor + t0)[1] = hi;
         } else {
 #pragma unroll
             for (int k = 0; k < kPer; ++k)
-                if (t0 + k < tiles) { start[t0 + k] = e[k]; cursor[t0 + k] = e[k]; }
+                if (t0 + k < tiles) start[t0 + k] = e[k];
+        }
+        // the cursor is only read for tiles with unreserved duplicates: they go behind the reserved slots (c - u of them)
+        if (any2) {
+#pragma unroll
+            for (int k = 0; k < kPer; ++k)
+                if (t0 + k < tiles && u[k]) cursor[t0 + k] = e[k] + (c[k] - u[k]);
         }
         carry += total;
     }
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
+    for (int off = 1; off < 64; off <<= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
+        visible += (uint32_t)__shfl_xor((int)visible, off);
+    }
     if (lane == 0) atomicMax(&s_max, mx);
     __syncthreads();
     if (tid == 0) {
@@ -120,6 +137,7 @@ __device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__rest
         counters[D3GA_CNT_D] = carry;
         counters[D3GA_CNT_OVERFLOW] = (uint64_t)carry > dcap ? 1u : 0u;
         counters[D3GA_CNT_MAXTILE] = s_max;
+        counters[D3GA_CNT_VISIBLE] = visible;
     }
 }
 
@@ -127,8 +145,8 @@ __device__ __forceinline__ void tile_scan_body(int tiles, const uint32_t *__rest
 // scaled to the longest list; order inside a bucket is arbitrary).  All active compositing wavefronts are resident at once
 // and the dispatcher deals workgroups round-robin, so dealing them in descending order of work gives every SIMD one
 // wavefront from each work quantile instead of a random handful.
-__device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__restrict__ count,
-                                                uint32_t *__restrict__ order, uint32_t *__restrict__ counters) {
+__device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__restrict__ count, const uint32_t *__restrict__ count2,
+                                                const uint32_t *__restrict__ vis_part, uint32_t *__restrict__ order, uint32_t *__restrict__ counters) {
     // Round 3: ONE pass over the counts.  The bucket of a tile is its list length in units of 16 entries (the group size of
     // the compositing backward), clipped at 254 -- a fixed map, so the maximum need not be known first (round 2 took the
     // maximum, then built the histogram, then scattered: three dependent rounds of global loads on one workgroup, 10 us);
@@ -138,6 +156,7 @@ __device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__res
     __shared__ uint32_t s_zero;                           // empty tiles (most of the image for an avatar): wavefront-
     const int tid = threadIdx.x, lane = tid & 63;         // aggregated, thousands of same-address LDS atomics serialise
     constexpr int kPer = 8;
+    const bool unresv = vis_part[kUnresvWord] != 0u;      // (uniform) as in the scan workgroup
     if (tid < 256) s_hist[tid] = 0;
     if (tid == 0) s_zero = 0;
     __syncthreads();
@@ -147,7 +166,7 @@ __device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__res
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
             const int t = c0 + k * kScanBlock + tid;
-            c[k] = t < tiles ? count[t] : 0xffffffffu;                    // 0xffffffff: no tile
+            c[k] = t < tiles ? count[t] + (unresv ? count2[t] : 0u) : 0xffffffffu;        // 0xffffffff: no tile
         }
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
@@ -187,7 +206,7 @@ __device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__res
 #pragma unroll
                 for (int k = 0; k < kPer; ++k) {
                     const int t = c1 + k * kScanBlock + tid;
-                    c[k] = t < tiles ? count[t] : 0xffffffffu;
+                    c[k] = t < tiles ? count[t] + (unresv ? count2[t] : 0u) : 0xffffffffu;
                 }
             }
 #pragma unroll
@@ -208,6 +227,8 @@ __device__ __forceinline__ void tile_order_body(int tiles, const uint32_t *__res
 
 // one launch, two workgroups: block 0 scans the histogram, block 1 orders the tiles (they only share the read-only counts)
 __global__ __launch_bounds__(kScanBlock) void tile_scan_order_kernel(int tiles, const uint32_t *__restrict__ count,
+                                                                     const uint32_t *__restrict__ count2,
+                                                                     const uint32_t *__restrict__ vis_part,
                                                                      uint32_t *__restrict__ start,
                                                                      uint32_t *__restrict__ cursor,
                                                                      uint32_t *__restrict__ counters, uint64_t dcap,
@@ -216,53 +237,60 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_order_kernel(int tiles, 
                                                                      uint32_t *__restrict__ mid_tiles, uint32_t n_small,
                                                                      uint32_t n_mid, uint32_t n_large,
                                                                      uint32_t *__restrict__ order) {
-    if (blockIdx.x == 0) tile_scan_body(tiles, count, start, cursor, counters, dcap, big_tiles, huge_tiles, mid_tiles, n_small, n_mid, n_large);
-    else tile_order_body(tiles, count, order, counters);
+    if (blockIdx.x == 0) tile_scan_body(tiles, count, count2, vis_part, start, cursor, counters, dcap, big_tiles, huge_tiles, mid_tiles, n_small, n_mid, n_large);
+    else tile_order_body(tiles, count, count2, vis_part, order, counters);
 }
 
+// grid: (blocks of one view, views) -- the wavefronts are those of the view's preprocess launch, record for record.  P: Gaussians
+// per view; the key carries the record index v P + i of the batch.
 __global__ __launch_bounds__(kBlock) void tile_scatter_kernel(int P, int gx, const uint2 *__restrict__ rect,
                                                               const float *__restrict__ depth,
+                                                              const uint32_t *__restrict__ start,
+                                                              const uint32_t *__restrict__ resv,
                                                               uint32_t *__restrict__ cursor, uint64_t *__restrict__ keys,
                                                               uint64_t dcap) {
-    __shared__ int s_box[4];
-    // pass A: per-tile count of this block; pass B: the first slot reserved for the block in the tile's list; pass C: the running
-    // slot.  ONE array (round 4: a second one for the bases made it 32 KB -- four workgroups per CU, 1.9 rounds of the 1954
-    // workgroups at C3; with 16 KB the launch is one round)
-    __shared__ uint32_t s_cnt[kWinTiles];
-    const int tid = threadIdx.x;
+    // the running slot of every tile of the wavefront's window: private to the wavefront, so program order + wave_barrier suffice
+    __shared__ uint32_t s_cur[kBlock / 64][kResvTiles];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * kBlock + tid;
+    if (i - lane >= P) return;                               // (uniform) no Gaussian, no record
+    const size_t j = (size_t)blockIdx.y * P + i;
+    const uint32_t *rec = resv + ((size_t)blockIdx.y * gridDim.x * (kBlock / 64) + blockIdx.x * (kBlock / 64) + wave) * kResvStride;
+    const uint2 box = *reinterpret_cast<const uint2 *>(rec);
+    uint32_t base[kResvSlots];
+    base[0] = rec[kResvHdr + lane];                          // in flight with the rectangle (read whatever the window is: inside the record)
     int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
     uint64_t key = 0;
     if (i < P) {
-        const uint2 rc = rect[i];
+        const uint2 rc = rect[j];
         x0 = rc.x & 0xffffu; y0 = rc.x >> 16; x1 = rc.y & 0xffffu; y1 = rc.y >> 16;
-        key = ((uint64_t)__float_as_uint(depth[i]) << 32) | (uint32_t)i;
+        key = ((uint64_t)__float_as_uint(depth[j]) << 32) | (uint32_t)j;
     }
     const bool visible = x1 > x0 && y1 > y0;
-    const TileWindow win = block_tile_window(s_box, visible, x0, y0, x1, y1);
-    const int area = win.area();
-    if (area == 0) return;                                   // uniform
+    TileWindow win;
+    win.x0 = (int)(box.x & 0xffffu); win.y0 = (int)(box.x >> 16); win.w = (int)(box.y & 0xffffu); win.h = (int)(box.y >> 16);
+    if (win.empty()) return;                                 // uniform
     if (win.fits()) {
-        for (int k = tid; k < area; k += kBlock) s_cnt[k] = 0;
-        __syncthreads();
-        if (visible)
-            for (int ty = y0; ty < y1; ++ty)
-                for (int tx = x0; tx < x1; ++tx) atomicAdd(&s_cnt[(ty - win.y0) * win.w + (tx - win.x0)], 1u);
-        __syncthreads();
+        const int area = win.area();
+        uint32_t *cur = s_cur[wave];
         const float inv_w = 1.0f / (float)win.w;
-        for (int k = tid; k < area; k += kBlock) {           // ONE global (returning) atomic per touched tile
-            const uint32_t c = s_cnt[k];
-            if (c) s_cnt[k] = atomicAdd(&cursor[win.tile_of(k, gx, inv_w)], c);
+#pragma unroll
+        for (int q = 1; q < kResvSlots; ++q) base[q] = lane + 64 * q < area ? rec[kResvHdr + lane + 64 * q] : 0u;
+#pragma unroll
+        for (int q = 0; q < kResvSlots; ++q) {
+            const int k = lane + 64 * q;
+            if (k < area) cur[k] = start[win.tile_of(k, gx, inv_w)] + base[q];
         }
-        __syncthreads();
+        __builtin_amdgcn_wave_barrier();
         if (visible)
             for (int ty = y0; ty < y1; ++ty)
                 for (int tx = x0; tx < x1; ++tx) {
                     const int l = (ty - win.y0) * win.w + (tx - win.x0);
-                    const uint32_t pos = atomicAdd(&s_cnt[l], 1u);
+                    if ((unsigned)l >= (unsigned)area) continue;      // (a rectangle outside its wavefront's box: never, by construction)
+                    const uint32_t pos = atomicAdd(&cur[l], 1u);
                     if (pos < dcap) keys[pos] = key;
                 }
-    } else if (visible) {
+    } else if (visible) {                                    // an unreserved wavefront: behind the reserved slots of every tile
         for (int ty = y0; ty < y1; ++ty)
             for (int tx = x0; tx < x1; ++tx) {
                 const uint32_t pos = atomicAdd(&cursor[ty * gx + tx], 1u);
@@ -588,13 +616,14 @@ extern "C" int d3ga_raster_bin_sort(const d3ga_raster_params *prm, void *geom, v
     const int64_t P = (int64_t)prm->P * views;
     BinBuf bin = carve_bin(binning, tiles, d_capacity);
     GeomBuf g = carve_geom(geom, P);
-    hipLaunchKernelGGL(tile_scan_order_kernel, dim3(2), dim3(kScanBlock), 0, s, tiles, bin.tile_count, bin.tile_start,
+    hipLaunchKernelGGL(tile_scan_order_kernel, dim3(2), dim3(kScanBlock), 0, s, tiles, bin.tile_count, bin.tile_count2, bin.vis_part, bin.tile_start,
                        bin.tile_cursor, bin.counters, (uint64_t)d_capacity, bin.big_tiles, bin.huge_tiles, bin.mid_tiles,
                        (uint32_t)kSortSmall, (uint32_t)kSortMid, (uint32_t)kSortLarge, bin.tile_order);
     D3GA_TRY(check_launch(s, prm->debug));
     if (P == 0 || d_capacity == 0) return D3GA_OK;
-    hipLaunchKernelGGL(tile_scatter_kernel, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (int)P, gx, g.rect,
-                       g.depth, bin.tile_cursor, bin.keys, (uint64_t)d_capacity);
+    hipLaunchKernelGGL(tile_scatter_kernel, dim3((unsigned)((prm->P + kBlock - 1) / kBlock), (unsigned)views), dim3(kBlock), 0, s, prm->P,
+                       gx, g.rect, g.depth, bin.tile_start, resv_records(binning, tiles, d_capacity, views, is_windowed(prm)),
+                       bin.tile_cursor, bin.keys, (uint64_t)d_capacity);
     D3GA_TRY(check_launch(s, prm->debug));
     {
         static std::atomic<int> resident[64] = {};           // per device: workgroups of the per-tile sort the chip holds at once (a cache of two queries)

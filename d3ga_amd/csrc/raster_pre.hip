@@ -1,6 +1,6 @@
 // raster_pre.hip -- per-Gaussian stages of the tile rasterizer for gfx950.
 //
-//   preprocess_kernel      project, EWA 2D covariance, conic, radius, tile rectangle, SH colour, tile histogram
+//   preprocess_kernel      project, EWA 2D covariance, conic, radius, tile rectangle, SH colour, tile histogram + slot reservation
 //   preprocess_bwd_kernel  conic/mean2D/colour/opacity gradients -> mean3D, cov3D | (scale, rotation), SH
 //
 // Both are HBM-streaming: one thread per Gaussian, every per-Gaussian array read/written once (algorithmic bytes per
@@ -133,10 +133,15 @@ __device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, 
     }
 }
 
-// what preprocess leaves per Gaussian (GeomBuf records of ITS view, radius); returns the tile rectangle in the batch's grid
+// a Gaussian's tile rectangle in the batch's grid (tile_row0: its view's first tile row there)
 struct TileRect { bool visible; int r0, r1, r2, r3; };
-__device__ __forceinline__ TileRect write_geom_records(const GeomBuf &geom, int i, const PreOut &o, bool keep_cov, int tile_row0,
-                                                       int32_t *__restrict__ radii, bool want_j, const ShColJ &cj) {
+__device__ __forceinline__ TileRect view_tile_rect(const PreOut &o, int tile_row0) {
+    const Splat &sp = o.sp;
+    return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
+}
+// what preprocess leaves per Gaussian (GeomBuf records of ITS view, radius)
+__device__ __forceinline__ void write_geom_records(const GeomBuf &geom, int i, const PreOut &o, bool keep_cov, int tile_row0,
+                                                   int32_t *__restrict__ radii, bool want_j, const ShColJ &cj) {
     const Splat &sp = o.sp;
     if (keep_cov) {                         // (uniform) a precomputed covariance is read again from the caller's tensor
 #pragma unroll
@@ -156,7 +161,6 @@ __device__ __forceinline__ TileRect write_geom_records(const GeomBuf &geom, int 
     geom.rgb_invd[i] = make_float4(o.rgb[0], o.rgb[1], o.rgb[2], sp.visible ? 1.0f / sp.depth : 0.f);
     geom.clamped[i] = o.clampmask;
     if (want_j) dcol_store(geom.dcol, geom.dcol_stride, i, cj);
-    return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
 }
 
 // Windowed camera slot (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): the splat was projected on the view's full raster; its tile rectangle
@@ -178,43 +182,70 @@ __global__ void window_table_kernel(d3ga_raster_params prm, const float *__restr
     table[v] = make_int4(c.ox, c.oy, c.W, c.H);
 }
 
-// tile histogram (counting-sort pass 1) of this block's Gaussians through its LDS window.  Every thread of the block must call it
-// (barriers inside); s_cnt: kWinTiles words that nobody else uses between the call's first and last barrier.
-__device__ __forceinline__ void tile_histogram(int *s_box, uint32_t *s_cnt, const TileRect &t, int gx, uint32_t *__restrict__ tile_count,
-                                               uint32_t *__restrict__ counters) {
-    const int tid = threadIdx.x;
-    const TileWindow win = block_tile_window(s_box, t.visible, t.r0, t.r1, t.r2, t.r3);   // barriers inside
-    const int nvis = __syncthreads_count(t.visible);
-    if (tid == 0 && nvis) atomicAdd(&counters[D3GA_CNT_VISIBLE], (uint32_t)nvis);
-    const int area = win.area();
-    if (area == 0) return;                                   // uniform
-    if (win.fits()) {
-        for (int k = tid; k < area; k += kBlock) s_cnt[k] = 0;
-        __syncthreads();
+// Tile histogram (counting-sort pass 1) and slot reservation of ONE WAVEFRONT's Gaussians (d3ga_internal.h: reservation records),
+// in two steps so that the round trip of the returning atomics runs under the stores of the geometry records between them.
+// s_win: kResvTiles words of LDS that only this wavefront touches (program order + wave_barrier order its accesses); every lane of
+// the wavefront must call both.
+struct TileResv { TileWindow win; uint32_t base[kResvSlots]; };
+__device__ __forceinline__ TileResv tile_reserve_issue(uint32_t *s_win, const TileRect &t, int gx, uint32_t *__restrict__ tile_count,
+                                                       uint32_t *__restrict__ tile_count2, uint32_t *__restrict__ vis_part) {
+    const int lane = threadIdx.x & 63;
+    TileResv r;
+    r.win = wave_tile_window(t.visible, t.r0, t.r1, t.r2, t.r3);
+#pragma unroll
+    for (int j = 0; j < kResvSlots; ++j) r.base[j] = 0u;
+    // the visible count: one popcount and one atomic per wavefront, spread over kVisParts cache lines that the scan workgroup sums.
+    // (Into counters[D3GA_CNT_VISIBLE] directly -- 7813 adds to ONE address at C3 -- the counter was the kernel's critical path:
+    // same-address atomics are served one after the other, preprocess 57 -> 122 us; LOG "Binning: slots reserved in preprocess".)
+    const unsigned long long vis = __ballot(t.visible);
+    if (lane == 0 && vis) atomicAdd(&vis_part[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) % kVisParts) * kVisStride], (uint32_t)__popcll(vis));
+    if (r.win.empty()) return r;                             // uniform
+    if (r.win.fits()) {
+        const int area = r.win.area();
+        __builtin_amdgcn_wave_barrier();                     // (whatever the wavefront read from this LDS before)
+#pragma unroll
+        for (int j = 0; j < kResvSlots; ++j)
+            if (lane + 64 * j < area) s_win[lane + 64 * j] = 0u;
+        __builtin_amdgcn_wave_barrier();
         if (t.visible)
             for (int ty = t.r1; ty < t.r3; ++ty)
-                for (int tx = t.r0; tx < t.r2; ++tx) atomicAdd(&s_cnt[(ty - win.y0) * win.w + (tx - win.x0)], 1u);
-        __syncthreads();
-        const float inv_w = 1.0f / (float)win.w;
-        for (int k = tid; k < area; k += kBlock) {
-            const uint32_t c = s_cnt[k];
-            if (c) atomicAdd(&tile_count[win.tile_of(k, gx, inv_w)], c);
+                for (int tx = t.r0; tx < t.r2; ++tx) atomicAdd(&s_win[(ty - r.win.y0) * r.win.w + (tx - r.win.x0)], 1u);
+        __builtin_amdgcn_wave_barrier();
+        const float inv_w = 1.0f / (float)r.win.w;
+#pragma unroll
+        for (int j = 0; j < kResvSlots; ++j) {               // ONE global (returning) atomic per touched tile
+            const int k = lane + 64 * j;
+            const uint32_t c = k < area ? s_win[k] : 0u;
+            if (c) r.base[j] = atomicAdd(&tile_count[r.win.tile_of(k, gx, inv_w)], c);
         }
-    } else if (t.visible) {                                  // huge footprints: straight to global memory
-        for (int ty = t.r1; ty < t.r3; ++ty)
-            for (int tx = t.r0; tx < t.r2; ++tx) atomicAdd(&tile_count[ty * gx + tx], 1u);
+    } else {                                                 // huge footprints: straight to global memory, no slots reserved
+        if (lane == 0) atomicOr(&vis_part[kUnresvWord], 1u);  // (the scan reads tile_count2 only if told so)
+        if (t.visible)
+            for (int ty = t.r1; ty < t.r3; ++ty)
+                for (int tx = t.r0; tx < t.r2; ++tx) atomicAdd(&tile_count2[ty * gx + tx], 1u);
     }
+    return r;
+}
+// rec: this wavefront's reservation record.  Every base of the window is written, 0 where the wavefront has no duplicate: the
+// scatter reads them all, and so never sees what an earlier frame left in the scratch.
+__device__ __forceinline__ void tile_reserve_store(const TileResv &r, uint32_t *__restrict__ rec) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 0)
+        *reinterpret_cast<uint4 *>(rec) = make_uint4((uint32_t)r.win.x0 | ((uint32_t)r.win.y0 << 16), (uint32_t)r.win.w | ((uint32_t)r.win.h << 16), 0u, 0u);
+    if (r.win.empty() || !r.win.fits()) return;              // uniform
+    const int area = r.win.area();
+#pragma unroll
+    for (int j = 0; j < kResvSlots; ++j)
+        if (lane + 64 * j < area) rec[kResvHdr + lane + 64 * j] = r.base[j];
 }
 
 // The per-view tail of both forward kernels: R1 of Gaussian i in view `cam` from what the kernel has in registers (staged: the SH
-// colour sum in cj.a0..a2; pre: the covariance row and raw opacity), then the view's records.  WIN: the rectangle is clipped to the
-// window's gx x gy tiles.
+// colour sum in cj.a0..a2; pre: the covariance row and raw opacity).  WIN: the rectangle is clipped to the window's gx x gy tiles.
 template <bool WIN>
-__device__ __forceinline__ TileRect preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D,
+__device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D,
                                                     const float *sh_row, bool staged, const ShColJ &cj, bool pre, const float (&pc6)[6],
                                                     float pop, const float *colors_precomp, const float *opacities, const float *scales,
-                                                    const float *rotations, const float *cov3D_precomp, const GeomBuf &geom,
-                                                    int tile_row0, int32_t *radii, bool want_j, int gx, int gy) {
+                                                    const float *rotations, const float *cov3D_precomp, int gx, int gy) {
     PreLoaded pl;
     pl.has_sh = staged; pl.has_c6 = pre;
     pl.sh[0] = cj.a0; pl.sh[1] = cj.a1; pl.sh[2] = cj.a2;
@@ -223,7 +254,7 @@ __device__ __forceinline__ TileRect preprocess_view(const d3ga_raster_params &pr
     pl.op = pop;
     PreOut o = preprocess_one(prm, cam, i, means3D, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
     if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
-    return write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, want_j, cj);
+    return o;
 }
 
 // WIN: windowed camera slot (campos: 9 floats, d3ga.h): project with the view's raster size, histogram over the window's tiles
@@ -233,19 +264,19 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
     const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp, const float *__restrict__ viewmatrix,
     const float *__restrict__ projmatrix, const float *__restrict__ campos, GeomBuf geom,
-    uint32_t *__restrict__ tile_count, uint32_t *__restrict__ counters, int32_t *__restrict__ radii,
+    uint32_t *__restrict__ tile_count, uint32_t *__restrict__ tile_count2, uint32_t *__restrict__ vis_part,
+    uint32_t *__restrict__ resv /* this view's reservation records */, int32_t *__restrict__ radii,
     int tile_row0 /* view-batched renders: this view's first tile row in the batch's grid (d3ga.h: n_views); else 0 */) {
     const ViewCam cam = view_cam(prm, viewmatrix, projmatrix, campos, WIN);
     const int gx = (prm.W + kTile - 1) / kTile + (WIN ? 1 : 0), gy = (prm.H + kTile - 1) / kTile + 1;   // (WIN) the window's grid
-    // one dynamic LDS region, used first as the SH staging slabs and then (after a barrier) as the tile window
+    // one dynamic LDS region per wavefront, used first as its SH staging slab and then as its tile window: no workgroup barrier
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_box[4];
     float *s_sh = reinterpret_cast<float *>(smem);
-    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(smem);
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6;
     const int i = blockIdx.x * kBlock + tid;
     const int M3 = 3 * prm.M;
     const bool staged = shs != nullptr && sh_staged(prm.M);
+    uint32_t *s_win = reinterpret_cast<uint32_t *>(smem) + wave * (staged ? kShHalfSlab : kResvStride);
     // covariance row and opacity: in flight while the SH rows are staged
     float pc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pop = 0.f;
     const bool pre = staged && cov3D_precomp != nullptr;
@@ -259,18 +290,21 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     if (staged) {
         staged_sh_colour<WANT_J>(prm, means3D, shs, campos, s_sh, acc, cj);
         if (!WANT_J) { cj.a0 = acc[0]; cj.a1 = acc[1]; cj.a2 = acc[2]; }
-        __syncthreads();                                            // the region becomes the tile window below
     }
     TileRect tr = {false, 0, 0, 0, 0};
+    PreOut o = {};
     if (i < prm.P) {
         // two call sites so that each inlined copy sees ONE address space (registers vs global_load, never flat)
-        tr = staged ? preprocess_view<WIN>(prm, cam, i, means3D, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
-                                           rotations, cov3D_precomp, geom, tile_row0, radii, WANT_J, gx, gy)
-                    : preprocess_view<WIN>(prm, cam, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
-                                           colors_precomp, opacities, scales, rotations, cov3D_precomp, geom, tile_row0, radii,
-                                           WANT_J, gx, gy);
+        o = staged ? preprocess_view<WIN>(prm, cam, i, means3D, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
+                                          rotations, cov3D_precomp, gx, gy)
+                   : preprocess_view<WIN>(prm, cam, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
+                                          colors_precomp, opacities, scales, rotations, cov3D_precomp, gx, gy);
+        tr = view_tile_rect(o, tile_row0);
     }
-    tile_histogram(s_box, s_cnt, tr, gx, tile_count, counters);      // (barriers inside: the slabs are dead now)
+    // the slab is dead now; the reservation's atomics are in flight while the records are stored
+    const TileResv rs = tile_reserve_issue(s_win, tr, gx, tile_count, tile_count2, vis_part);
+    if (i < prm.P) write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, WANT_J, cj);
+    tile_reserve_store(rs, resv + (size_t)(blockIdx.x * (kBlock / 64) + wave) * kResvStride);
 }
 
 // The same for KV views of ONE set of Gaussians in one pass (view-batched renders with shared geometry, d3ga.h: n_views): the
@@ -336,14 +370,15 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
     const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp, ViewCams<KV> cams, GeomBuf geom /* of the first view */,
-    uint32_t *__restrict__ tile_count, uint32_t *__restrict__ counters, int32_t *__restrict__ radii /* of the first view */,
+    uint32_t *__restrict__ tile_count, uint32_t *__restrict__ tile_count2, uint32_t *__restrict__ vis_part,
+    uint32_t *__restrict__ resv /* reservation records of the first view */, int32_t *__restrict__ radii /* of the first view */,
     int tile_row0, int gyv, size_t pv /* records between the views' geometry: 0 = k cameras of one set of Gaussians, P = a batch of frames */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_box[4];
     float *s_sh = reinterpret_cast<float *>(smem);
-    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(smem);
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6;
     const int i = blockIdx.x * kBlock + tid;
+    uint32_t *s_win = reinterpret_cast<uint32_t *>(smem) + wave * kShHalfSlab;      // the wavefront's slab, once the colours are formed
+    const size_t wpv = (size_t)gridDim.x * (kBlock / 64);                            // reservation records per view (resv_waves)
     // shared by the views: covariance row and opacity (in flight while the SH rows are staged)
     float pc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pop = 0.f;
     const bool pre = cov3D_precomp != nullptr && pv == 0;
@@ -358,17 +393,20 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
     staged_sh_colour_views<WANT_J, KV>(prm, means3D, pv, shs, cams, s_sh, cj);
     const int gx = (prm.W + kTile - 1) / kTile;
 #pragma unroll
-    for (int v = 0; v < KV; ++v) {
-        __syncthreads();                                        // the LDS region changes hands: slabs -> window, window -> window
+    for (int v = 0; v < KV; ++v) {                              // (the window is the wavefront's own: slab -> window -> window in program order)
         TileRect tr = {false, 0, 0, 0, 0};
+        PreOut o = {};
         if (i < prm.P) {
             const size_t og = pv * v;
-            tr = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, means3D + 3 * og, nullptr, true,
-                                        cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
-                                        rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr,
-                                        geom_view(geom, prm.P, v), tile_row0 + v * gyv, radii + (size_t)prm.P * v, WANT_J, gx, 0);
+            o = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, means3D + 3 * og, nullptr, true,
+                                       cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
+                                       rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, gx, 0);
+            tr = view_tile_rect(o, tile_row0 + v * gyv);
         }
-        tile_histogram(s_box, s_cnt, tr, gx, tile_count, counters);
+        const TileResv rs = tile_reserve_issue(s_win, tr, gx, tile_count, tile_count2, vis_part);
+        if (i < prm.P)
+            write_geom_records(geom_view(geom, prm.P, v), i, o, !cov3D_precomp, tile_row0 + v * gyv, radii + (size_t)prm.P * v, WANT_J, cj[v]);
+        tile_reserve_store(rs, resv + (wpv * v + blockIdx.x * (kBlock / 64) + wave) * kResvStride);
     }
 }
 
@@ -665,8 +703,8 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     const int64_t tiles = (int64_t)grid_x(prm) * gyv * views;
     const bool wnd = is_windowed(prm);
     BinBuf bin = carve_bin(binning, tiles, d_capacity);
-    // counters + tile_count are adjacent: one memset
-    D3GA_HIP(zero_async(bin.counters, 256 + align256(4 * tiles), s));
+    // counters + tile_count + tile_count2 + vis_part are adjacent: one clear
+    D3GA_HIP(zero_async(bin.counters, 256 + 2 * align256(4 * tiles) + 4 * kVisParts * kVisStride, s));
     if (wnd) hipLaunchKernelGGL(window_table_kernel, dim3((views + 63) / 64), dim3(64), 0, s, *prm, campos, views, win_table(binning, tiles, d_capacity));
     if (prm->P == 0) return D3GA_OK;          // empty scene: every per-Gaussian tensor is empty (NULL)
     if ((shs != nullptr) == (colors_precomp != nullptr)) return D3GA_E_CONFIG;
@@ -677,7 +715,9 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     if (shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M) return D3GA_E_CONFIG;
     if (!means3D || !opacities || !radii) return D3GA_E_NULL;
     const GeomBuf g = carve_geom(geom, (int64_t)prm->P * views);
-    const size_t lds = lds_bytes(staged(prm, shs), kShHalfLdsBytes, (size_t)kWinTiles * 4);
+    const size_t lds = lds_bytes(staged(prm, shs), kShHalfLdsBytes, (size_t)(kBlock / 64) * kResvStride * 4);
+    uint32_t *const resv = resv_records(binning, tiles, d_capacity, views, wnd);
+    const size_t resv_view = (size_t)resv_waves(prm->P) * kResvStride;                 // words between the views' records
     const bool want_j = leaves_dcol(prm, shs);
     const int cs = cam_stride(prm);
     // a batch of views writes view v's records at v P + i of the batch's buffers: grouped launches below when the SH row can be
@@ -696,7 +736,8 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
         hipLaunchKernelGGL((want_j ? preprocess_views_kernel<true, KV> : preprocess_views_kernel<false, KV>), grid, block, lds, s, *prm,
                            at(means3D, 3, og), shs, colors_precomp, opacities, at(scales, 3, og), at(rotations, 4, og),
                            at(cov3D_precomp, 6, og), view_cams<KV>(viewmatrix, projmatrix, campos, cs, v0, KV), geom_view(g, prm->P, v0),
-                           bin.tile_count, bin.counters, radii + (size_t)prm->P * v0, v0 * gyv, gyv, pv);
+                           bin.tile_count, bin.tile_count2, bin.vis_part, resv + resv_view * v0, radii + (size_t)prm->P * v0, v0 * gyv,
+                           gyv, pv);
         v0 += KV;
     };
     while (grouped && views - v0 >= 2) {
@@ -712,7 +753,8 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
         const size_t og = pv * v, oa = pa * v;
         hipLaunchKernelGGL(kernel, grid, block, lds, s, *prm, at(means3D, 3, og), shs, at(colors_precomp, 3, oa), opacities + oa,
                            at(scales, 3, og), at(rotations, 4, og), at(cov3D_precomp, 6, og), c.vm[0], c.pm[0], c.cp[0],
-                           geom_view(g, prm->P, v), bin.tile_count, bin.counters, radii + (size_t)prm->P * v, v * gyv);
+                           geom_view(g, prm->P, v), bin.tile_count, bin.tile_count2, bin.vis_part, resv + resv_view * v,
+                           radii + (size_t)prm->P * v, v * gyv);
     }
     return check_launch(s, prm->debug & 0xff);
 }
