@@ -79,8 +79,49 @@ constexpr int kShPassRows = 32;
 constexpr int kShHalfSlab = kShPassRows * kShRow;
 constexpr size_t kShHalfLdsBytes = (size_t)(kBlock / 64) * kShHalfSlab * sizeof(float);      // 26,624 B per block
 
-// sum_k Y_k(dir_i) * coeff_k of this thread's Gaussian, with the (P,M,3) block read through wavefront-private LDS: into acc, or
-// (WANT_J) into cj.a0..a2 with J = d(colour)/d(unit direction) (sh_accumulate_jacobian), from the same staged row.
+// The two passes of a full wavefront of full rows (M = 16) of the training forward, with `before` between the issue of half 0 and
+// its use: what the caller has to do that does not need the rows and may use the slab region, which is free until then
+// (preprocess_full_wavefront: projection and slot reservation; staged_sh_colour: the basis).
+// What the compiler makes of it (ISA of preprocess_kernel<true,false>): the six loads of half 0 are issued right behind the
+// caller's mean and opacity loads and are first waited for in front of their slab writes; half 1, issued in the source behind the
+// first pass, is six loads and their wait in front of the second pass (ahead of the first pass it costs 24 registers at the kernel's
+// peak, 93 -> 107 VGPRs, four wavefronts per SIMD).
+// SIX NAMED VALUES per half, not ShRegs: the loads of an array (sh_rows48_load) are sunk to their first use, behind `before` -- the
+// forward-only branch of staged_sh_colour relies on exactly that to stay at its 72 VGPRs (with the named values it has 86 and loses
+// two wavefronts per SIMD) -- while named values stay where the source has them.  Nothing else holds a load of a `const
+// __restrict__` argument in place that does not also change what the vectoriser packs, and with it the rounding (docs/LOG.md).
+#define D3GA_SH_HALF_ISSUE(H, SRC)                                                                                        \
+    const float4 *H##g = reinterpret_cast<const float4 *>(SRC) + lane;                                                     \
+    const float4 H##0 = H##g[0], H##1 = H##g[64], H##2 = H##g[128], H##3 = H##g[192], H##4 = H##g[256], H##5 = H##g[320];
+#define D3GA_SH_HALF_TO_SLAB(H)                                                                                           \
+    sh_row48_put(slab, lane, H##0); sh_row48_put(slab, lane + 64, H##1); sh_row48_put(slab, lane + 128, H##2);             \
+    sh_row48_put(slab, lane + 192, H##3); sh_row48_put(slab, lane + 256, H##4); sh_row48_put(slab, lane + 320, H##5);
+static_assert(kShPassRows * 12 / 64 == 6, "six 16-byte loads per lane and half");
+// 16-byte piece v of a block of full rows -> its place in the slab (as sh_rows48_to_slab)
+__device__ __forceinline__ void sh_row48_put(float *slab, int v, float4 x) {
+    const int e = 4 * v, row = e / 48, c = e - row * 48;
+    *reinterpret_cast<float4 *>(slab + row * kShRow + c) = x;
+}
+template <class Before, class Eval>
+__device__ __forceinline__ void sh_two_pass48(float *slab, const float *__restrict__ src, int lane, Before &&before, Eval &&eval) {
+    D3GA_SH_HALF_ISSUE(h0_, src)
+    before();
+    __builtin_amdgcn_wave_barrier();
+    D3GA_SH_HALF_TO_SLAB(h0_)
+    __builtin_amdgcn_wave_barrier();
+    if (lane / kShPassRows == 0) eval(slab + (lane % kShPassRows) * kShRow);
+    D3GA_SH_HALF_ISSUE(h1_, src + 48 * kShPassRows)
+    __builtin_amdgcn_wave_barrier();
+    D3GA_SH_HALF_TO_SLAB(h1_)
+    __builtin_amdgcn_wave_barrier();
+    if (lane / kShPassRows == 1) eval(slab + (lane % kShPassRows) * kShRow);
+}
+#undef D3GA_SH_HALF_ISSUE
+#undef D3GA_SH_HALF_TO_SLAB
+
+// sum_k Y_k(dir_i) * coeff_k of this thread's Gaussian (mean: its means3D row, loaded by the caller; any value for i >= P), with
+// the (P,M,3) block read through wavefront-private LDS: into acc, or (WANT_J) into cj.a0..a2 with J = d(colour)/d(unit direction)
+// (sh_accumulate_jacobian), from the same staged row.
 // SH colour in two PASSES over half of the wavefront's rows each (full 192-byte rows, so every byte is fetched once): the slab
 // of a wavefront is 32 x 52 floats, 6.5 KiB (20 resident wavefronts per CU; 64 rows would be 13 KiB and 12).  Round 4
 // measured 16 rows per pass (3.3 KiB: the tile window's 16 KiB is then the block's LDS, 28 wavefronts per CU, the launch's
@@ -90,9 +131,8 @@ constexpr size_t kShHalfLdsBytes = (size_t)(kBlock / 64) * kShHalfSlab * sizeof(
 // more than the occupancy returns (docs/LOG.md).  Only wavefront-private LDS is touched: no workgroup barrier, program order +
 // wave_barrier suffice.  Every thread of the block must call it.
 template <bool WANT_J>
-__device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, const float *__restrict__ means3D,
-                                                 const float *__restrict__ shs, const float *__restrict__ campos,
-                                                 float *s_sh, float acc[3], ShColJ &cj) {
+__device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, V3 mean, const float *__restrict__ shs,
+                                                 const float *__restrict__ campos, float *s_sh, float acc[3], ShColJ &cj) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * kBlock + tid;
     const int M3 = 3 * prm.M;
@@ -102,17 +142,25 @@ __device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, 
     const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
     float B[16];
     float dx = 0.f, dy = 0.f, dz = 1.f;
-    if (WANT_J && i < prm.P) sh_view_dir(means3D, i, campos, dx, dy, dz);
     auto eval = [&](const float *row) __attribute__((always_inline)) {
         if (WANT_J) cj = sh_accumulate_jacobian(B, dx, dy, dz, row, nb, cj);
         else sh_accumulate(B, row, 0, 16, nb, acc);
     };
     if (M3 == 48 && rows == 64) {                              // wave-uniform: a full wavefront of full rows
-        // both halves' loads are issued up front (the second half waits in registers while the first is evaluated)
+        if (WANT_J) {
+            sh_two_pass48(slab, shs + (size_t)48 * row0, lane, [&]() __attribute__((always_inline)) {
+                sh_view_dir(mean, campos, dx, dy, dz);
+                sh_basis(prm.sh_degree, dx, dy, dz, B);
+            }, eval);
+            return;
+        }
+        // Forward only, as it was: the source issues both halves up front as arrays, and the compiler sinks each to its use (six
+        // loads, their wait, the slab writes, the pass; then the same again) -- which keeps these light kernels at their occupancy:
+        // through sh_two_pass48 preprocess_kernel<false,.> has 86 VGPRs instead of 72 (7 -> 5 wavefronts per SIMD).
         const float *src = shs + (size_t)48 * row0;
         const ShRegs<kShPassRows> h0 = sh_rows48_load<kShPassRows>(src, lane);
         const ShRegs<kShPassRows> h1 = sh_rows48_load<kShPassRows>(src + 48 * kShPassRows, lane);
-        sh_view_basis(prm, means3D, i, campos, B);
+        sh_view_basis(prm, mean, campos, B);
         __builtin_amdgcn_wave_barrier();
         sh_rows48_to_slab<kShPassRows>(slab, h0, lane);
         __builtin_amdgcn_wave_barrier();
@@ -123,7 +171,8 @@ __device__ __forceinline__ void staged_sh_colour(const d3ga_raster_params &prm, 
         if (lane / kShPassRows == 1) eval(slab + (lane % kShPassRows) * kShRow);
         return;
     }
-    if (i < prm.P) sh_view_basis(prm, means3D, i, campos, B);
+    if (WANT_J && i < prm.P) sh_view_dir(mean, campos, dx, dy, dz);
+    if (i < prm.P) sh_view_basis(prm, mean, campos, B);
     for (int h = 0; h < 2; ++h) {
         const int r = min(kShPassRows, rows - kShPassRows * h);
         __builtin_amdgcn_wave_barrier();
@@ -139,9 +188,11 @@ __device__ __forceinline__ TileRect view_tile_rect(const PreOut &o, int tile_row
     const Splat &sp = o.sp;
     return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
 }
-// what preprocess leaves per Gaussian (GeomBuf records of ITS view, radius)
-__device__ __forceinline__ void write_geom_records(const GeomBuf &geom, int i, const PreOut &o, bool keep_cov, int tile_row0,
-                                                   int32_t *__restrict__ radii, bool want_j, const ShColJ &cj) {
+// what preprocess leaves per Gaussian (GeomBuf records of ITS view, radius), in two parts: what the projection alone decides, and
+// what needs the colour.  preprocess_kernel's full wavefronts store the first part before the SH passes, so that the splat does not
+// sit in registers through them; 1 / depth and the visibility are what the second part keeps of it.
+__device__ __forceinline__ float write_geom_records_splat(const GeomBuf &geom, int i, const PreOut &o, bool keep_cov, int tile_row0,
+                                                          int32_t *__restrict__ radii) {
     const Splat &sp = o.sp;
     if (keep_cov) {                         // (uniform) a precomputed covariance is read again from the caller's tensor
 #pragma unroll
@@ -158,9 +209,18 @@ __device__ __forceinline__ void write_geom_records(const GeomBuf &geom, int i, c
         const SplatCull sc = splat_cull(sp.conic[0], sp.conic[1], sp.conic[2], o.opacity);
         geom.xyh[i] = make_float4(sp.px, sp.py, sp.visible ? sc.hx : -1.0f, sc.hy);
     }
-    geom.rgb_invd[i] = make_float4(o.rgb[0], o.rgb[1], o.rgb[2], sp.visible ? 1.0f / sp.depth : 0.f);
-    geom.clamped[i] = o.clampmask;
+    return sp.visible ? 1.0f / sp.depth : 0.f;
+}
+__device__ __forceinline__ void write_geom_records_colour(const GeomBuf &geom, int i, float r, float g, float b, float invd,
+                                                           uint8_t clampmask, bool want_j, const ShColJ &cj) {
+    geom.rgb_invd[i] = make_float4(r, g, b, invd);
+    geom.clamped[i] = clampmask;
     if (want_j) dcol_store(geom.dcol, geom.dcol_stride, i, cj);
+}
+__device__ __forceinline__ void write_geom_records(const GeomBuf &geom, int i, const PreOut &o, bool keep_cov, int tile_row0,
+                                                   int32_t *__restrict__ radii, bool want_j, const ShColJ &cj) {
+    const float invd = write_geom_records_splat(geom, i, o, keep_cov, tile_row0, radii);
+    write_geom_records_colour(geom, i, o.rgb[0], o.rgb[1], o.rgb[2], invd, o.clampmask, want_j, cj);
 }
 
 // Windowed camera slot (d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): the splat was projected on the view's full raster; its tile rectangle
@@ -183,15 +243,23 @@ __global__ void window_table_kernel(d3ga_raster_params prm, const float *__restr
 }
 
 // Tile histogram (counting-sort pass 1) and slot reservation of ONE WAVEFRONT's Gaussians (d3ga_internal.h: reservation records),
-// in two steps so that the round trip of the returning atomics runs under the stores of the geometry records between them.
+// in two steps so that the round trip of the returning atomics runs under what the caller puts between them (preprocess_kernel's
+// full wavefronts: the SH passes and the record stores; otherwise the record stores alone).
 // s_win: kResvTiles words of LDS that only this wavefront touches (program order + wave_barrier order its accesses); every lane of
 // the wavefront must call both.
 struct TileResv { TileWindow win; uint32_t base[kResvSlots]; };
+template <bool SCALAR_WIN = false /* the caller carries the window through long code: keep it in scalar registers */>
 __device__ __forceinline__ TileResv tile_reserve_issue(uint32_t *s_win, const TileRect &t, int gx, uint32_t *__restrict__ tile_count,
                                                        uint32_t *__restrict__ tile_count2, uint32_t *__restrict__ vis_part) {
     const int lane = threadIdx.x & 63;
     TileResv r;
     r.win = wave_tile_window(t.visible, t.r0, t.r1, t.r2, t.r3);
+    // the same in every lane: told to the compiler, the window lives in scalar registers from here to tile_reserve_store (four
+    // vector registers less through the SH passes of preprocess_full_wavefront, which is what keeps it at five wavefronts per SIMD)
+    if constexpr (SCALAR_WIN) {
+    r.win.x0 = __builtin_amdgcn_readfirstlane(r.win.x0); r.win.y0 = __builtin_amdgcn_readfirstlane(r.win.y0);
+    r.win.w = __builtin_amdgcn_readfirstlane(r.win.w); r.win.h = __builtin_amdgcn_readfirstlane(r.win.h);
+    }
 #pragma unroll
     for (int j = 0; j < kResvSlots; ++j) r.base[j] = 0u;
     // the visible count: one popcount and one atomic per wavefront, spread over kVisParts cache lines that the scan workgroup sums.
@@ -240,9 +308,9 @@ __device__ __forceinline__ void tile_reserve_store(const TileResv &r, uint32_t *
 }
 
 // The per-view tail of both forward kernels: R1 of Gaussian i in view `cam` from what the kernel has in registers (staged: the SH
-// colour sum in cj.a0..a2; pre: the covariance row and raw opacity).  WIN: the rectangle is clipped to the window's gx x gy tiles.
+// colour sum in cj.a0..a2; pre: the covariance row and raw opacity; mean: its means3D row).  WIN: the rectangle is clipped to the window's gx x gy tiles.
 template <bool WIN>
-__device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D,
+__device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, V3 mean,
                                                     const float *sh_row, bool staged, const ShColJ &cj, bool pre, const float (&pc6)[6],
                                                     float pop, const float *colors_precomp, const float *opacities, const float *scales,
                                                     const float *rotations, const float *cov3D_precomp, int gx, int gy) {
@@ -252,9 +320,64 @@ __device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm,
 #pragma unroll
     for (int k = 0; k < 6; ++k) pl.c6[k] = pc6[k];
     pl.op = pop;
-    PreOut o = preprocess_one(prm, cam, i, means3D, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
+    pl.has_mean = true; pl.mean = mean;
+    PreOut o = preprocess_one(prm, cam, i, nullptr, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
     if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
     return o;
+}
+
+// A FULL wavefront of the training forward with full SH rows (M = 16) and precomputed covariances: Gaussian i = this lane's.
+// (Covariances from (scale, rotation) take the other order in preprocess_kernel: forming them here was the kernel's register peak.)
+// Source order: mean (one load), opacity, covariance row, SH half 0; the projection; the records that the projection alone decides;
+// tile histogram and the reservation's returning atomics -- nothing of that depends on SH, and the slab region is free to be the
+// tile window until the rows are copied into it (LDS operations of a wavefront execute in order); then the two SH passes, under
+// which the atomics return; colour records; reservation record.
+// Compiled (ISA, both WIN): mean, opacity and the six loads of half 0 are issued together; vmcnt(7) waits for the mean alone.  The
+// COVARIANCE ROW is not among them: the compiler sinks its two loads behind the near-plane test of the projection (the parent had
+// them in front of its SH staging), a dependent round trip whose wait, vmcnt(0), also takes in half 0 -- so half 0's latency hides
+// under the mean's and the covariance's round trips, not under the projection.  Then projection, eight returning atomics and the
+// record stores with nothing waited for, the slab writes of half 0 (vmcnt(10)..(5): the atomics stay out), first pass, half 1.
+// Per wavefront: mean | covariance (+ half 0) | half 1, against the parent's mean | half 0 | half 1 | mean again.  slab: its LDS.
+template <bool WIN>
+__device__ __forceinline__ void preprocess_full_wavefront(
+    const d3ga_raster_params &prm, const ViewCam &cam, const float *__restrict__ means3D, const float *__restrict__ shs,
+    const float *__restrict__ opacities, const float *__restrict__ cov3D_precomp, const float *__restrict__ campos, const GeomBuf &geom,
+    uint32_t *__restrict__ tile_count,
+    uint32_t *__restrict__ tile_count2, uint32_t *__restrict__ vis_part, uint32_t *__restrict__ rec, int32_t *__restrict__ radii,
+    int tile_row0, int gx, int gy, float *slab) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int i = blockIdx.x * kBlock + tid;
+    const int row0 = i - lane;
+    PreLoaded pl;
+    pl.has_sh = true; pl.has_c6 = true; pl.has_mean = true;
+    pl.mean = ld3(means3D, i);                 // ONE load per Gaussian: the projection and the direction both take the value
+    pl.op = opacities[i];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pl.c6[k] = cov3D_precomp[6 * (size_t)i + k];
+    const int nb = (prm.sh_degree + 1) * (prm.sh_degree + 1);
+    float B[16];
+    float dx, dy, dz, invd;
+    bool visible = false;
+    TileResv rs;
+    ShColJ cj = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    sh_two_pass48(slab, shs + (size_t)48 * row0, lane, [&]() __attribute__((always_inline)) {
+        PreOut o = preprocess_geom(prm, cam, i, pl.mean, opacities, nullptr, nullptr, cov3D_precomp, pl);
+        if constexpr (WIN) visible = o.sp.visible;   // before the window clip: what the colour is formed for
+        if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
+        rs = tile_reserve_issue<true>(reinterpret_cast<uint32_t *>(slab), view_tile_rect(o, tile_row0), gx, tile_count, tile_count2, vis_part);
+        invd = write_geom_records_splat(geom, i, o, false, tile_row0, radii);
+        sh_view_dir(pl.mean, campos, dx, dy, dz);
+        sh_basis(prm.sh_degree, dx, dy, dz, B);
+    }, [&](const float *row) __attribute__((always_inline)) {
+        cj = sh_accumulate_jacobian(B, dx, dy, dz, row, nb, cj);
+    });
+    pl.sh[0] = cj.a0; pl.sh[1] = cj.a1; pl.sh[2] = cj.a2;
+    float rgb[3] = {0.f, 0.f, 0.f};
+    uint8_t clampmask = 0;
+    if constexpr (!WIN) visible = invd != 0.f;   // (1 / depth of a visible Gaussian, 0 otherwise: one register less through the passes)
+    preprocess_colour(prm, cam, i, pl.mean, nullptr, nullptr, pl, visible, rgb, clampmask);
+    write_geom_records_colour(geom, i, rgb[0], rgb[1], rgb[2], invd, clampmask, true, cj);
+    tile_reserve_store(rs, rec);
 }
 
 // WIN: windowed camera slot (campos: 9 floats, d3ga.h): project with the view's raster size, histogram over the window's tiles
@@ -269,7 +392,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     int tile_row0 /* view-batched renders: this view's first tile row in the batch's grid (d3ga.h: n_views); else 0 */) {
     const ViewCam cam = view_cam(prm, viewmatrix, projmatrix, campos, WIN);
     const int gx = (prm.W + kTile - 1) / kTile + (WIN ? 1 : 0), gy = (prm.H + kTile - 1) / kTile + 1;   // (WIN) the window's grid
-    // one dynamic LDS region per wavefront, used first as its SH staging slab and then as its tile window: no workgroup barrier
+    // one dynamic LDS region per wavefront, its tile window and its SH staging slab in turn: no workgroup barrier
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_sh = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x, wave = tid >> 6;
@@ -277,34 +400,48 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const int M3 = 3 * prm.M;
     const bool staged = shs != nullptr && sh_staged(prm.M);
     uint32_t *s_win = reinterpret_cast<uint32_t *>(smem) + wave * (staged ? kShHalfSlab : kResvStride);
-    // covariance row and opacity: in flight while the SH rows are staged
+    uint32_t *const rec = resv + (size_t)(blockIdx.x * (kBlock / 64) + wave) * kResvStride;
+    const int row0 = blockIdx.x * kBlock + wave * 64;           // first Gaussian of this wavefront
+    // (Training forward with precomputed covariances only.  The forward-only kernel is lighter in its SH passes: carrying the reservation's bases and 1 / depth
+    // through them costs it registers, 71 -> 85 VGPRs and from 7 to 5 wavefronts per SIMD.  It keeps the order below.)
+    if (WANT_J && staged && cov3D_precomp && M3 == 48 && prm.P - row0 >= 64) {   // wave-uniform: a full wavefront of full rows (M = 16)
+        preprocess_full_wavefront<WIN>(prm, cam, means3D, shs, opacities, cov3D_precomp, campos, geom, tile_count, tile_count2, vis_part, rec,
+                                       radii, tile_row0, gx, gy, s_sh + wave * kShHalfSlab);
+        return;
+    }
+    // mean (ONE load per Gaussian: the direction and the projection both take the value), covariance row and opacity
+    V3 mean = v3(0.f, 0.f, 0.f);
     float pc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pop = 0.f;
     const bool pre = staged && cov3D_precomp != nullptr;
-    if (pre && i < prm.P) {
+    if (i < prm.P) {
+        mean = ld3(means3D, i);
+        if (pre) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) pc6[k] = cov3D_precomp[6 * (size_t)i + k];
-        pop = opacities[i];
+            for (int k = 0; k < 6; ++k) pc6[k] = cov3D_precomp[6 * (size_t)i + k];
+            pop = opacities[i];
+        }
     }
     ShColJ cj = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float acc[3] = {0.f, 0.f, 0.f};
+    // every other wavefront (partial, M != 16, unstaged colours): colour first, then the projection and the reservation
     if (staged) {
-        staged_sh_colour<WANT_J>(prm, means3D, shs, campos, s_sh, acc, cj);
+        staged_sh_colour<WANT_J>(prm, mean, shs, campos, s_sh, acc, cj);
         if (!WANT_J) { cj.a0 = acc[0]; cj.a1 = acc[1]; cj.a2 = acc[2]; }
     }
     TileRect tr = {false, 0, 0, 0, 0};
     PreOut o = {};
     if (i < prm.P) {
         // two call sites so that each inlined copy sees ONE address space (registers vs global_load, never flat)
-        o = staged ? preprocess_view<WIN>(prm, cam, i, means3D, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
+        o = staged ? preprocess_view<WIN>(prm, cam, i, mean, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
                                           rotations, cov3D_precomp, gx, gy)
-                   : preprocess_view<WIN>(prm, cam, i, means3D, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
+                   : preprocess_view<WIN>(prm, cam, i, mean, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
                                           colors_precomp, opacities, scales, rotations, cov3D_precomp, gx, gy);
         tr = view_tile_rect(o, tile_row0);
     }
     // the slab is dead now; the reservation's atomics are in flight while the records are stored
     const TileResv rs = tile_reserve_issue(s_win, tr, gx, tile_count, tile_count2, vis_part);
     if (i < prm.P) write_geom_records(geom, i, o, !cov3D_precomp, tile_row0, radii, WANT_J, cj);
-    tile_reserve_store(rs, resv + (size_t)(blockIdx.x * (kBlock / 64) + wave) * kResvStride);
+    tile_reserve_store(rs, rec);
 }
 
 // The same for KV views of ONE set of Gaussians in one pass (view-batched renders with shared geometry, d3ga.h: n_views): the
@@ -398,7 +535,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
         PreOut o = {};
         if (i < prm.P) {
             const size_t og = pv * v;
-            o = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, means3D + 3 * og, nullptr, true,
+            o = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, ld3(means3D + 3 * og, i), nullptr, true,
                                        cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
                                        rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, gx, 0);
             tr = view_tile_rect(o, tile_row0 + v * gyv);
@@ -426,7 +563,7 @@ __global__ __launch_bounds__(kBlock) void recolor_kernel(d3ga_raster_params prm,
     const bool staged = shs != nullptr && sh_staged(prm.M);
     ShColJ cj = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float acc[3] = {0.f, 0.f, 0.f};
-    if (staged) staged_sh_colour<WANT_J>(prm, means3D, shs, campos, s_sh, acc, cj);
+    if (staged) staged_sh_colour<WANT_J>(prm, i < prm.P ? ld3(means3D, i) : v3(0.f, 0.f, 0.f), shs, campos, s_sh, acc, cj);
     if (i >= prm.P) return;
     if (WANT_J) {
         acc[0] = cj.a0; acc[1] = cj.a1; acc[2] = cj.a2;

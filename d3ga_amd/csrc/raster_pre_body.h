@@ -16,20 +16,26 @@ struct PreOut {
     uint8_t clampmask;
 };
 
-// The unit view direction of Gaussian i: normalize(mean - campos), as in R1.  Without contraction, like sh_basis: the
+// The unit view direction of a Gaussian: normalize(mean - campos), as in R1.  Without contraction, like sh_basis: the
 // inference forward and the forward that also leaves d(colour)/d(direction) must evaluate the same basis values.
-D3GA_HD void sh_view_dir(const float *means3D, int i, const float *campos, float &x, float &y, float &z) {
+// By value: the kernels load the mean once and hand it to the direction and to the projection; the pointer forms load it.
+D3GA_HD void sh_view_dir(V3 m, const float *campos, float &x, float &y, float &z) {
     D3GA_NO_CONTRACT
-    const V3 m = ld3(means3D, i);
     const float dx = m.x - campos[0], dy = m.y - campos[1], dz = m.z - campos[2];
     const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
     x = dx * inv; y = dy * inv; z = dz * inv;
 }
-// SH basis of Gaussian i's view direction
-D3GA_HD void sh_view_basis(const d3ga_raster_params &prm, const float *means3D, int i, const float *campos, float B[16]) {
+D3GA_HD void sh_view_dir(const float *means3D, int i, const float *campos, float &x, float &y, float &z) {
+    sh_view_dir(ld3(means3D, i), campos, x, y, z);
+}
+// SH basis of a Gaussian's view direction
+D3GA_HD void sh_view_basis(const d3ga_raster_params &prm, V3 m, const float *campos, float B[16]) {
     float x, y, z;
-    sh_view_dir(means3D, i, campos, x, y, z);
+    sh_view_dir(m, campos, x, y, z);
     sh_basis(prm.sh_degree, x, y, z, B);
+}
+D3GA_HD void sh_view_basis(const d3ga_raster_params &prm, const float *means3D, int i, const float *campos, float B[16]) {
+    sh_view_basis(prm, ld3(means3D, i), campos, B);
 }
 // acc[c] += sum_k B[k] * coeff[k][c]  AND  J[3 dir + c] = sum_k dY_k/d(dir)(x, y, z) * coeff[k][c] -- the derivative of the
 // (unclamped, un-offset) SH colour w.r.t. the unit direction -- in ONE walk over the row: every coefficient is read once and
@@ -137,15 +143,18 @@ D3GA_HD void dcol_store(float *dcol, int64_t stride, size_t j, const ShColJ &c) 
 // memory -- 69 scratch instructions in the kernel and a dependent memory round trip in front of the colour).
 struct PreLoaded {
     bool has_sh = false, has_c6 = false;   // uniform over the launch
+    bool has_mean = false;                 // uniform over the launch: `mean` is means3D[i], loaded by the caller (once per Gaussian)
     float sh[3] = {0.f, 0.f, 0.f};         // sum_k Y_k(dir) * coeff_k, already evaluated (sh_view_basis / sh_accumulate)
     float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float op = 0.f;                        // raw opacity (with has_c6)
+    V3 mean = {0.f, 0.f, 0.f};
 };
-D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D, const float *sh_row,
-                              const float *colors_precomp, const float *opacities, const float *scales,
-                              const float *rotations, const float *cov3D_precomp, const PreLoaded pl = PreLoaded()) {
+// R1 in two steps, so that a kernel can run the projection (and what hangs on the tile rectangle) while the SH rows are still
+// in flight: preprocess_geom is everything that needs mean, covariance, opacity and camera only; preprocess_colour fills in
+// rgb / clampmask of a visible Gaussian.  preprocess_one is the two in a row.
+D3GA_HD PreOut preprocess_geom(const d3ga_raster_params &prm, const ViewCam &cam, int i, V3 mean, const float *opacities,
+                               const float *scales, const float *rotations, const float *cov3D_precomp, const PreLoaded &pl) {
     PreOut o;
-    const V3 mean = ld3(means3D, i);
     const float raw_opacity = pl.has_c6 ? pl.op : opacities[i];
     if (pl.has_c6) {
         for (int k = 0; k < 6; ++k) o.c6[k] = pl.c6[k];
@@ -171,24 +180,37 @@ D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, const ViewCam &cam,
         return o;
     }
     o.opacity *= o.sp.aa;                    // antialiasing (branch dr_aa): what the compositing stage sees is opacity x h_convolution_scaling
+    return o;
+}
+// visible: o.sp.visible as preprocess_geom left it (a window clip behind it does not count)
+D3GA_HD void preprocess_colour(const d3ga_raster_params &prm, const ViewCam &cam, int i, V3 mean, const float *sh_row,
+                               const float *colors_precomp, const PreLoaded &pl, bool visible, float (&rgb)[3], uint8_t &clampmask) {
+    if (!visible) return;
     if (colors_precomp) {
-        o.rgb[0] = colors_precomp[3 * (size_t)i]; o.rgb[1] = colors_precomp[3 * (size_t)i + 1];
-        o.rgb[2] = colors_precomp[3 * (size_t)i + 2];
+        rgb[0] = colors_precomp[3 * (size_t)i]; rgb[1] = colors_precomp[3 * (size_t)i + 1];
+        rgb[2] = colors_precomp[3 * (size_t)i + 2];
     } else {
         float acc[3] = {0.f, 0.f, 0.f};
         if (pl.has_sh) {
             acc[0] = pl.sh[0]; acc[1] = pl.sh[1]; acc[2] = pl.sh[2];
         } else {
             float B[16];
-            sh_view_basis(prm, means3D, i, cam.cp, B);
+            sh_view_basis(prm, mean, cam.cp, B);
             sh_accumulate(B, sh_row, 0, 16, (prm.sh_degree + 1) * (prm.sh_degree + 1), acc);
         }
         for (int c = 0; c < 3; ++c) {
             const float v = acc[c] + 0.5f;
-            if (v < 0.f) o.clampmask |= (uint8_t)(1u << c);
-            o.rgb[c] = fmaxf(v, 0.f);
+            if (v < 0.f) clampmask |= (uint8_t)(1u << c);
+            rgb[c] = fmaxf(v, 0.f);
         }
     }
+}
+D3GA_HD PreOut preprocess_one(const d3ga_raster_params &prm, const ViewCam &cam, int i, const float *means3D, const float *sh_row,
+                              const float *colors_precomp, const float *opacities, const float *scales,
+                              const float *rotations, const float *cov3D_precomp, const PreLoaded pl = PreLoaded()) {
+    const V3 mean = pl.has_mean ? pl.mean : ld3(means3D, i);
+    PreOut o = preprocess_geom(prm, cam, i, mean, opacities, scales, rotations, cov3D_precomp, pl);
+    preprocess_colour(prm, cam, i, mean, sh_row, colors_precomp, pl, o.sp.visible, o.rgb, o.clampmask);
     return o;
 }
 
