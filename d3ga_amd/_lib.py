@@ -215,6 +215,14 @@ _SIGNATURES = {
     "d3ga_skeleton_bwd": ([_sk] + [ctypes.c_int32] * 4 + [_vp, _f, ctypes.c_int32] + [_vp] * 8 + [_vp], _i),
     "d3ga_skeleton_mats_fwd": ([ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
     "d3ga_skeleton_mats_bwd": ([ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
+    "d3ga_vgg_panel_bytes": ([ctypes.c_int32, ctypes.c_int32], _i64),
+    "d3ga_vgg_pack_weights": ([ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp], _i),
+    "d3ga_vgg_conv3x3": ([ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_int32] * 2 + [_vp, _vp], _i),
+    "d3ga_vgg_maxpool2_fwd": ([ctypes.c_int32] * 3 + [_vp, _vp, _vp], _i),
+    "d3ga_vgg_maxpool2_bwd": ([ctypes.c_int32] * 3 + [_vp, _vp, _vp, _vp], _i),
+    "d3ga_vgg_box_down2_fwd": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
+    "d3ga_vgg_box_down2_bwd": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
+    "d3ga_vgg_scratch_bytes": ([ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

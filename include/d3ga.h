@@ -28,7 +28,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 112 /* the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* (the d3ga_vgg_* entry points were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -972,6 +972,45 @@ int d3ga_skeleton_bwd(const d3ga_skeleton *model, int32_t B, int32_t n_sets, int
 int d3ga_skeleton_mats_fwd(int32_t B, int32_t J, const float *bind, const float *states, float *mats, d3ga_stream_t stream);
 int d3ga_skeleton_mats_bwd(int32_t B, int32_t J, const float *bind, const float *states, const float *g_mats, float *g_states,
                            d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * VGG19 perceptual loss.  Replaces utils/loss_utils.py:109-160 VGGLoss (train.py:212-214): the 2x2 box downsize,
+ * conv1_1 .. conv5_1 with ReLU and four 2x2 max pools, and an L1 mean per feature tap (d3ga_l1_mean_fwd_ws / _bwd above).
+ * The weights are frozen: only input gradients exist.  Activations are channels-last (H, W, C) float32; the image is (C, H, W).
+ * No entry point allocates or synchronises; all are capturable.  Every size is checked before any launch: H, W, C >= 1 and
+ * H W C <= INT32_MAX (else D3GA_E_SIZE), required pointers (D3GA_E_NULL), alignment and flags (D3GA_E_CONFIG).
+ *
+ * d3ga_vgg_panel_bytes(cin, cout): bytes of the packed weights of a convolution GEMM with cin inputs and cout outputs (three
+ *   bf16 planes, K and N padded to the MFMA tile; csrc/perceptual_math.h has the slot map).  < 0: D3GA_E_SIZE.
+ * d3ga_vgg_pack_weights: weight (w_cout, w_cin, 3, 3) -> panel, once per weight set.  transposed = 0: the forward panel
+ *   (d3ga_vgg_panel_bytes(w_cin, w_cout)); transposed = 1: the flipped, transposed panel of the input gradient
+ *   (d3ga_vgg_panel_bytes(w_cout, w_cin)).  panel 16-byte aligned.
+ * d3ga_vgg_conv3x3: y (H,W,cout) = [accumulate ? y : 0] + act( conv3x3(x', panel) + bias ), stride 1, zero padding 1, with
+ *   x' = x (H,W,cin), or x (.) [mask_y > 0] when mask_y (H,W,cin) is given; act = ReLU when relu = 1; bias (cout) | NULL.
+ *   Forward: (x, NULL, forward panel, bias, relu 1).  Input gradient of the layer that produced Y: (dY, Y, transposed panel,
+ *   NULL, relu 0) with cin = the layer's output width.  f32-equivalent arithmetic (three-piece bf16 split, six products).
+ *   x, mask_y, panel 16-byte aligned; y must not alias x or mask_y (D3GA_E_CONFIG).
+ * d3ga_vgg_maxpool2_fwd / _bwd: 2x2, stride 2, floor; x (H,W,C) -> y (H/2,W/2,C); gx (H,W,C) from gy: the window's first
+ *   maximum in row-major order takes the gradient (torch's rule), the dropped odd row / column exact zeros.  H, W >= 2.
+ * d3ga_vgg_box_down2_fwd / _bwd: img (C,H,W) -> out (H/2,W/2,C) = the 2x2 box mean of img[:, :2(H/2), :2(W/2)] -- what
+ *   F.interpolate(scale_factor=0.5, mode="bilinear") computes -- or, with down = 0, the transpose to channels-last alone (the
+ *   reference passes a 512 x 512 image unchanged).  bwd: g (out's shape) -> g_img (C,H,W), zeros in a dropped row / column.
+ * d3ga_vgg_scratch_bytes (host): for a (3,H,W) image, halved first by d3ga_vgg_box_down2_fwd if down = 1, n_layers taps (1..5, else D3GA_E_CONFIG) and 13 conv widths (NULL:
+ *   VGG19's), out[0] = bytes of the source activations and per-tap L1 gradients kept for the backward, out[1] = bytes of the forward's work area
+ *   (target ping-pong, D3GA_LOSS_PARTIALS, tap means), out[2] = bytes of the backward's gradient ping-pong; every tensor
+ *   inside starts on a 256-byte boundary, in the order d3ga_amd/perceptual.py carves them.  An image too small for the
+ *   pools of the chain: D3GA_E_SIZE.
+ * ------------------------------------------------------------------------------------------------------- */
+int64_t d3ga_vgg_panel_bytes(int32_t cin, int32_t cout);
+int d3ga_vgg_pack_weights(int32_t w_cout, int32_t w_cin, const float *weight, int32_t transposed, void *panel,
+                          d3ga_stream_t stream);
+int d3ga_vgg_conv3x3(int32_t H, int32_t W, int32_t cin, int32_t cout, const float *x, const float *mask_y, const void *panel,
+                     const float *bias, int32_t relu, int32_t accumulate, float *y, d3ga_stream_t stream);
+int d3ga_vgg_maxpool2_fwd(int32_t H, int32_t W, int32_t C, const float *x, float *y, d3ga_stream_t stream);
+int d3ga_vgg_maxpool2_bwd(int32_t H, int32_t W, int32_t C, const float *x, const float *gy, float *gx, d3ga_stream_t stream);
+int d3ga_vgg_box_down2_fwd(int32_t C, int32_t H, int32_t W, int32_t down, const float *img, float *out, d3ga_stream_t stream);
+int d3ga_vgg_box_down2_bwd(int32_t C, int32_t H, int32_t W, int32_t down, const float *g, float *g_img, d3ga_stream_t stream);
+int d3ga_vgg_scratch_bytes(int32_t H, int32_t W, int32_t down, int32_t n_layers, const int32_t *widths, int64_t *out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
