@@ -25,6 +25,7 @@ EVAL_BG_WHITE, EVAL_COMPOSED, EVAL_ALPHA3, EVAL_BOUNDARY_F32 = 1, 2, 4, 8
 EVAL_MAX_PARTIALS = 2048  # D3GA_EVAL_MAX_PARTIALS: d3ga_eval_partials(H, W) never exceeds it
 MESH_MAX_SIDE = 16384    # D3GA_MESH_MAX_SIDE (include/d3ga.h): the largest frame side the mesh rasterizer accepts
 MESH_CAM_FLOATS = 16     # D3GA_MESH_CAM_FLOATS: R row-major, t, fx, fy, cx, cy
+POINTS_MAX_K = 8         # D3GA_POINTS_MAX_K: the most points the point-cloud rasterizer keeps per pixel
 OPTIM_CHUNK = 8192      # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
 OPTIM_ALIGNED16 = 1      # D3GA_OPTIM_ALIGNED16: flag of a chunk whose four pointers are 16-byte aligned
 
@@ -205,6 +206,9 @@ _SIGNATURES = {
     "d3ga_mesh_shade_flat": ([ctypes.c_int32] * 5 + [_vp] * 6 + [ctypes.POINTER(ctypes.c_float), _vp] + [_vp], _i),
     "d3ga_mesh_vertex_normals": ([ctypes.c_int32] * 3 + [_vp] * 5 + [_vp], _i),
     "d3ga_mesh_maps": ([ctypes.c_int32] * 5 + [_vp] * 10 + [_vp], _i),
+    "d3ga_points_raster_scratch_bytes": ([ctypes.c_int32] * 4 + [_f, ctypes.POINTER(ctypes.c_size_t)], _i),
+    "d3ga_points_rasterize": ([ctypes.c_int32] * 5 + [_f] + [_vp] * 6 + [_vp], _i),
+    "d3ga_points_composite": ([ctypes.c_int32] * 5 + [_f] + [_vp] * 3 + [ctypes.POINTER(ctypes.c_float), _vp] + [_vp], _i),
     "d3ga_optim_scratch_bytes":([ctypes.c_int32] * 3 + [ctypes.POINTER(_i64)], _i),
     "d3ga_optim_clip_adam_step": ([_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp], _i),
     "d3ga_body_model_scratch_bytes": ([_bm, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i),

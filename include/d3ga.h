@@ -762,6 +762,37 @@ int d3ga_mesh_maps(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const 
                    float *normal, float *depth, float *mask, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Point-cloud view: the reference's recorder/pc_renderer.py::PCRenderer (a pytorch3d PointsRasterizer that keeps the K
+ * nearest points of every pixel, + AlphaCompositor) for B clouds of P points, one camera each.  Forward only.  Semantics:
+ * DESIGN.md 4.4h.
+ *   points (B,P,3) f32 world space;  cams (B,D3GA_MESH_CAM_FLOATS) f32 as for the mesh rasterizer above, same projection and
+ *   pixel centres;  radius: of a point's disc in NDC units, the shorter image side spanning [-1, 1] (radius min(H, W) / 2
+ *   pixels);  K: points kept per pixel, 1 .. D3GA_POINTS_MAX_K.
+ * d3ga_points_rasterize: a point at z <= 0.01 (or not finite) is dropped.  dist2 = ((i + 0.5 - u)^2 + (j + 0.5 - v)^2)
+ *   (2 / min(H, W))^2; a point belongs to a pixel iff dist2 < radius^2.  Per pixel the K members with the smallest view depth
+ *   z, equal depths by ascending index (the total order float_bits(z) << 32 | index: bit-reproducible, whatever the order of the
+ *   points), nearest first: idx (B,H,W,K) int32, the index into the cloud, zbuf (B,H,W,K) f32 = z, dists (B,H,W,K) f32 = dist2;
+ *   -1 in the empty slots; zbuf and dists optional.
+ *   scratch: d3ga_points_raster_scratch_bytes bytes, 16-byte aligned, contents irrelevant before the call.  It holds the
+ *   per-tile lists, sized by a closed-form bound on the 16 x 16 tiles a disc can touch: they cannot overflow.
+ *   Launches: clear, count, two scans, scatter, one 256-lane workgroup per (view, tile).
+ * d3ga_points_composite: image (B,H,W,3) f32 from idx and dists: sum_k w_k f_k prod_{j<k} (1 - w_j) over the filled slots with
+ *   w_k = 1 - dists_k / radius^2 and f the point's colour, colors (B,P,3) f32 or NULL: (154, 205, 50) / 255; bg (3 floats, HOST
+ *   memory, read by the call) only where slot 0 is empty: a covered pixel is not blended with the background.
+ *   Status, nothing launched: a negative size, H or W outside [1, D3GA_MESH_MAX_SIDE], B P >= 2^31 or lists beyond 2^36
+ *   records D3GA_E_SIZE; K outside [1, D3GA_POINTS_MAX_K] or a radius that is not positive and finite D3GA_E_CONFIG; a required
+ *   pointer NULL (points with P > 0, cams, scratch, idx; idx, dists, bg, image) D3GA_E_NULL; a pointer not aligned to its
+ *   element (scratch: 16 bytes) D3GA_E_CONFIG.  B = 0 and P = 0 are valid (P = 0: background only).  No host
+ *   synchronisation; capturable.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_POINTS_MAX_K 8
+int d3ga_points_raster_scratch_bytes(int32_t B, int32_t P, int32_t H, int32_t W, float radius, size_t *bytes);
+int d3ga_points_rasterize(int32_t B, int32_t P, int32_t H, int32_t W, int32_t K, float radius, const float *points,
+                          const float *cams, void *scratch, int32_t *idx, float *zbuf, float *dists, d3ga_stream_t stream);
+int d3ga_points_composite(int32_t B, int32_t P, int32_t H, int32_t W, int32_t K, float radius, const int32_t *idx,
+                          const float *dists, const float *colors, const float *bg, float *image, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimizer step, models/trainer.py:188-189: clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() for every
  * parameter in THREE launches whatever the number of tensors (two with clipping off).  The tensors are described by tables
  * that the caller builds once per set of addresses, in device memory or in pinned host memory mapped to the device (read by
