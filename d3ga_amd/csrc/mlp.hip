@@ -1114,13 +1114,13 @@ static int mlp_wgrad_launch(int32_t P, int32_t N, int32_t K, const float *dpre, 
     if (P < 0 || N < 1 || N > 128 || K < 1 || K > 128) return D3GA_E_SIZE;
     if (!dW) return D3GA_E_NULL;
     if ((int64_t)P * N >= (1ll << 31) || (int64_t)P * K >= (1ll << 31)) return D3GA_E_SIZE;
+    if (P > 0 && (!dpre || !X)) return D3GA_E_NULL;                    // every refusal before the first memset or launch
     hipStream_t s = (hipStream_t)stream;
     if (zero_first) {
         D3GA_HIP(zero_async(dW, sizeof(float) * (size_t)N * K, s));
         if (db) D3GA_HIP(zero_async(db, sizeof(float) * (size_t)N, s));
     }
     if (P == 0) return D3GA_OK;
-    if (!dpre || !X) return D3GA_E_NULL;
     const int NBn = (N + 31) / 32, NBk = (K + 31) / 32;
     int grid = 256;                                                   // row ranges; every workgroup ends with N*K atomics
     int rows = (P + grid - 1) / grid;
@@ -1238,6 +1238,11 @@ extern "C" int d3ga_mlp_chain_fwd(int32_t P, int32_t K0, const float *X, int32_t
     // shapes the kernel is built for (everything else: the per-layer kernels): >= 2 layers, all but the last 128 wide
     if (L < 2) return D3GA_E_CONFIG;
     for (int l = 0; l + 1 < L; ++l) if (Ns[l] != 128) return D3GA_E_CONFIG;
+    // the backward's chain: no bias, no activation, no sign output anywhere -- its own instantiation without that arithmetic
+    bool bwd = masks != nullptr;
+    for (int l = 0; l < L && bwd; ++l) bwd = !signs[l] && slopes[l] == 1.f && !(biases && biases[l]);
+    if (masks && !bwd)                                     // masks together with bias / activation / sign output: not built
+        for (int l = 0; l < L; ++l) if (masks[l]) return D3GA_E_CONFIG;      // (before the bias launch: a refused call writes nothing)
     const int ntl = (Ns[L - 1] + 31) / 32;
     const int abl = debug_knob(D3GA_KNOB_CHAIN_ABL);      // timing ablations (wrong results)
     a.abl = abl;
@@ -1253,17 +1258,12 @@ extern "C" int d3ga_mlp_chain_fwd(int32_t P, int32_t K0, const float *X, int32_t
         for (const void *k : ks) D3GA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr[dev] = true;
     }
-    // the backward's chain: no bias, no activation, no sign output anywhere -- its own instantiation without that arithmetic
-    bool bwd = masks != nullptr;
-    for (int l = 0; l < L && bwd; ++l) bwd = !signs[l] && slopes[l] == 1.f && !(biases && biases[l]);
     // this call's biases into the panels' tails.  (The BWD instantiation never reads a bias -- the tail still rides along with the
     // panel's DMA, whatever it holds: no launch for it, 5.7 us x 3 chains per colour step.)
     if (!bwd) hipLaunchKernelGGL(chain_bias_kernel, dim3(L), dim3(128), 0, s, ba);
     const int nblocks = (P + kChainRows - 1) / kChainRows;
     const int grid_cap = debug_knob(D3GA_KNOB_CHAIN_GRID) > 0 ? debug_knob(D3GA_KNOB_CHAIN_GRID) : 2048 / kChainWaves;
     const dim3 grid(nblocks < grid_cap ? nblocks : grid_cap), block(kChainThreads);
-    if (masks && !bwd)                                     // masks together with bias / activation / sign output: not built
-        for (int l = 0; l < L; ++l) if (masks[l]) return D3GA_E_CONFIG;
     if (bwd) {
         if (ntl == 1) hipLaunchKernelGGL((chain_fwd_kernel<1, true>), grid, block, lds, s, P, K0, X, a);
         else if (ntl == 2) hipLaunchKernelGGL((chain_fwd_kernel<2, true>), grid, block, lds, s, P, K0, X, a);

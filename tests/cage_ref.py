@@ -1,6 +1,7 @@
 """Float64 side of tests/test_gpu_cage_paths.py: random cage bindings, the oracle chain lbs_cage -> cage_deform (oracle.deform)
-with every gradient, the element-wise bars of test_cage_deform_fuzz, and output buffers with guard bands.  CPU only, no GPU call
-in here except GuardedBuffer's allocation."""
+with every gradient, the element-wise bars of test_cage_deform_fuzz, and output buffers with guard bands (float32: GuardedBuffer;
+uint32 words: GuardedWords, also used by tests/test_gpu_mlp_paths.py).  CPU only, no GPU call in here except the guarded
+buffers' allocation and checks."""
 import numpy as np
 import torch
 
@@ -140,22 +141,41 @@ def float32_order_spread(c, *, exp, dbary):
 class GuardedBuffer:
     """An output (shape, float32) in the middle of a larger device buffer filled with a NaN bit pattern: `t` is the output,
     `check()` asserts that the GUARD floats on either side still hold the pattern and that the output holds no NaN,
-    `untouched()` that nothing at all was written."""
+    `untouched()` that nothing at all was written.  skew: the output starts that many elements later (skew = 1: an output that
+    is 4-byte but not 8- or 16-byte aligned); the skipped elements belong to the front guard."""
 
-    def __init__(self, name, shape, dev):
+    def __init__(self, name, shape, dev, skew=0):
         self.name, n = name, int(np.prod(shape))
-        self.raw = torch.full((n + 2 * GUARD,), FILL, dtype=torch.int32, device=dev)
-        self.t = self.raw[GUARD:GUARD + n].view(torch.float32).view(shape)
+        self.lo = GUARD + skew
+        self.raw = torch.full((n + 2 * GUARD + skew,), FILL, dtype=torch.int32, device=dev)
+        self.t = self.raw[self.lo:self.lo + n].view(torch.float32).view(shape)
 
     def ptr(self):
         return self.t.data_ptr()
 
     def check(self):
-        raw = self.raw.cpu()
-        n = raw.numel() - 2 * GUARD
-        assert bool((raw[:GUARD] == FILL).all()), f"{self.name}: written before its first element"
-        assert bool((raw[GUARD + n:] == FILL).all()), f"{self.name}: written past its last element"
+        raw = self.raw                                     # (compared where it lives: three flags cross to the host, not the buffer)
+        n = raw.numel() - self.lo - GUARD
+        assert bool((raw[:self.lo] == FILL).all()), f"{self.name}: written before its first element"
+        assert bool((raw[self.lo + n:] == FILL).all()), f"{self.name}: written past its last element"
         assert not bool(torch.isnan(self.t).any()), f"{self.name}: elements left unwritten (or NaN)"
 
     def untouched(self):
         assert bool((self.raw == FILL).all().cpu()), f"{self.name}: written by a refused call"
+
+
+class GuardedWords(GuardedBuffer):
+    """The integer variant (shape, int32 holding uint32 bit patterns): sign words, packed weight panels.  `check()` asserts the
+    guards and that no word of the output still holds the fill pattern (first: only that many leading words must be written)."""
+
+    def __init__(self, name, shape, dev, skew=0):
+        super().__init__(name, shape, dev, skew)
+        self.t = self.t.view(torch.int32)
+
+    def check(self, first=None):
+        raw = self.raw
+        n = raw.numel() - self.lo - GUARD
+        assert bool((raw[:self.lo] == FILL).all()), f"{self.name}: written before its first word"
+        assert bool((raw[self.lo + n:] == FILL).all()), f"{self.name}: written past its last word"
+        body = raw[self.lo:self.lo + (n if first is None else first)]
+        assert not bool((body == FILL).any()), f"{self.name}: words left unwritten"

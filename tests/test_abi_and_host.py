@@ -571,3 +571,33 @@ def test_field_ref_closed_forms_agree_with_autograd():
     torch.testing.assert_close(torch.linalg.norm(v, dim=-1), torch.ones(50, dtype=torch.float64), rtol=1e-14, atol=0)
     v.backward(up)
     torch.testing.assert_close(means.grad, field_ref.view_dirs_vjp(means.detach(), cam, up), rtol=1e-10, atol=1e-14)
+
+
+def test_mlp_entry_points_refuse_sizes_no_buffer_can_back_no_gpu_needed():
+    """The 32-bit-offset refusals of the field-network entry points (d3ga_mlp_linear, d3ga_mlp_wgrad / _acc: P K or P N >= 2^31
+    elements; d3ga_mlp_chain_fwd: (P + 256) N or (P + 256) K >= 2^30, the rows past P of the last row block included), decided
+    before any HIP call: the device pointers are made-up addresses that are never read, the chain's Ks / Ns / pointer arrays are
+    the host arrays they always are.  tests/test_gpu_mlp_paths.py runs every other refusal on device buffers."""
+    import d3ga_amd
+    L = d3ga_amd.lib()
+    E_SIZE, vp, i32, f32 = -2, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+    x, w, y, b = vp(0x10000), vp(0x20000), vp(0x30000), vp(0x40000)
+    P = 1 << 24
+    assert L.d3ga_mlp_linear(P, 128, 1, x, w, None, 1.0, None, None, 1.0, y, None) == E_SIZE            # P K = 2^31
+    assert L.d3ga_mlp_linear(P, 1, 128, x, w, None, 1.0, None, None, 1.0, y, None) == E_SIZE            # P n_out = 2^31
+    assert L.d3ga_mlp_linear(2 ** 31 - 1, 2, 1, x, w, None, 1.0, None, None, 1.0, y, None) == E_SIZE
+    for fn in (L.d3ga_mlp_wgrad, L.d3ga_mlp_wgrad_acc):
+        assert fn(P, 128, 1, x, w, y, b, None) == E_SIZE                                                 # P N = 2^31
+        assert fn(P, 1, 128, x, w, y, b, None) == E_SIZE                                                 # P K = 2^31
+        assert fn(P, 128, 1, x, w, y, None, None) == E_SIZE
+
+    def chain(P, widths):
+        n = len(widths) - 1
+        arr = lambda base: (vp * n)(*[base + 0x1000 * l for l in range(n)])
+        return L.d3ga_mlp_chain_fwd(P, widths[0], x, n, (i32 * n)(*widths[:-1]), (i32 * n)(*widths[1:]), arr(0x100000), None,
+                                    (f32 * n)(*[1.0] * n), arr(0x200000), (vp * n)(), None, None, None)
+    Pc = (1 << 23) - 256
+    assert chain(Pc, [4, 128, 128, 4]) == E_SIZE                     # (P + 256) 128 = 2^30 on a hidden layer's output
+    assert chain(Pc, [128, 1]) == E_SIZE                             # ... on the first layer's input (before the shape refusal)
+    assert chain(Pc, [4, 128, 128]) == E_SIZE                        # ... on the last layer's output
+    assert chain((1 << 28) - 256, [1, 4]) == E_SIZE                  # (P + 256) 4 = 2^30
