@@ -8,6 +8,8 @@
 
 #include <stdlib.h>
 
+#include <mutex>
+
 namespace d3ga {
 
 __device__ __forceinline__ float wave_sum_loss(float v) {
@@ -204,11 +206,39 @@ __device__ __forceinline__ f2 vtaps2(const float *col, int r, const float (&w)[1
     return a;
 }
 
+// The two scalars of a forward launch (mean SSIM, fused mean L1).  One float atomic per workgroup on the result word is neither
+// accurate nor reproducible: with thousands of workgroups the sum moved by 1.5e-6 relative with the order of arrival
+// (tests/test_gpu_losses.py).  So every workgroup stores its two partials (plain stores, no zero fill) and ONE workgroup adds them
+// in index order (ssim_finish_kernel), as the two-stage l1_mean does -- in scratch the library owns, because the entry points
+// carry none: kSsimSlots slots in device memory, handed out on the host (ssim_scratch_slot).
+constexpr int kSsimTiledFwdGrid = 2048, kSsimMarchFwdGrid = 4096, kSsimBwdGrid = 8192;      // persistent grids: workgroups at most
+constexpr int kSsimPartials = 4096;           // partials per scalar and slot: the largest forward grid
+constexpr int kSsimStreamSlots = 64;          // slots of eager launches, one per (device, stream): launches of a stream are ordered
+constexpr int kSsimSlots = 256;               // the rest: one per launch recorded into a graph, owned by that graph node for good
+static_assert(kSsimTiledFwdGrid <= kSsimPartials && kSsimMarchFwdGrid <= kSsimPartials, "a partial per workgroup");
+__device__ float g_ssim_partials[kSsimSlots][2][kSsimPartials];
+
+__global__ __launch_bounds__(kBlock) void ssim_finish_kernel(int np, int slot, float *__restrict__ out, float *__restrict__ out_l1) {
+    __shared__ float s_part[2][kBlock / 64];
+    float acc = 0.f, acc_l1 = 0.f;
+    for (int i = threadIdx.x; i < np; i += kBlock) { acc += g_ssim_partials[slot][0][i]; acc_l1 += g_ssim_partials[slot][1][i]; }
+    acc = wave_sum_loss(acc);
+    acc_l1 = wave_sum_loss(acc_l1);
+    if ((threadIdx.x & 63) == 0) { s_part[0][threadIdx.x >> 6] = acc; s_part[1][threadIdx.x >> 6] = acc_l1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f, t_l1 = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) { t += s_part[0][w]; t_l1 += s_part[1][w]; }
+        out[0] = t;
+        if (out_l1) out_l1[0] = t_l1;
+    }
+}
+
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(int C, int H, int W, int tiles_x, int tiles_y,
                                                        const float *__restrict__ img1, const float *__restrict__ img2,
-                                                       float inv_n, float *__restrict__ out, float *__restrict__ Dm,
-                                                       float *__restrict__ Dq1, float *__restrict__ Dq12,
-                                                       float *__restrict__ out_l1) {
+                                                       float inv_n, int slot, float *__restrict__ Dm,
+                                                       float *__restrict__ Dq1, float *__restrict__ Dq12) {
     __shared__ __attribute__((aligned(16))) float s_x[kSsimInH][kSsimXP], s_y[kSsimInH][kSsimXP];
     __shared__ __attribute__((aligned(16))) float s_h[5][kSsimTW][kSsimHP];
     __shared__ float s_part[8];
@@ -294,8 +324,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(int C, int H, int W, int 
     if ((tid & 63) == 0) { s_part[tid >> 6] = local; s_part[4 + (tid >> 6)] = local_l1; }
     __syncthreads();
     if (tid == 0) {
-        atomicAdd(out, (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * inv_n);
-        if (out_l1) atomicAdd(out_l1, (s_part[4] + s_part[5] + s_part[6] + s_part[7]) * inv_n);
+        g_ssim_partials[slot][0][blockIdx.x] = (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * inv_n;
+        g_ssim_partials[slot][1][blockIdx.x] = (s_part[4] + s_part[5] + s_part[6] + s_part[7]) * inv_n;
     }
 }
 
@@ -395,9 +425,8 @@ __device__ __forceinline__ void march_htaps(const float *row, int g, const float
 
 __global__ __launch_bounds__(kMarchW, 4) void ssim_march_fwd_kernel(int C, int H, int W, int strips, int segs, int seg_rows,
                                                                   const float *__restrict__ img1, const float *__restrict__ img2,
-                                                                  float inv_n, float *__restrict__ out, float *__restrict__ Dm,
-                                                                  float *__restrict__ Dq1, float *__restrict__ Dq12,
-                                                                  float *__restrict__ out_l1, int vec_ok) {
+                                                                  float inv_n, int slot, float *__restrict__ Dm,
+                                                                  float *__restrict__ Dq1, float *__restrict__ Dq12, int vec_ok) {
     __shared__ __attribute__((aligned(16))) float s_v[8][5][kMarchLd];      // two buffers of four rows: ONE barrier per group (40 KB: four workgroups per CU)
     float *const s_part = &s_v[0][0][0];                   // (the loss partials reuse it at the very end)
     const int tid = threadIdx.x;
@@ -510,8 +539,8 @@ __global__ __launch_bounds__(kMarchW, 4) void ssim_march_fwd_kernel(int C, int H
     if ((tid & 63) == 0) { s_part[tid >> 6] = local; s_part[4 + (tid >> 6)] = local_l1; }
     __syncthreads();
     if (tid == 0) {
-        atomicAdd(out, (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * inv_n);
-        if (out_l1) atomicAdd(out_l1, (s_part[4] + s_part[5] + s_part[6] + s_part[7]) * inv_n);
+        g_ssim_partials[slot][0][blockIdx.x] = (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * inv_n;
+        g_ssim_partials[slot][1][blockIdx.x] = (s_part[4] + s_part[5] + s_part[6] + s_part[7]) * inv_n;
     }
 }
 
@@ -707,14 +736,42 @@ static int ssim_march_rows(const void *kernel, int C, int H, int strips) {
 }
 static inline int ssim_impl() { return debug_knob(D3GA_KNOB_SSIM_IMPL); }      // 1 (default) the marching kernels, 0 the LDS-tiled ones of round 3
 
+// The scratch slot of a forward launch on stream s.  Eager launches: one slot per (device, stream), found or taken on first
+// sight -- launches of one stream run in order, so the finish kernel has read the slot before the next forward writes it.  A
+// launch recorded into a graph gets a slot of its own for good: a replay may run on any stream, next to anything.
+// < 0: D3GA_E_CAPACITY (more than kSsimStreamSlots streams, or more than kSsimSlots - kSsimStreamSlots recorded launches).
+static int ssim_scratch_slot(hipStream_t s, int *slot) {
+    static std::mutex mu;
+    static struct { int dev; hipStream_t stream; } streams[kSsimStreamSlots];
+    static int n_streams = 0, n_recorded = 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s != nullptr) D3GA_HIP(hipStreamIsCapturing(s, &cap));
+    int dev = 0;
+    D3GA_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (cap != hipStreamCaptureStatusNone) {
+        if (n_recorded >= kSsimSlots - kSsimStreamSlots) return D3GA_E_CAPACITY;
+        *slot = kSsimStreamSlots + n_recorded++;
+        return D3GA_OK;
+    }
+    for (int i = 0; i < n_streams; ++i)
+        if (streams[i].dev == dev && streams[i].stream == s) { *slot = i; return D3GA_OK; }
+    if (n_streams >= kSsimStreamSlots) return D3GA_E_CAPACITY;
+    streams[n_streams].dev = dev;
+    streams[n_streams].stream = s;
+    *slot = n_streams++;
+    return D3GA_OK;
+}
+
 extern "C" int d3ga_ssim_l1_fwd(int32_t C, int32_t H, int32_t W, const float *img1, const float *img2, float *out,
                                 float *Dm, float *Dq1, float *Dq12, float *out_l1, d3ga_stream_t stream) {
     if (C <= 0 || H <= 0 || W <= 0) return D3GA_E_SIZE;
     if (!img1 || !img2 || !out) return D3GA_E_NULL;
     if ((Dm != nullptr) != (Dq1 != nullptr) || (Dm != nullptr) != (Dq12 != nullptr)) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
-    D3GA_HIP(zero_async(out, sizeof(float), s));
-    if (out_l1) D3GA_HIP(zero_async(out_l1, sizeof(float), s));
+    int slot = 0;
+    const int st = ssim_scratch_slot(s, &slot);
+    if (st != D3GA_OK) return st;
     if (ssim_impl() == 1) {
         const int strips = (W + kMarchUse - 1) / kMarchUse;
         static int rows_cache[4] = {0, 0, 0, 0};            // (C, H, strips) -> rows: the occupancy query is not free
@@ -724,14 +781,17 @@ extern "C" int d3ga_ssim_l1_fwd(int32_t C, int32_t H, int32_t W, const float *im
         }
         const int seg_rows = rows_cache[3], segs = (H + seg_rows - 1) / seg_rows;
         const int vec_ok = (W % 4 == 0) && !(((uintptr_t)Dm | (uintptr_t)Dq1 | (uintptr_t)Dq12) & 15);
-        hipLaunchKernelGGL(ssim_march_fwd_kernel, dim3(ssim_grid(C * strips * segs, 4096)), dim3(kMarchW), 0, s, C, H, W, strips, segs, seg_rows,
-                           img1, img2, 1.0f / ((float)C * (float)H * (float)W), out, Dm, Dq1, Dq12, out_l1, vec_ok);
+        const int np = ssim_grid(C * strips * segs, kSsimMarchFwdGrid);
+        hipLaunchKernelGGL(ssim_march_fwd_kernel, dim3(np), dim3(kMarchW), 0, s, C, H, W, strips, segs, seg_rows,
+                           img1, img2, 1.0f / ((float)C * (float)H * (float)W), slot, Dm, Dq1, Dq12, vec_ok);
+        hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(kBlock), 0, s, np, slot, out, out_l1);
         return check_launch(s, 0);
     }
     const int tx = (W + kSsimTW - 1) / kSsimTW, ty = (H + kSsimTH - 1) / kSsimTH;
-    // persistent grid: every workgroup ends with ONE atomic on the result word (same-address atomics serialise)
-    hipLaunchKernelGGL(ssim_fwd_kernel, dim3(ssim_grid(C * tx * ty, 2048)), dim3(256), 0, s, C, H, W, tx, ty, img1, img2,
-                       1.0f / ((float)C * (float)H * (float)W), out, Dm, Dq1, Dq12, out_l1);
+    const int np = ssim_grid(C * tx * ty, kSsimTiledFwdGrid);
+    hipLaunchKernelGGL(ssim_fwd_kernel, dim3(np), dim3(256), 0, s, C, H, W, tx, ty, img1, img2,
+                       1.0f / ((float)C * (float)H * (float)W), slot, Dm, Dq1, Dq12);
+    hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(kBlock), 0, s, np, slot, out, out_l1);
     return check_launch(s, 0);
 }
 
@@ -755,12 +815,12 @@ extern "C" int d3ga_ssim_l1_bwd(int32_t C, int32_t H, int32_t W, const float *im
         }
         const int seg_rows = rows_cache[3], segs = (H + seg_rows - 1) / seg_rows;
         const int vec_ok = (W % 4 == 0) && !(((uintptr_t)img1 | (uintptr_t)img2 | (uintptr_t)grad_img1) & 15);
-        hipLaunchKernelGGL(ssim_march_bwd_kernel, dim3(ssim_grid(C * strips * segs, 8192)), dim3(kMarchW), 0, s, C, H, W, strips, segs, seg_rows,
+        hipLaunchKernelGGL(ssim_march_bwd_kernel, dim3(ssim_grid(C * strips * segs, kSsimBwdGrid)), dim3(kMarchW), 0, s, C, H, W, strips, segs, seg_rows,
                            img1, img2, Dm, Dq1, Dq12, g, g_l1, 1.0f / ((float)C * (float)H * (float)W), grad_img1, vec_ok);
         return check_launch(s, 0);
     }
     const int tx = (W + kSsimTW - 1) / kSsimTW, ty = (H + kSsimTH - 1) / kSsimTH;
-    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(ssim_grid(C * tx * ty, 8192)), dim3(256), 0, s, C, H, W, tx, ty, img1, img2,
+    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(ssim_grid(C * tx * ty, kSsimBwdGrid)), dim3(256), 0, s, C, H, W, tx, ty, img1, img2,
                        Dm, Dq1, Dq12, g, g_l1, 1.0f / ((float)C * (float)H * (float)W), grad_img1);
     return check_launch(s, 0);
 }

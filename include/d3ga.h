@@ -544,7 +544,11 @@ int d3ga_l1_mean_bwd_cell(int64_t n, const float *a, const float *const *b_cell,
 
 /* 11x11 Gaussian-window SSIM, mean over all channels and pixels.  Replaces utils/loss_utils.py:46-86 (ssim / _ssim with
  * window_size = 11, sigma = 1.5, zero padding 5, size_average = True; called at train.py:192).
- *   fwd: img1, img2 (C,H,W) -> out[0] = mean ssim_map (zeroed by the call).  Dm, Dq1, Dq12: optional (C,H,W) outputs
+ *   fwd: img1, img2 (C,H,W) -> out[0] = mean ssim_map, written by the call (contents irrelevant before): every workgroup
+ *        stores a partial sum in scratch the library owns and one workgroup adds them in index order -- the same bits on
+ *        every call.  An eager launch uses the scratch slot of its (device, stream), a launch recorded into a graph keeps a
+ *        slot for good: D3GA_E_CAPACITY beyond 64 streams or 192 recorded launches per process.
+ *        Dm, Dq1, Dq12: optional (C,H,W) outputs
  *        (all three or none) holding d ssim_map / d(w*img1), d(w*img1^2), d(w*img1*img2) for the backward.
  *   bwd: grad_img1 (C,H,W) = g[0]/(C*H*W) * ( w*Dm + 2 img1 (w*Dq1) + img2 (w*Dq12) ),  g: device scalar dL/d(mean).
  * The gradient w.r.t. img2 is the same call with the two images swapped (SSIM is symmetric). */
@@ -687,8 +691,7 @@ int d3ga_frame_prep(int32_t B, int32_t H, int32_t W, int32_t flags, const void *
  *   bytes: 4-byte) the planes are moved in 16-byte quads, otherwise pixel by pixel: same values either way.
  * d3ga_eval_ssim: the forward of the 11x11 Gaussian-window SSIM described at d3ga_ssim_fwd, for B frames of three channels, one
  *   plainly stored partial (the sum of ssim_map over a 16 x 16 tile) per tile: d3ga_eval_ssim_partials(H, W) floats per frame,
- *   frame-major.  Unlike d3ga_ssim_fwd, whose sum over workgroups uses float atomics, its result does not depend on arrival
- *   order.  pred, target (B,3,H,W) f32, element-aligned.
+ *   frame-major, added in index order by d3ga_eval_finish.  pred, target (B,3,H,W) f32, element-aligned.
  * d3ga_eval_finish, one workgroup per frame: adds the frame's partials in index order (bit-reproducible),
  *   mse_c = sum_c / (H W),   psnr = mean_c 20 log10(1 / sqrt(mse_c))      the MEAN OF THE PER-CHANNEL PSNRs, as
  *   psnr(fake, target).mean() of heatmap.py:39 is (utils/image_utils.py:20-22), not the PSNR of the pooled error; mse_c = 0
