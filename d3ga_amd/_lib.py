@@ -26,7 +26,8 @@ EVAL_MAX_PARTIALS = 2048  # D3GA_EVAL_MAX_PARTIALS: d3ga_eval_partials(H, W) nev
 MESH_MAX_SIDE = 16384    # D3GA_MESH_MAX_SIDE (include/d3ga.h): the largest frame side the mesh rasterizer accepts
 MESH_CAM_FLOATS = 16     # D3GA_MESH_CAM_FLOATS: R row-major, t, fx, fy, cx, cy
 POINTS_MAX_K = 8         # D3GA_POINTS_MAX_K: the most points the point-cloud rasterizer keeps per pixel
-OPTIM_CHUNK = 8192      # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
+LPIPS_PARTIALS = 1024   # D3GA_LPIPS_PARTIALS (include/d3ga.h): floats of scratch per image behind d3ga_lpips_tap's spatial mean
+OPTIM_CHUNK = 8192     # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
 OPTIM_ALIGNED16 = 1      # D3GA_OPTIM_ALIGNED16: flag of a chunk whose four pointers are 16-byte aligned
 
 
@@ -227,6 +228,11 @@ _SIGNATURES = {
     "d3ga_vgg_box_down2_fwd": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
     "d3ga_vgg_box_down2_bwd": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
     "d3ga_vgg_scratch_bytes": ([ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _i),
+    "d3ga_vgg_conv3x3_n": ([ctypes.c_int32] * 5 + [_vp] * 4 + [ctypes.c_int32] * 2 + [_vp, _vp], _i),
+    "d3ga_vgg_maxpool2_fwd_n": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
+    "d3ga_lpips_input": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
+    "d3ga_lpips_tap": ([ctypes.c_int32] * 4 + [_vp] * 6 + [ctypes.c_int32, _vp], _i),
+    "d3ga_lpips_scratch_bytes": ([ctypes.c_int32] * 3 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -17,6 +17,12 @@
 // and never stored.  The next k-step's loads are issued before the current one is multiplied.
 //
 // Layout: activations are channels-last (H, W, C) f32.  The image enters as (3, H, W): box_down2 does the transpose.
+//
+// BATCH (d3ga_vgg_conv3x3_n, d3ga_vgg_maxpool2_fwd_n): N images (N, H, W, C) ride in the GEMM's M dimension, row
+// p = (n H + y) W + x, so a wavefront's 32 pixels may span two images and the N images share every weight load.  A lane takes
+// its pixel apart into (n, y, x) once; the zero padding is decided from (y, x) alone, so a tap never crosses a seam, and a row
+// of the MFMA depends on nothing but its own pixel: image n of a batch is bit for bit the single-image call on that image.
+// The single-image entry points are the N = 1 case of the same kernels.
 #include "d3ga_internal.h"
 #include "perceptual_math.h"
 
@@ -73,19 +79,21 @@ struct ConvRaw {
 };
 
 template <int NB, bool VEC, bool MASK>
-__global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(int H, int W, int Cin, int Cout, const float *__restrict__ X,
+__global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(int M, int H, int W, int Cin, int Cout, const float *__restrict__ X,
                                                                const float *__restrict__ Ym, const uint4 *__restrict__ panel,
                                                                const float *__restrict__ bias, int relu, int accumulate,
                                                                float *__restrict__ Y) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l32 = lane & 31;
-    const int M = H * W;
     const int row0 = ((int)blockIdx.x * 4 + wave) * 32;
     if (row0 >= M) return;                                            // wave-uniform; the kernel has no barrier
     const int cu = pc_units_per_tap(Cin), KK = pc_ksteps(Cin), nbt = pc_nblocks(Cout);
     const int64_t plane = (int64_t)KK * 2 * nbt * 32;
     const int p = row0 + l32;
     const bool prow = p < M;
-    const int py = prow ? p / W : 0, px = prow ? p - py * W : 0;
+    const int HW = H * W;                                             // M = N HW rows, image after image
+    const int pn = prow ? p / HW : 0, pq = p - pn * HW;
+    const int py = prow ? pq / W : 0, px = prow ? pq - py * W : 0;
+    const size_t img0 = (size_t)pn * (size_t)HW;                      // first row of this pixel's image
     int nbg[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) nbg[nb] = min((int)blockIdx.y * NB + nb, nbt - 1);
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(int H, int W, int
         r.a0 = r.a1 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (MASK) r.m0 = r.m1 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok) {
-            const size_t o = ((size_t)yy * (size_t)W + (size_t)xx) * (size_t)Cin + (size_t)c8 * 8;
+            const size_t o = (img0 + (size_t)yy * (size_t)W + (size_t)xx) * (size_t)Cin + (size_t)c8 * 8;
             if constexpr (VEC) {                                       // Cin % 8 == 0: 32-byte aligned, all 8 channels exist
                 r.a0 = *reinterpret_cast<const float4 *>(X + o);
                 r.a1 = *reinterpret_cast<const float4 *>(X + o + 4);
@@ -198,15 +206,17 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(int H, int W, int
     }
 }
 
-// 2x2 max pool, stride 2, floor; channels-last.  One thread per output element.
-__global__ __launch_bounds__(kBlock) void pc_pool_fwd_kernel(int H, int W, int C, const float *__restrict__ x, float *__restrict__ y) {
+// 2x2 max pool, stride 2, floor; channels-last, N images back to back.  One thread per output element.
+__global__ __launch_bounds__(kBlock) void pc_pool_fwd_kernel(int N, int H, int W, int C, const float *__restrict__ x, float *__restrict__ y) {
     const int Ho = H / 2, Wo = W / 2;
-    const int64_t n = (int64_t)Ho * Wo * C;
+    const int64_t n = (int64_t)N * Ho * Wo * C;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const int c = (int)(i % C);
         const int64_t q = i / C;
-        const int ox = (int)(q % Wo), oy = (int)(q / Wo);
-        const float *s = x + ((int64_t)(2 * oy) * W + 2 * ox) * C + c;
+        const int ox = (int)(q % Wo);
+        const int64_t r = q / Wo;
+        const int oy = (int)(r % Ho), im = (int)(r / Ho);
+        const float *s = x + (((int64_t)im * H + 2 * oy) * W + 2 * ox) * C + c;
         const float a = s[0], b = s[C], d = s[(int64_t)W * C], e = s[(int64_t)W * C + C];
         y[i] = fmaxf(fmaxf(a, b), fmaxf(d, e));
     }
@@ -279,10 +289,10 @@ static inline unsigned pc_grid(int64_t n) {
 }
 
 template <int NB>
-static void launch_conv(bool vec, bool mask, dim3 grid, hipStream_t s, int H, int W, int cin, int cout, const float *x,
+static void launch_conv(bool vec, bool mask, dim3 grid, hipStream_t s, int M, int H, int W, int cin, int cout, const float *x,
                         const float *mask_y, const uint4 *panel, const float *bias, int relu, int accumulate, float *y) {
 #define D3GA_PC_LAUNCH(V, K) \
-    hipLaunchKernelGGL((conv3x3_kernel<NB, V, K>), grid, dim3(kConvThreads), 0, s, H, W, cin, cout, x, mask_y, panel, bias, relu, accumulate, y)
+    hipLaunchKernelGGL((conv3x3_kernel<NB, V, K>), grid, dim3(kConvThreads), 0, s, M, H, W, cin, cout, x, mask_y, panel, bias, relu, accumulate, y)
     if (vec && mask) D3GA_PC_LAUNCH(true, true);
     else if (vec) D3GA_PC_LAUNCH(true, false);
     else if (mask) D3GA_PC_LAUNCH(false, true);
@@ -290,9 +300,9 @@ static void launch_conv(bool vec, bool mask, dim3 grid, hipStream_t s, int H, in
 #undef D3GA_PC_LAUNCH
 }
 
-// sizes of one channels-last activation: positive, and every element index fits an int32
-static inline bool pc_sizes_ok(int64_t H, int64_t W, int64_t C) {
-    return H > 0 && W > 0 && C > 0 && H * W <= INT32_MAX && H * W * C <= INT32_MAX;
+// sizes of N channels-last activations: positive, and every element index of the batch fits an int32
+static inline bool pc_sizes_ok(int64_t H, int64_t W, int64_t C, int64_t N = 1) {
+    return N > 0 && H > 0 && W > 0 && C > 0 && H * W <= INT32_MAX && N * H * W <= INT32_MAX && N * H * W * C <= INT32_MAX;
 }
 
 }  // namespace d3ga
@@ -318,10 +328,10 @@ extern "C" int d3ga_vgg_pack_weights(int32_t w_cout, int32_t w_cin, const float 
     return check_launch(s, 0);
 }
 
-extern "C" int d3ga_vgg_conv3x3(int32_t H, int32_t W, int32_t cin, int32_t cout, const float *x, const float *mask_y,
-                                const void *panel, const float *bias, int32_t relu, int32_t accumulate, float *y,
-                                d3ga_stream_t stream) {
-    if (!pc_sizes_ok(H, W, cin) || !pc_sizes_ok(H, W, cout)) return D3GA_E_SIZE;
+extern "C" int d3ga_vgg_conv3x3_n(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, const float *x, const float *mask_y,
+                                  const void *panel, const float *bias, int32_t relu, int32_t accumulate, float *y,
+                                  d3ga_stream_t stream) {
+    if (!pc_sizes_ok(H, W, cin, N) || !pc_sizes_ok(H, W, cout, N)) return D3GA_E_SIZE;
     if (pc_plane_slots(cin, cout) > INT32_MAX) return D3GA_E_SIZE;
     if (!x || !panel || !y) return D3GA_E_NULL;
     if ((relu & ~1) || (accumulate & ~1)) return D3GA_E_CONFIG;
@@ -331,13 +341,28 @@ extern "C" int d3ga_vgg_conv3x3(int32_t H, int32_t W, int32_t cin, int32_t cout,
     hipStream_t s = (hipStream_t)stream;
     const int nbt = pc_nblocks(cout);
     const int NB = nbt >= 3 ? 4 : nbt;
-    const int64_t M = (int64_t)H * W;
-    const dim3 grid((unsigned)((M + kConvRows - 1) / kConvRows), (unsigned)((nbt + NB - 1) / NB));
+    const int M = N * H * W;
+    const dim3 grid((unsigned)(((int64_t)M + kConvRows - 1) / kConvRows), (unsigned)((nbt + NB - 1) / NB));
     const bool vec = (cin & 7) == 0, mask = mask_y != nullptr;
     const uint4 *pn = reinterpret_cast<const uint4 *>(panel);
-    if (NB == 1) launch_conv<1>(vec, mask, grid, s, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
-    else if (NB == 2) launch_conv<2>(vec, mask, grid, s, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
-    else launch_conv<4>(vec, mask, grid, s, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
+    if (NB == 1) launch_conv<1>(vec, mask, grid, s, M, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
+    else if (NB == 2) launch_conv<2>(vec, mask, grid, s, M, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
+    else launch_conv<4>(vec, mask, grid, s, M, H, W, cin, cout, x, mask_y, pn, bias, relu, accumulate, y);
+    return check_launch(s, 0);
+}
+
+extern "C" int d3ga_vgg_conv3x3(int32_t H, int32_t W, int32_t cin, int32_t cout, const float *x, const float *mask_y,
+                                const void *panel, const float *bias, int32_t relu, int32_t accumulate, float *y,
+                                d3ga_stream_t stream) {
+    return d3ga_vgg_conv3x3_n(1, H, W, cin, cout, x, mask_y, panel, bias, relu, accumulate, y, stream);
+}
+
+extern "C" int d3ga_vgg_maxpool2_fwd_n(int32_t N, int32_t H, int32_t W, int32_t C, const float *x, float *y, d3ga_stream_t stream) {
+    if (!pc_sizes_ok(H, W, C, N) || H < 2 || W < 2) return D3GA_E_SIZE;
+    if (!x || !y) return D3GA_E_NULL;
+    if (x == y) return D3GA_E_CONFIG;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(pc_grid((int64_t)N * (H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, N, H, W, C, x, y);
     return check_launch(s, 0);
 }
 
@@ -345,7 +370,7 @@ extern "C" int d3ga_vgg_maxpool2_fwd(int32_t H, int32_t W, int32_t C, const floa
     if (!pc_sizes_ok(H, W, C) || H < 2 || W < 2) return D3GA_E_SIZE;
     if (!x || !y) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(pc_grid((int64_t)(H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, H, W, C, x, y);
+    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(pc_grid((int64_t)(H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, 1, H, W, C, x, y);
     return check_launch(s, 0);
 }
 

@@ -63,34 +63,50 @@ def plan(H, W, n_layers=5, downsize=True):
     return Plan(down, image, tuple(convs), tuple(convs[t] for t in TAPS[:n_layers]), 0 if max(image) <= 512 else 2)
 
 
+def read_state_dict(weights, what="VGGLoss"):
+    """A state dict as it is, or the one a path names (loaded with weights_only=True)."""
+    if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
+    if not hasattr(weights, "keys"):
+        raise TypeError(f"{what}: weights must be a state dict or a path to one")
+    return weights
+
+
+def state_tensor(weights, names, what="VGGLoss"):
+    """(the first of `names` the dict has, its tensor as float32); KeyError naming every candidate."""
+    found = [n for n in names if n in weights]
+    if not found:
+        raise KeyError(f"{what}: the state dict has " + ("neither " + " nor ".join(repr(n) for n in names) if len(names) > 1
+                                                           else f"no {names[0]!r}"))
+    t = weights[found[0]]
+    if not torch.is_tensor(t) or not t.is_floating_point():
+        raise ValueError(f"{what}: {found[0]} is not a floating-point tensor")
+    return found[0], t.detach().to(torch.float32)
+
+
+def load_conv_chain(weights, conv_keys, prefixes=("features.{k}", "{k}"), what="VGGLoss"):
+    """[(weight (Cout,Cin,3,3), bias (Cout))] float32 of the 3x3 convolutions `conv_keys` of a state dict (or a path to one), key
+    K found as `<prefix>.weight` / `<prefix>.bias` under the first of `prefixes` (formatted with k=K, or a function K -> list of
+    prefixes) the dict has.  Any widths are accepted as long as they chain: Cin of the first is 3, of every other the Cout before."""
+    weights = read_state_dict(weights, what)
+    out, cin = [], 3
+    for k in conv_keys:
+        pre = prefixes(k) if callable(prefixes) else [p.format(k=k) for p in prefixes]
+        (wn, w), (bn, b) = (state_tensor(weights, [f"{p}.{leaf}" for p in pre], what) for leaf in ("weight", "bias"))
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] != cin or w.shape[0] < 1:
+            raise ValueError(f"{what}: {wn} must be (Cout, {cin}, 3, 3), got {tuple(w.shape)}")
+        if tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"{what}: {bn} must be ({w.shape[0]},), got {tuple(b.shape)}")
+        out.append((w.contiguous(), b.contiguous()))
+        cin = w.shape[0]
+    return out
+
+
 def load_vgg_weights(weights, n_layers=5):
     """[(weight (Cout,Cin,3,3), bias (Cout))] float32 for the convolutions `n_layers` needs, from a torchvision-style state dict
     (keys `features.K.weight` / `features.K.bias` or `K.weight` / `K.bias`, K in CONV_KEYS) or a path to one (loaded with
     weights_only=True).  Any widths are accepted as long as they chain: Cin of the first is 3, of every other the Cout before."""
-    if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
-        weights = torch.load(weights, map_location="cpu", weights_only=True)
-    if not hasattr(weights, "keys"):
-        raise TypeError("VGGLoss: weights must be a state dict or a path to one")
-    out, cin = [], 3
-    for k in CONV_KEYS[:n_convs(n_layers)]:
-        pair = []
-        for leaf in ("weight", "bias"):
-            names = (f"features.{k}.{leaf}", f"{k}.{leaf}")
-            found = [n for n in names if n in weights]
-            if not found:
-                raise KeyError(f"VGGLoss: the state dict has neither {names[0]!r} nor {names[1]!r}")
-            t = weights[found[0]]
-            if not torch.is_tensor(t) or not t.is_floating_point():
-                raise ValueError(f"VGGLoss: {found[0]} is not a floating-point tensor")
-            pair.append(t.detach().to(torch.float32))
-        w, b = pair
-        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] != cin or w.shape[0] < 1:
-            raise ValueError(f"VGGLoss: features.{k}.weight must be (Cout, {cin}, 3, 3), got {tuple(w.shape)}")
-        if tuple(b.shape) != (w.shape[0],):
-            raise ValueError(f"VGGLoss: features.{k}.bias must be ({w.shape[0]},), got {tuple(b.shape)}")
-        out.append((w.contiguous(), b.contiguous()))
-        cin = w.shape[0]
-    return out
+    return load_conv_chain(weights, CONV_KEYS[:n_convs(n_layers)])
 
 
 def _torchvision_weights():
@@ -168,6 +184,38 @@ def maxpool2(x, out=None):
     H, W, C = x.shape
     y = _out(out, (H // 2, W // 2, C), x, "maxpool2")
     check(_lib.lib().d3ga_vgg_maxpool2_fwd(H, W, C, dptr(x), dptr(y), stream_handle()), "d3ga_vgg_maxpool2_fwd")
+    return y
+
+
+def _act_n(x, what):
+    require_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous float32 (N, H, W, C) tensor, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def conv3x3_n(x, panel, bias, cout, relu=True, out=None, mask_y=None, accumulate=False):
+    """The convolution over N images at once (d3ga_vgg_conv3x3_n): x (N, H, W, Cin) -> y (N, H, W, cout), the images sharing
+    every weight load; image n is bit for bit conv3x3_relu / conv3x3_relu_bwd on x[n].  mask_y (N, H, W, Cin): x is zeroed
+    where mask_y <= 0 (the input-gradient form, with the transposed panel and bias None); accumulate: add to `out`."""
+    x = _act_n(x, "conv3x3_n")
+    N, H, W, cin = x.shape
+    if mask_y is not None and _act_n(mask_y, "conv3x3_n").shape != x.shape:
+        raise ValueError(f"conv3x3_n: mask_y {tuple(mask_y.shape)} and x {tuple(x.shape)} differ")
+    if accumulate and out is None:
+        raise ValueError("conv3x3_n: accumulate needs out")
+    y = _out(out, (N, H, W, cout), x, "conv3x3_n")
+    check(_lib.lib().d3ga_vgg_conv3x3_n(N, H, W, cin, cout, dptr(x), dptr(mask_y), dptr(panel), dptr(bias), int(bool(relu)),
+                                        int(bool(accumulate)), dptr(y), stream_handle()), "d3ga_vgg_conv3x3_n")
+    return y
+
+
+def maxpool2_n(x, out=None):
+    """maxpool2 over N images at once: x (N, H, W, C) -> (N, H/2, W/2, C)."""
+    x = _act_n(x, "maxpool2_n")
+    N, H, W, C = x.shape
+    y = _out(out, (N, H // 2, W // 2, C), x, "maxpool2_n")
+    check(_lib.lib().d3ga_vgg_maxpool2_fwd_n(N, H, W, C, dptr(x), dptr(y), stream_handle()), "d3ga_vgg_maxpool2_fwd_n")
     return y
 
 

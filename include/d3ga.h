@@ -1045,6 +1045,38 @@ int d3ga_vgg_maxpool2_bwd(int32_t H, int32_t W, int32_t C, const float *x, const
 int d3ga_vgg_box_down2_fwd(int32_t C, int32_t H, int32_t W, int32_t down, const float *img, float *out, d3ga_stream_t stream);
 int d3ga_vgg_box_down2_bwd(int32_t C, int32_t H, int32_t W, int32_t down, const float *g, float *g_img, d3ga_stream_t stream);
 int d3ga_vgg_scratch_bytes(int32_t H, int32_t W, int32_t down, int32_t n_layers, const int32_t *widths, int64_t *out);
+/* The same convolution and pool over N images (N,H,W,C) at once: the images ride in the GEMM's M dimension and share every
+ * weight load; the zero padding is per image (no tap reads across a seam).  Every other argument as above; the size rule is
+ * N H W C <= INT32_MAX.  Image n of the result is bit for bit what the single-image call gives on image n; the single-image
+ * entry points are the N = 1 case of the same kernels.  d3ga_vgg_maxpool2_fwd_n: y must not be x (D3GA_E_CONFIG). */
+int d3ga_vgg_conv3x3_n(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, const float *x, const float *mask_y,
+                       const void *panel, const float *bias, int32_t relu, int32_t accumulate, float *y, d3ga_stream_t stream);
+int d3ga_vgg_maxpool2_fwd_n(int32_t N, int32_t H, int32_t W, int32_t C, const float *x, float *y, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * LPIPS (VGG), forward only: the third metric of recorder/heatmap.py:13, 40.  The chain is VGG16 -- 13 convolutions
+ * (d3ga_vgg_conv3x3_n), a pool (d3ga_vgg_maxpool2_fwd_n) in front of conv index 2, 4, 7, 10, a tap behind conv index 1, 3, 6,
+ * 9, 12 -- with fake and target as one batch of 2 B images; csrc/lpips_math.h states the arithmetic.  No entry point
+ * allocates or synchronises; all are capturable; sizes (D3GA_E_SIZE), pointers (D3GA_E_NULL), alignment, flags and
+ * overlapping buffers (D3GA_E_CONFIG) are refused before any launch.  No float atomics: results are reproducible bit for bit.
+ *
+ * d3ga_lpips_input: img (N,3,H,W) -> out (N,H,W,3) = ((normalize ? 2 x - 1 : x) - shift_c) / scale_c,
+ *   shift = (-.030, -.088, -.188), scale = (.458, .448, .450).
+ * d3ga_lpips_tap: features a, b (B,h,w,C), 1 <= C <= 512, weights lin (C), any sign:
+ *     d(p) = sum_c lin_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2,  |a| = sqrt(sum_c a_c^2)
+ *   (the difference before the square: a == b gives exactly 0; an all-zero vector contributes 0, not NaN) -> map (B,h,w) | NULL,
+ *   and value[b] = [accumulate ? value[b] : 0] + mean_p d(p) through `partials`, B * D3GA_LPIPS_PARTIALS floats of scratch, in
+ *   two stages of a fixed order: image b of a batch is bit for bit the single-pair call.  a may be b.
+ * d3ga_lpips_scratch_bytes (host): the work area of B image pairs (3,H,W), H, W >= 16 (four floor pools; else D3GA_E_SIZE),
+ *   with 13 conv widths (NULL: VGG16's; a tap wider than 512: D3GA_E_SIZE): out[0] = all of it = 2 out[1] + out[2],
+ *   out[1] = one buffer of the activation ping-pong (the widest layer of the 2 B images), out[2] = the partials; each part
+ *   starts on a 256-byte boundary in that order.  A tap's features are consumed before the buffers rotate.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_LPIPS_PARTIALS 1024
+int d3ga_lpips_input(int32_t N, int32_t H, int32_t W, int32_t normalize, const float *img, float *out, d3ga_stream_t stream);
+int d3ga_lpips_tap(int32_t B, int32_t h, int32_t w, int32_t C, const float *a, const float *b, const float *lin, float *map,
+                   float *partials, float *value, int32_t accumulate, d3ga_stream_t stream);
+int d3ga_lpips_scratch_bytes(int32_t B, int32_t H, int32_t W, const int32_t *widths, int64_t *out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
