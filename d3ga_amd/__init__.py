@@ -5,11 +5,12 @@ There is NO CPU fallback: every op raises if the library is missing or the tenso
 """
 from ._lib import D3GAError, lib, library_path  # noqa: F401
 from .evaluation import Evaluator, compute_errors, compute_heatmap, error_heatmap, psnr  # noqa: F401
+from .knn import knn_points  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
-from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, rasterize_meshes, to_cameras,  # noqa: F401
-                          vertex_normals)
+from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, interpolate_face_attributes,  # noqa: F401
+                          rasterize_meshes, to_cameras, vertex_normals)
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
            "Fragments", "MeshCameras", "MeshScratch", "MeshTopology", "Renderer", "rasterize_meshes", "to_cameras", "vertex_normals",
-           "PCRenderer", "PointFragments", "PointScratch", "rasterize_points"]
+           "PCRenderer", "PointFragments", "PointScratch", "rasterize_points", "knn_points", "interpolate_face_attributes"]

@@ -25,7 +25,9 @@ EVAL_BG_WHITE, EVAL_COMPOSED, EVAL_ALPHA3, EVAL_BOUNDARY_F32 = 1, 2, 4, 8
 EVAL_MAX_PARTIALS = 2048  # D3GA_EVAL_MAX_PARTIALS: d3ga_eval_partials(H, W) never exceeds it
 MESH_MAX_SIDE = 16384    # D3GA_MESH_MAX_SIDE (include/d3ga.h): the largest frame side the mesh rasterizer accepts
 MESH_CAM_FLOATS = 16     # D3GA_MESH_CAM_FLOATS: R row-major, t, fx, fy, cx, cy
-POINTS_MAX_K = 8         # D3GA_POINTS_MAX_K: the most points the point-cloud rasterizer keeps per pixel
+INTERP_MAX_D = 64        # D3GA_INTERP_MAX_D: the most channels d3ga_interp_face_attrs interpolates
+KNN_MAX_K = 16           # D3GA_KNN_MAX_K: the most neighbours d3ga_knn_points keeps per query
+POINTS_MAX_K = 8       # D3GA_POINTS_MAX_K: the most points the point-cloud rasterizer keeps per pixel
 LPIPS_PARTIALS = 1024   # D3GA_LPIPS_PARTIALS (include/d3ga.h): floats of scratch per image behind d3ga_lpips_tap's spatial mean
 OPTIM_CHUNK = 8192     # D3GA_OPTIM_CHUNK (include/d3ga.h): elements per record of the optimizer's chunk table
 OPTIM_ALIGNED16 = 1      # D3GA_OPTIM_ALIGNED16: flag of a chunk whose four pointers are 16-byte aligned
@@ -163,6 +165,9 @@ _SIGNATURES = {
     "d3ga_knn3_mean_dist2": ([_i, _vp, _vp, _vp], _i),
     "d3ga_compute_bary_grid": ([_i] + [_vp] * 9 + [_vp], _i),
     "d3ga_knn3_mean_dist2_grid": ([_i] + [_vp] * 6 + [_vp], _i),
+    "d3ga_knn_points": ([_i] * 4 + [_vp] * 4 + [_vp], _i),
+    "d3ga_knn_points_grid": ([_i] * 3 + [_vp] * 8 + [_vp], _i),
+    "d3ga_interp_face_attrs": ([_i64, _i64, _i] + [_vp] * 4 + [_vp], _i),
     "d3ga_l1_mean_fwd": ([_i64, _vp, _vp, _vp, _vp], _i),
     "d3ga_l1_mean_fwd_ws": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
     "d3ga_l1_mean_bwd": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),

@@ -312,6 +312,23 @@ __global__ __launch_bounds__(kBlock) void mesh_vertex_normals_kernel(int64_t n, 
     }
 }
 
+// one lane per (pixel, channel): the channels of a face corner are contiguous, so loads and stores coalesce
+__global__ __launch_bounds__(kBlock) void mesh_interp_kernel(int64_t n, int64_t F_total, int D, const int64_t *__restrict__ pix_to_face,
+                                                             const float *__restrict__ bary, const float *__restrict__ face_attrs,
+                                                             float *__restrict__ out) {
+    for (int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x; g < n; g += (int64_t)gridDim.x * kBlock) {
+        const int64_t p = g / D;
+        const int c = (int)(g - p * D);
+        const int64_t f = pix_to_face[p];
+        float v = 0.f;
+        if (f >= 0 && f < F_total) {
+            const float *a = face_attrs + (size_t)f * 3 * D + c;
+            v = mesh_interp_attr(bary[3 * p], bary[3 * p + 1], bary[3 * p + 2], a[0], a[D], a[2 * D]);
+        }
+        out[g] = v;
+    }
+}
+
 static inline unsigned mesh_grid(int64_t n) {
     const int64_t blocks = (n + kBlock - 1) / kBlock;
     return (unsigned)(blocks < 1 ? 1 : (blocks > kMeshMaxGrid ? kMeshMaxGrid : blocks));
@@ -416,5 +433,18 @@ extern "C" int d3ga_mesh_maps(int32_t B, int32_t V, int32_t F, int32_t H, int32_
     const int64_t hw = (int64_t)H * W, n = hw * B;
     hipLaunchKernelGGL(mesh_maps_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, hw, V, F, verts, faces, vertex_normals, cams, pix_to_face,
                        bary, position, normal, depth, mask);
+    return check_launch(s, 0);
+}
+
+extern "C" int d3ga_interp_face_attrs(int64_t n_pix, int64_t F_total, int D, const int64_t *pix_to_face, const float *bary,
+                                      const float *face_attrs, float *out, d3ga_stream_t stream) {
+    if (n_pix < 0 || F_total < 0 || D < 1 || D > D3GA_INTERP_MAX_D) return D3GA_E_SIZE;
+    if (n_pix >= ((int64_t)1 << 40) || F_total >= ((int64_t)1 << 40)) return D3GA_E_SIZE;
+    if (n_pix == 0) return D3GA_OK;
+    if (!pix_to_face || !bary || !out || (F_total > 0 && !face_attrs)) return D3GA_E_NULL;
+    if (mesh_unaligned(pix_to_face, 7) || mesh_unaligned(bary) || mesh_unaligned(face_attrs) || mesh_unaligned(out)) return D3GA_E_CONFIG;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = n_pix * D;
+    hipLaunchKernelGGL(mesh_interp_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, F_total, D, pix_to_face, bary, face_attrs, out);
     return check_launch(s, 0);
 }

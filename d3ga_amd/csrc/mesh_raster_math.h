@@ -92,6 +92,10 @@ D3GA_FHD int mesh_face_setup(const float *cam, const float *w0, const float *w1,
     return (((i1 - i0) / kMeshChunk) + 1) * (((j1 - j0) / kMeshChunk) + 1);
 }
 
+// pytorch3d's interpolate_face_attributes (recorder/mesh_renderer.py:80-93) for one channel of one pixel: the weights are
+// taken as they come (the reference passes ones for its normal map), the sum runs in the order b0 a0, b1 a1, b2 a2
+D3GA_FHD float mesh_interp_attr(float b0, float b1, float b2, float a0, float a1, float a2) { return (b0 * a0 + b1 * a1) + b2 * a2; }
+
 D3GA_FHD int mesh_box_lo(int32_t packed) { return packed & 0xffff; }
 D3GA_FHD int mesh_box_hi(int32_t packed) { return (packed >> 16) & 0xffff; }
 

@@ -358,3 +358,31 @@ def vertex_normals(vertices, faces):
         check(_lib.lib().d3ga_mesh_vertex_normals(B, V, topo.F, dptr(verts), dptr(topo.faces(verts.device)), dptr(offsets), dptr(lists), dptr(out),
                                                   stream_handle()), "d3ga_mesh_vertex_normals")
     return out
+
+
+def interpolate_face_attributes(pix_to_face, barycentric_coords, face_attributes, out=None):
+    """pytorch3d's `interpolate_face_attributes` as Renderer.map of the reference runs it (recorder/mesh_renderer.py:11,80-93):
+    pix_to_face (N,H,W,K) int64 into the packed faces, < 0 at background pixels; barycentric_coords (N,H,W,K,3) float32;
+    face_attributes (F,3,D) float32, 1 <= D <= 64 -> (N,H,W,K,D) float32: b0 a0 + b1 a1 + b2 a2 of the pixel's face, 0 at
+    background pixels (and where an index is >= F).  The weights are taken as they come (the reference passes ones for its
+    normal map).  FORWARD ONLY: inputs that require grad are detached.  Never synchronises with the host; with `out=` (a
+    contiguous float32 tensor of the result's shape) nothing is allocated, so a captured step can contain it."""
+    what = "interpolate_face_attributes"
+    if not torch.is_tensor(pix_to_face) or pix_to_face.dim() != 4 or pix_to_face.dtype != torch.int64:
+        raise ValueError(f"{what}: pix_to_face must be an int64 tensor (N,H,W,K)")
+    if not torch.is_tensor(barycentric_coords) or tuple(barycentric_coords.shape) != tuple(pix_to_face.shape) + (3,) or \
+            barycentric_coords.dtype != torch.float32:
+        raise ValueError(f"{what}: barycentric_coords must be a float32 tensor {tuple(pix_to_face.shape) + (3,)}")
+    if not torch.is_tensor(face_attributes) or face_attributes.dim() != 3 or face_attributes.shape[1] != 3 or \
+            face_attributes.dtype != torch.float32:
+        raise ValueError(f"{what}: face_attributes must be a float32 tensor (F,3,D)")
+    F, D = int(face_attributes.shape[0]), int(face_attributes.shape[2])
+    if not 1 <= D <= _lib.INTERP_MAX_D:
+        raise ValueError(f"{what}: D = {D} outside 1 .. {_lib.INTERP_MAX_D}")
+    _device(what, pix_to_face, barycentric_coords, face_attributes)
+    p2f, bary, attrs = pix_to_face.detach().contiguous(), barycentric_coords.detach().contiguous(), face_attributes.detach().contiguous()
+    res = _out(what, "out", out, tuple(pix_to_face.shape) + (D,), p2f.device)
+    with torch.no_grad():
+        check(_lib.lib().d3ga_interp_face_attrs(p2f.numel(), F, D, dptr(p2f), dptr(bary), dptr(attrs), dptr(res), stream_handle()),
+              "d3ga_interp_face_attrs")
+    return res

@@ -764,6 +764,16 @@ int d3ga_mesh_maps(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const 
                    const float *vertex_normals, const float *cams, const int32_t *pix_to_face, const float *bary, float *position,
                    float *normal, float *depth, float *mask, d3ga_stream_t stream);
 
+/* pytorch3d's interpolate_face_attributes as the reference's Renderer.map runs it per frame (recorder/mesh_renderer.py:11,80-93):
+ * pix_to_face (n_pix) int64 into packed faces, <0 = background; bary (n_pix,3); face_attrs (F_total,3,D) -> out (n_pix,D):
+ *   out = b0*a0 + b1*a1 + b2*a2 in that order, f32, no contraction; background pixels get 0.
+ * An index >= F_total writes 0 and reads nothing.  Forward only.  Status, nothing launched: a negative size
+ * or D outside [1, D3GA_INTERP_MAX_D] D3GA_E_SIZE; a required pointer NULL (face_attrs with F_total > 0) D3GA_E_NULL; a pointer
+ * not aligned to its element D3GA_E_CONFIG.  n_pix = 0 is valid.  No host synchronisation; capturable. */
+#define D3GA_INTERP_MAX_D 64
+int d3ga_interp_face_attrs(int64_t n_pix, int64_t F_total, int D, const int64_t *pix_to_face, const float *bary,
+                           const float *face_attrs, float *out, d3ga_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Point-cloud view: the reference's recorder/pc_renderer.py::PCRenderer (a pytorch3d PointsRasterizer that keeps the K
  * nearest points of every pixel, + AlphaCompositor) for B clouds of P points, one camera each.  Forward only.  Semantics:
@@ -870,6 +880,24 @@ int d3ga_knn3_mean_dist2(int P, const float *points, float *out, d3ga_stream_t s
  * above, HOST arrays): ring search outwards from the point's cell, exact. */
 int d3ga_knn3_mean_dist2_grid(int P, const float *points, const int32_t *cell_start, const int32_t *cell_points,
                               const float *origin_h, const int32_t *dims, float *out, d3ga_stream_t stream);
+
+/* K nearest neighbours with distances and indices: pytorch3d's knn_points as models/cage_net.py:21,66 calls it
+ * (knn_points(points[None], points[None], K = 4)), forward only.  Semantics (specification of record):
+ * the squared distance is dx*dx + dy*dy + dz*dz in f32 without contraction, plus the first-order term of what the three f32
+ * subtractions lost (0 where they are exact; csrc/knn_math.h: within 4 * 2^-24 d of the distance of the f32 coordinates); neighbours are ordered by the
+ * pair (distance, index), the lower index first on equal distances, so the result does not depend on the order of the search;
+ * a query that is itself in p2 finds itself; with P2 < K the missing slots are dists = 0, idx = 0 (pytorch3d's padding).
+ *   p1 (N,P1,3), p2 (N,P2,3) f32 -> dists (N,P1,K) f32 squared distances ascending, idx (N,P1,K) int64 into p2.  Exhaustive. */
+#define D3GA_KNN_MAX_K 16
+int d3ga_knn_points(int N, int P1, int P2, int K, const float *p1, const float *p2, float *dists, int64_t *idx, d3ga_stream_t s);
+/* one batch element, p2 bucketed in a uniform grid (CSR as d3ga_knn3_mean_dist2_grid takes it; origin_h, dims HOST arrays):
+ * exact ring search, bit-identical to d3ga_knn_points.  The queries need not be members of p2 nor lie inside its box.
+ * Status of both, nothing launched: a negative size, N > 65535, K outside [1, D3GA_KNN_MAX_K], a dimension < 1, a cell edge
+ * that is not positive and finite D3GA_E_SIZE; a required pointer NULL (p2, cell_points with P2 > 0) D3GA_E_NULL.  P1 = 0 or
+ * N = 0: D3GA_OK without a launch. */
+int d3ga_knn_points_grid(int P1, int P2, int K, const float *p1, const float *p2, const int32_t *cell_start,
+                         const int32_t *cell_points, const float *origin_h, const int32_t *dims,
+                         float *dists, int64_t *idx, d3ga_stream_t s);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Field networks: the dense layer of models/mlp.py:39-232 -- every field is
