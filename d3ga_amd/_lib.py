@@ -135,6 +135,8 @@ _SIGNATURES = {
     "d3ga_cage_deform_bwd": ([ctypes.POINTER(c) for c in (CageDeformIn, CageDeformGrads, CageDeformRoute, CageDeformSkin)] + [_lpg, _vp], _i),
     "d3ga_fem_energy_fwd": ([_i] + [_vp] * 4 + [_vp], _i),
     "d3ga_fem_energy_bwd": ([_i, _i] + [_vp] * 5 + [_vp], _i),
+    "d3ga_bary_interp_fwd": ([ctypes.c_int32] * 3 + [_vp] * 5 + [_vp], _i),
+    "d3ga_bary_interp_bwd": ([ctypes.c_int32] * 4 + [_vp] * 9 + [_vp], _i),
     "d3ga_raster_scratch_bytes": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_scratch_bytes_views": ([ctypes.c_int32] * 4 + [_i64, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
     "d3ga_raster_scratch_bytes_window": ([ctypes.c_int32] * 4 + [_i64, ctypes.c_int32, ctypes.POINTER(_i64)], _i),

@@ -28,7 +28,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 112 /* (the d3ga_vgg_* entry points were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* (the d3ga_vgg_* and d3ga_bary_interp_* entry points were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -193,6 +193,38 @@ int d3ga_fem_energy_fwd(int T, const float *tetpoints, const int32_t *tetras, co
                         d3ga_stream_t stream);
 int d3ga_fem_energy_bwd(int T, int V, const float *tetpoints, const int32_t *tetras, const float *Dn_inv,
                         const float *g_energy, float *g_tetpoints, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * D2b  Barycentric attributes over a static binding (added without an ABI number change: new entry points only).
+ * Replaces: the gather + einsum("ikj,ik->ij", attr[cells][cell_id], barys) wherever it is applied to data other than the posed
+ *           cage: models/cage_net.py:236-241 (the ambient-occlusion value through cage_to_body_vertex, tetra_faces, tetra_id
+ *           into `shadow`), models/cage_net.py:270 (canonical_means3D) and models/mesh_net.py:193,226 (the means of the mesh
+ *           primitive: barycentric points on body-mesh triangles).
+ *   attr (V,C); rows (P,K) int32: corner k of Gaussian i reads row rows[i,k] of attr -- the binding as ONE table, built once
+ *   (d3ga_amd/bary_interp.py BaryBinding: tetras[tetra_id], vertex_map[tetras[tetra_id]] or the mesh's (P,3) face ids);
+ *   barys (P,K); delta_barys (P,K) | NULL is added to barys (models/cage_net.py:213 fused)  ->  out (P,C).
+ *   Domain: K in {3, 4}, 1 <= C <= 8, P >= 0, V >= 0, K P <= INT32_MAX.  With K == 4 rows, barys, delta_barys and g_barys are
+ *   read / written 16 bytes per Gaussian and must be 16-byte aligned.  rows are NOT range-checked (the binding validates them).
+ * fwd: w_k = barys[i,k] + delta_barys[i,k] (one rounding; barys[i,k] itself without delta_barys);
+ *   out[i,c] = w_0 a_0, then fmaf(w_k, a_k, .) for k = 1 .. K-1 in that order, a_k = attr[rows[i,k], c].
+ * bwd: g_out (P,C) -> g_barys (P,K) | NULL and g_attr (V,C) | NULL (each skipped when NULL).
+ *   g_barys[i,k] = a_0 g_0, then fmaf(a_c, g_c, .) for c = 1 .. C-1, a_c = attr[rows[i,k], c], g_c = g_out[i,c]; it is the
+ *   gradient of barys and of delta_barys.
+ *   g_attr[v,c] = sum over the items of v of w g_out, a GATHER over the CSR lists vert_start (V+1) / vert_items (K P; item
+ *   K i + k, built over the FINAL row ids), 16 lanes per row v: lane l adds the items at list positions l, l + 16, l + 32, ...
+ *   of v's list in that order (s = 0; s = fmaf(w, g_out[i,c], s)), then the 16 lane sums are added by a butterfly over lane
+ *   distance 1, 2, 4, 8.  No float atomics, the order depends on the lists alone: repeated calls are bit-identical.  Every row
+ *   of g_attr is written (an empty list gives 0); the caller never zeroes it.
+ *   P == 0: the forward launches nothing; the backward zeroes g_attr | NULL and reads no other pointer.
+ *   Status, before any HIP call: a negative size, K not in {3, 4}, C outside 1..8 or K P > INT32_MAX D3GA_E_SIZE; with P > 0 a
+ *   NULL attr, rows, barys, out / g_out, or g_attr without vert_start / vert_items D3GA_E_NULL; a misaligned pointer with
+ *   K == 4 D3GA_E_CONFIG.  No host synchronisation, capturable.
+ * ------------------------------------------------------------------------------------------------------- */
+int d3ga_bary_interp_fwd(int32_t P, int32_t K, int32_t C, const float *attr, const int32_t *rows, const float *barys,
+                         const float *delta_barys, float *out, d3ga_stream_t stream);
+int d3ga_bary_interp_bwd(int32_t P, int32_t V, int32_t K, int32_t C, const float *attr, const int32_t *rows, const float *barys,
+                         const float *delta_barys, const float *g_out, const int32_t *vert_start, const int32_t *vert_items,
+                         float *g_attr, float *g_barys, d3ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * B1  SMPL / SMPL-X body model (added without an ABI number change: new entry points only, no existing layout moves).

@@ -30,6 +30,9 @@ called as they are:
               (unbound Batcher: object.__new__ plus config and bg_color) for five cage sets and both backgrounds (only with the
               argument `frames`, or a full run).  kornia is not vendored: the median and the morphology of Batcher.process have
               NO reference-held pin (tests/frame_ref.py restates them)                       -> frame_cases.npz
+  G14 interp  models.cage_net.CageNet.forward with batch["pred_ao"] behind a many-to-one cage_to_body_vertex (`shadow`,
+              `canonical_means3D`) and models.mesh_net.MeshNet.forward (the mesh primitive's means), both unbound, with autograd
+              gradients (only with the argument `interp`)                                     -> interp_cases.npz
 The only stand-in with numerical content besides that blur is ``Tetra.gradient`` (un-vendored tetra_sampler): it is
 written here as the column-edge matrix of lib/tet_mesh.py:88-94 (the reference's in-tree analogue).
 """
@@ -750,9 +753,93 @@ def gen_skeleton(bm):
              state_dict_keys=np.asarray(list(mod.state_dict().keys())))
 
 
+def gen_interp(cn, CageBase, mn):
+    """G14: the barycentric interpolation of data other than the posed cage, float32, from the reference's own forwards.
+    Cage: models.cage_net.CageNet.forward (unbound, the stand-in geometry of G3) on a 2x2x2 Kuhn lattice with batch["pred_ao"]
+    over 11 body vertices behind a many-to-one geometry.cage_to_body_vertex (27 cage vertices; body vertex 7 is used by none);
+    the stub color_field records its `shadow` argument (cage_net.py:236-241), `canonical_means3D` is cage_net.py:270, and the
+    autograd gradients of sum(shadow * up) w.r.t. pred_ao and delta_bary are kept.  Mesh: models.mesh_net.MeshNet.forward
+    (unbound) on a namespace geometry with V = 30 vertices and F = 40 random triangles, P Gaussians bound to faces; means3D
+    (mesh_net.py:193), canonical_means3D (:226) and the gradients of sum(means3D * up) w.r.t. the posed points and delta_bary."""
+    rng = np.random.default_rng(71)
+    g = torch.Generator().manual_seed(71)
+    P = 60
+    Rw2c, t = look_at([0.5, 0.2, -3.0], [0, 0, 0])
+    batch = {"camera_id": 0, "R": Rw2c.T.copy(), "T": t, "FoVx": 0.8, "FoVy": 0.9, "frame_id": 0, "width": 64, "height": 64,
+             "lbs": torch.zeros(87), "frame_encoding": None, "camera_encoding": None}
+    seen = {}
+
+    def namespace(P, geometry, d_bary, d_node):
+        scaling = torch.randn(P, 3, generator=g) * 0.3 - 4.0
+        rotation = torch.randn(P, 4, generator=g)
+        self = SimpleNamespace(geometry=geometry, training=False, tet_offset_pre_lbs=False, scaling=scaling, rotation=rotation,
+                               scaling_activation=torch.exp, rotation_activation=torch.nn.functional.normalize,
+                               get_rotation=torch.nn.functional.normalize(rotation), get_scales=torch.exp(scaling),
+                               get_colors_feat=torch.zeros(P, 4), silhouette_color=torch.tensor([1.0, 0.0, 0.0]),
+                               cage_config=SimpleNamespace(cage_name="body"), use_SHS=lambda: False)
+        self.deformation_field = lambda canon, cond: d_node
+        self.canonical_field = lambda rot, scale, bary, cond: (d_bary, torch.zeros(P, 4), torch.zeros(P, 3))
+        self.get_cond = lambda b, n: b["lbs"]
+        self.build_covariance_from_scaling_rotation = lambda s, r: cn.CageNet.build_covariance_from_scaling_rotation(self, s, r)
+
+        def color_field(feat, cond, viewdirs, frame, camera, shadow):
+            seen["shadow"] = shadow
+            return torch.rand(P, 3, generator=g), torch.rand(P, 1, generator=g)
+        self.color_field = color_field
+        return self
+
+    # --- cage: shadow through the vertex map, canonical means
+    pts, tets = kuhn_lattice(2, np.array([-0.3, -0.9, -0.2]), np.array([0.3, 0.9, 0.2]), 0.2, rng)
+    V, NB = pts.shape[0], 11
+    tetra_id = np.sort(rng.integers(0, tets.shape[0], size=P)).astype(np.int64)
+    barys = rng.dirichlet(np.ones(4), size=P).astype(np.float32)
+    vmap = rng.choice(np.delete(np.arange(NB), 7), size=V).astype(np.int64)          # many-to-one; body vertex 7 stays unused
+    posed = torch.from_numpy((pts * 1.1 + 0.02).astype(np.float32))
+    geo = make_geometry(CageBase, pts, tets, tetra_id, barys, posed, torch.float32)
+    geo.cage_to_body_vertex = torch.from_numpy(vmap)
+    d_bary = (torch.tanh(torch.randn(P, 4, generator=g)) * 0.05).requires_grad_(True)
+    pred_ao = torch.rand(NB, generator=g).requires_grad_(True)
+    pkg = cn.CageNet.forward(namespace(P, geo, d_bary, torch.zeros(V, 3)), dict(batch, pred_ao=pred_ao))
+    shadow = seen.pop("shadow")
+    up_s = torch.randn(P, 1, generator=g)
+    g_ao, g_db = torch.autograd.grad((shadow * up_s).sum(), [pred_ao, d_bary])
+    out = dict(c_canon_points=pts, c_tetras=tets, c_tetra_id=tetra_id, c_barys=barys, c_delta_bary=d_bary.detach().numpy(),
+               c_vertex_map=vmap, c_pred_ao=pred_ao.detach().numpy(), c_shadow=shadow.detach().numpy(),
+               c_canonical_means3D=pkg["canonical_means3D"].detach().numpy(), c_up_shadow=up_s.numpy(),
+               c_grad_pred_ao=g_ao.numpy(), c_grad_delta_bary=g_db.numpy())
+
+    # --- mesh primitive: means on triangles
+    Vm, F = 30, 40
+    faces = np.stack([rng.choice(Vm, size=3, replace=False) for _ in range(F)]).astype(np.int64)
+    face_of = rng.integers(0, F, size=P)
+    init_faces = torch.from_numpy(faces[face_of])
+    init_barys = torch.from_numpy(rng.dirichlet(np.ones(3), size=P).astype(np.float32))
+    tmpl = torch.randn(Vm, 3, generator=g) * 0.4
+    posed_m = (tmpl * 1.05 + 0.01 * torch.randn(Vm, 3, generator=g)).requires_grad_(True)
+    d_node = torch.randn(Vm, 3, generator=g) * 0.005
+    d_bary_m = (torch.tanh(torch.randn(P, 3, generator=g)) * 0.05).requires_grad_(True)
+    geo_m = SimpleNamespace(get=lambda lbs, delta=None: (posed_m if delta is None else posed_m + delta)[None],
+                            body_template_vertices=tmpl[None], init_faces=init_faces, init_barys=init_barys,
+                            mc_source=SimpleNamespace(faces=faces))
+    pkg_m = mn.MeshNet.forward(namespace(P, geo_m, d_bary_m, d_node), batch)
+    up_m = torch.randn(P, 3, generator=g)
+    g_pts, g_dbm = torch.autograd.grad((pkg_m["means3D"] * up_m).sum(), [posed_m, d_bary_m])
+    out.update(m_points=(posed_m.detach() + d_node).numpy(), m_face_ids=init_faces.numpy(), m_barys=init_barys.numpy(),
+               m_delta_bary=d_bary_m.detach().numpy(), m_means3D=pkg_m["means3D"].detach().numpy(),
+               m_canonical_means3D=pkg_m["canonical_means3D"].detach().numpy(), m_up_means=up_m.numpy(),
+               m_grad_points=g_pts.numpy(), m_grad_delta_bary=g_dbm.numpy())
+    np.savez(os.path.join(OUT, "interp_cases.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_harness()
+    if sys.argv[1:] == ["interp"]:              # one section only (the other fixtures are left untouched)
+        import models.cage_net as cn
+        import models.mesh_net as mn
+        from lib.cage import CageBase
+        gen_interp(cn, CageBase, mn)
+        return
     if sys.argv[1:] == ["skeleton"]:            # one section only (the other fixtures are left untouched)
         import lbsmodel.body_model as bm
         gen_skeleton(bm)
