@@ -116,6 +116,15 @@ class Skeleton(ctypes.Structure):
                                                "csc_row", "csc_val")]
 
 
+CODE_MAX_B, CODE_MAX_D = 16, 4096    # D3GA_CODE_MAX_B, D3GA_CODE_MAX_D (include/d3ga.h): indices per lookup, widest code row
+ROW_CACHE_MAX_PAIRS = 16             # D3GA_ROW_CACHE_MAX_PAIRS: (table, stage) pairs of one d3ga_row_cache_select
+
+
+class RowPair(ctypes.Structure):
+    """struct d3ga_row_pair (include/d3ga.h): a table (n_rows, width) and its staged row, 4-byte words."""
+    _fields_ = [("table", ctypes.c_void_p), ("stage", ctypes.c_void_p), ("width", ctypes.c_int32), ("n_rows", ctypes.c_int32)]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _prm = ctypes.POINTER(RasterParams)
 _bm = ctypes.POINTER(BodyModel)
@@ -240,6 +249,12 @@ _SIGNATURES = {
     "d3ga_lpips_input": ([ctypes.c_int32] * 4 + [_vp, _vp, _vp], _i),
     "d3ga_lpips_tap": ([ctypes.c_int32] * 4 + [_vp] * 6 + [ctypes.c_int32, _vp], _i),
     "d3ga_lpips_scratch_bytes": ([ctypes.c_int32] * 3 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _i),
+    "d3ga_code_lookup_fwd": ([_vp, _vp] + [ctypes.c_int32] * 3 + [_f, _vp, _vp], _i),
+    "d3ga_code_lookup_bwd": ([_vp, _vp] + [ctypes.c_int32] * 3 + [_vp, _vp], _i),
+    "d3ga_table_mean_scratch_bytes": ([ctypes.c_int32] * 2 + [ctypes.POINTER(_i64)], _i),
+    "d3ga_table_mean": ([_vp] + [ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
+    "d3ga_row_cache_select": ([ctypes.POINTER(RowPair), ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "d3ga_row_cache_flush": ([ctypes.POINTER(RowPair), ctypes.c_int32, _vp, _vp, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -4,7 +4,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["deform.hip", "raster_pre.hip", "raster_bin.hip", "raster_composite.hip", "raster_composite_scan.hip", "raster_api.hip", "bary.hip", "loss.hip", "image_tail.hip", "calib.hip", "frame_prep.hip", "eval.hip", "mesh_raster.hip", "point_raster.hip", "optim.hip", "mlp.hip", "encoding.hip", "body_model.hip", "skeleton.hip", "perceptual.hip", "lpips.hip", "knn.hip", "bary_interp.hip"]
+SOURCES = ["deform.hip", "raster_pre.hip", "raster_bin.hip", "raster_composite.hip", "raster_composite_scan.hip", "raster_api.hip", "bary.hip", "loss.hip", "image_tail.hip", "calib.hip", "frame_prep.hip", "eval.hip", "mesh_raster.hip", "point_raster.hip", "optim.hip", "mlp.hip", "encoding.hip", "body_model.hip", "skeleton.hip", "perceptual.hip", "lpips.hip", "knn.hip", "bary_interp.hip", "frame_state.hip"]
 LINK_MAP = os.path.join(HERE, "d3ga.map")
 HEADERS = ["d3ga_math.h", "d3ga_internal.h", "raster_pre_body.h", "composite_common.h", "body_model_math.h", "skeleton_math.h", "frame_prep_math.h", "eval_math.h", "mesh_raster_math.h", "point_raster_math.h", "perceptual_math.h", "lpips_math.h", "knn_math.h", os.path.join("..", "..", "include", "d3ga.h")]
 ABL = os.environ.get("D3GA_SCAN_ABL")       # timing ablation of the compositing backward (wrong results): own objects + .so
@@ -35,6 +35,7 @@ EXTRA["mesh_raster.hip"] = ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-co
 EXTRA["lpips.hip"] = ["-fhip-fp32-correctly-rounded-divide-sqrt"]        # hipcc's default, stated: a unit vector is a float32 division by a float32 square root
 EXTRA["point_raster.hip"] = EXTRA["mesh_raster.hip"]                   # the same, for point_raster_math.h: membership is cut from float32 arithmetic
 EXTRA["knn.hip"] = ["-ffp-contract=off"]                               # the g++ build of knn_math.h is the yardstick: same distances, same order
+EXTRA["frame_state.hip"] = ["-fhip-fp32-correctly-rounded-divide-sqrt"]  # hipcc's default, stated: torch's renorm test is cut from a float32 square root
 if os.environ.get("D3GA_CHAIN_WAVES"):                      # A/B: wavefronts per workgroup of the fused field-network kernel
     FLAGS.append("-DD3GA_CHAIN_WAVES=" + os.environ["D3GA_CHAIN_WAVES"])
 if os.environ.get("D3GA_CHAIN_CS"):                           # A/B: k-steps per weight chunk of the fused field-network kernel

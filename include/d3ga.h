@@ -28,7 +28,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 112 /* (the d3ga_vgg_* and d3ga_bary_interp_* entry points were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* (the d3ga_vgg_*, d3ga_bary_interp_* and the frame-state entry points d3ga_code_lookup_*, d3ga_table_mean*, d3ga_row_cache_* were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -1137,6 +1137,48 @@ int d3ga_lpips_input(int32_t N, int32_t H, int32_t W, int32_t normalize, const f
 int d3ga_lpips_tap(int32_t B, int32_t h, int32_t w, int32_t C, const float *a, const float *b, const float *lin, float *map,
                    float *partials, float *value, int32_t accumulate, d3ga_stream_t stream);
 int d3ga_lpips_scratch_bytes(int32_t B, int32_t H, int32_t W, const int32_t *widths, int64_t *out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Per-frame state addressed by a device index: the frame codes and the refined SMPL-X parameters of
+ * models/garment_net.py:87-107, 163-178, 211-235, so that a captured step follows the frame of every replay.  No entry point
+ * allocates or synchronises; all are capturable; no atomics, every sum in a fixed order: results are reproducible bit for bit.
+ *
+ * d3ga_code_lookup_fwd: models/embeddings.py:31-36 over nn.Embedding(max_norm).  table (N,D), idx (B) int32 ON THE DEVICE, each
+ *   clamped into [0, N-1] (the reference clamps the top only) -> out (B,D).  First torch's embedding_renorm_, IN PLACE on
+ *   table: every distinct looked-up row whose L2 norm is > max_norm (strictly) is multiplied by max_norm / (norm + 1e-7);
+ *   max_norm <= 0: no renorm.  Then the rows are copied.  A row named several times is renormed once and all its copies in
+ *   out are equal.  One launch.  1 <= B <= D3GA_CODE_MAX_B, 1 <= D <= D3GA_CODE_MAX_D, N D <= INT32_MAX, else D3GA_E_SIZE.
+ * d3ga_code_lookup_bwd: dout (B,D) -> dtable (N,D), the dense gradient nn.Embedding produces.  EVERY element is written: the sum
+ *   of dout[b] over the b with idx[b] = row, in increasing b; zero for a row nobody names (no separate clear).  One launch.
+ * d3ga_table_mean: Embedding.average(): out (D) = the mean of table (N,D) over its rows, summed in float64 in two stages of a
+ *   fixed order (two launches) through `scratch`, d3ga_table_mean_scratch_bytes(N, D) bytes, 8-byte aligned (else D3GA_E_CONFIG).
+ * d3ga_row_cache_select: desc (HOST, copied into the launch) lists n_pairs <= D3GA_ROW_CACHE_MAX_PAIRS pairs of a table
+ *   (n_rows, width) and a stage (width) of 4-byte words; idx, prev, flag: one int32 each on the device.  In one launch:
+ *     1. if prev >= 0, every stage is copied back into row prev of its table;  2. row idx of every table is copied into its
+ *     stage;  3. prev = idx.
+ *   idx == prev changes nothing.  idx outside [0, n_rows) of ANY pair (or a prev that is not -1 or a row): nothing moves, prev
+ *   stays, and flag is set to 1 (sticky: nobody clears it but the caller).
+ * d3ga_row_cache_flush: step 1 alone; prev stays.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_CODE_MAX_B 16
+#define D3GA_CODE_MAX_D 4096
+#define D3GA_TABLE_MEAN_CHUNKS 64
+#define D3GA_ROW_CACHE_MAX_PAIRS 16
+typedef struct d3ga_row_pair {
+    float *table;
+    float *stage;
+    int32_t width;
+    int32_t n_rows;
+} d3ga_row_pair;
+int d3ga_code_lookup_fwd(float *table, const int32_t *idx, int32_t N, int32_t D, int32_t B, float max_norm, float *out,
+                         d3ga_stream_t stream);
+int d3ga_code_lookup_bwd(const float *dout, const int32_t *idx, int32_t N, int32_t D, int32_t B, float *dtable,
+                         d3ga_stream_t stream);
+int d3ga_table_mean_scratch_bytes(int32_t N, int32_t D, int64_t *bytes);
+int d3ga_table_mean(const float *table, int32_t N, int32_t D, float *out, void *scratch, d3ga_stream_t stream);
+int d3ga_row_cache_select(const d3ga_row_pair *desc, int32_t n_pairs, const int32_t *idx, int32_t *prev, int32_t *flag,
+                          d3ga_stream_t stream);
+int d3ga_row_cache_flush(const d3ga_row_pair *desc, int32_t n_pairs, int32_t *prev, int32_t *flag, d3ga_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
