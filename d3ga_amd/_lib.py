@@ -125,6 +125,24 @@ class RowPair(ctypes.Structure):
     _fields_ = [("table", ctypes.c_void_p), ("stage", ctypes.c_void_p), ("width", ctypes.c_int32), ("n_rows", ctypes.c_int32)]
 
 
+SCALE_ACT_NONE, SCALE_ACT_EXP = 0, 1     # D3GA_SCALE_ACT_* (include/d3ga.h)
+SCALE_ENERGY_GRID = 1536                 # D3GA_SCALE_ENERGY_GRID: workgroups (256 threads x 4 floats) of scale_energy's first stage, at most
+OBJ_MAX_FRAMES, OBJ_SLOTS, OBJ_MAX_LEN, OBJ_TERMS = 16, 9, 4096, 9    # D3GA_OBJ_* (include/d3ga.h)
+OBJ_STATUS_NAN_SEEN, OBJ_STATUS_FIRST_BAD, OBJ_STATUS_STEPS, OBJ_STATUS_TERMS, OBJ_STATUS_WORDS = 0, 1, 2, 4, 16
+
+
+class ObjectiveEntry(ctypes.Structure):
+    """struct d3ga_objective_entry (include/d3ga.h): one input of one frame, and where its gradient goes."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("len", ctypes.c_int32), ("goff", ctypes.c_int32)]
+
+
+class ObjectiveDesc(ctypes.Structure):
+    """struct d3ga_objective_desc (include/d3ga.h): the weights and the frame-major table of entries."""
+    _fields_ = [("n_frames", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_float) for n in ("lambda_dssim", "rgb_weight", "sil_weight", "fme_weight", "blur_weight", "vgg_weight")] + \
+               [("entry", ObjectiveEntry * (OBJ_MAX_FRAMES * OBJ_SLOTS))]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _prm = ctypes.POINTER(RasterParams)
 _bm = ctypes.POINTER(BodyModel)
@@ -255,6 +273,10 @@ _SIGNATURES = {
     "d3ga_table_mean": ([_vp] + [ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
     "d3ga_row_cache_select": ([ctypes.POINTER(RowPair), ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
     "d3ga_row_cache_flush": ([ctypes.POINTER(RowPair), ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_scale_energy_fwd": ([_i64, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_scale_energy_bwd": ([_i64, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_objective_fwd": ([ctypes.POINTER(ObjectiveDesc), _vp, _vp, _vp], _i),
+    "d3ga_objective_bwd": ([ctypes.POINTER(ObjectiveDesc), _vp, _vp, _i64, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -28,7 +28,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 112 /* (the d3ga_vgg_*, d3ga_bary_interp_* and the frame-state entry points d3ga_code_lookup_*, d3ga_table_mean*, d3ga_row_cache_* were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* (the d3ga_vgg_*, d3ga_bary_interp_* and the frame-state entry points d3ga_code_lookup_*, d3ga_table_mean*, d3ga_row_cache_*, and the objective's d3ga_scale_energy_*, d3ga_objective_* were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -1179,6 +1179,61 @@ int d3ga_table_mean(const float *table, int32_t N, int32_t D, float *out, void *
 int d3ga_row_cache_select(const d3ga_row_pair *desc, int32_t n_pairs, const int32_t *idx, int32_t *prev, int32_t *flag,
                           d3ga_stream_t stream);
 int d3ga_row_cache_flush(const d3ga_row_pair *desc, int32_t n_pairs, int32_t *prev, int32_t *flag, d3ga_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The training objective: the scale regulariser of models/cage_net.py:214, 226 and the block of train.py:190-244
+ * that turns the per-frame losses and regularisers into the weighted total, with the NaN test of train.py:64-69 left on the
+ * device.  No entry point allocates or synchronises; all are capturable; no atomics, every sum in a fixed order (written down
+ * in csrc/objective_math.h): results are reproducible bit for bit.
+ *
+ * d3ga_scale_energy_fwd: out[0] = (1/n) sum_i act(scaling_i + delta_i)^2 over n floats (delta NULL: 0); activation
+ *   D3GA_SCALE_ACT_EXP | D3GA_SCALE_ACT_NONE (else D3GA_E_CONFIG).  Two launches: one partial sum per workgroup into `partials`
+ *   (>= D3GA_LOSS_PARTIALS floats, contents irrelevant), then one workgroup adds them in index order.  scaling and delta
+ *   16-byte aligned (else D3GA_E_CONFIG).
+ * d3ga_scale_energy_bwd: grad_i = g[0] * d/dx act(x_i)^2 / n with x = scaling + delta, the activation recomputed: the ONE array
+ *   both inputs receive.  g on the device.  One launch; grad 16-byte aligned too.
+ * d3ga_objective_fwd: desc (HOST, copied into the launch: the table of pointers and lengths travels in the kernel arguments,
+ *   as d3ga_row_cache_select's does) lists, for each of 1 <= n_frames <= D3GA_OBJ_MAX_FRAMES frames, D3GA_OBJ_SLOTS entries in
+ *   the order l1, ssim, sil_l1 (1 float each), scale_energy (n_cages), fm_energy (n_cages | absent), frame_encoding (D),
+ *   optimizable_poses (N | absent), blur_weights (n | absent), vgg (1 | absent); an absent entry has ptr NULL, and every frame
+ *   must have the same entries present with the same lengths of scale_energy and fm_energy (else D3GA_E_CONFIG); lengths
+ *   1..D3GA_OBJ_MAX_LEN (else D3GA_E_SIZE).  out (1 + D3GA_OBJ_TERMS floats): out[0] = total, out[1..] = color_loss, sil_loss,
+ *   scale_loss, fme_loss, blur_loss, vgg_loss, bg_loss (= 0), codes_reg, total_loss.  status (D3GA_OBJ_STATUS_WORDS int32,
+ *   zeroed once by the caller): [STEPS] is incremented; on the first call whose total is NaN (not on an infinite one)
+ *   [NAN_SEEN] = 1, [FIRST_BAD] = the value of [STEPS] before that call, and words [TERMS .. TERMS + 8] keep that call's terms as
+ *   float bits.  One launch of one workgroup.  Calls that share a status cell must be ordered on one stream.
+ * d3ga_objective_bwd: every entry with goff >= 0 gets d total / d entry * g[0] written to grads[goff .. goff + len) (n_grads
+ *   floats; an entry reaching outside: D3GA_E_SIZE); goff < 0: no gradient.  g on the device.  One launch.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_SCALE_ACT_NONE 0
+#define D3GA_SCALE_ACT_EXP 1
+#define D3GA_SCALE_ENERGY_GRID 1536 /* workgroups of 256 x 4 floats, at most: one pass covers 3 * 2^19 floats */
+#define D3GA_OBJ_MAX_FRAMES 16
+#define D3GA_OBJ_SLOTS 9
+#define D3GA_OBJ_MAX_LEN 4096
+#define D3GA_OBJ_TERMS 9
+#define D3GA_OBJ_STATUS_NAN_SEEN 0
+#define D3GA_OBJ_STATUS_FIRST_BAD 1
+#define D3GA_OBJ_STATUS_STEPS 2
+#define D3GA_OBJ_STATUS_TERMS 4
+#define D3GA_OBJ_STATUS_WORDS 16
+typedef struct d3ga_objective_entry {
+    const float *ptr;
+    int32_t len;
+    int32_t goff;
+} d3ga_objective_entry;
+typedef struct d3ga_objective_desc {
+    int32_t n_frames;
+    int32_t reserved;
+    float lambda_dssim, rgb_weight, sil_weight, fme_weight, blur_weight, vgg_weight;
+    d3ga_objective_entry entry[D3GA_OBJ_MAX_FRAMES * D3GA_OBJ_SLOTS]; /* frame-major */
+} d3ga_objective_desc;
+int d3ga_scale_energy_fwd(int64_t n, const float *scaling, const float *delta, int32_t activation, float *out, float *partials,
+                          d3ga_stream_t stream);
+int d3ga_scale_energy_bwd(int64_t n, const float *scaling, const float *delta, int32_t activation, const float *g, float *grad,
+                          d3ga_stream_t stream);
+int d3ga_objective_fwd(const d3ga_objective_desc *desc, float *out, int32_t *status, d3ga_stream_t stream);
+int d3ga_objective_bwd(const d3ga_objective_desc *desc, const float *g, float *grads, int64_t n_grads, d3ga_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
