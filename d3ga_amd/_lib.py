@@ -149,6 +149,9 @@ _bm = ctypes.POINTER(BodyModel)
 _lpg = ctypes.POINTER(LbsPoseGrad)
 _sk = ctypes.POINTER(Skeleton)
 
+# what the *_deform entries take behind their parent's arguments: the deform backward that runs as the per-Gaussian kernel's tail
+_deform_tail = [ctypes.POINTER(c) for c in (CageDeformIn, CageDeformGrads, CageDeformRoute)]
+
 # name -> (argtypes, restype); the trailing _vp of every launch entry is the hipStream_t
 _SIGNATURES = {
     "d3ga_version": ([], _i),
@@ -160,6 +163,7 @@ _SIGNATURES = {
     "d3ga_lbs_pose_scratch_bytes": ([_i, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _i),
     "d3ga_cage_deform_fwd": ([ctypes.POINTER(CageDeformIn), _vp, _vp, _vp], _i),
     "d3ga_cage_deform_bwd": ([ctypes.POINTER(c) for c in (CageDeformIn, CageDeformGrads, CageDeformRoute, CageDeformSkin)] + [_lpg, _vp], _i),
+    "d3ga_cage_deform_bwd_tail": ([ctypes.POINTER(c) for c in (CageDeformIn, CageDeformGrads, CageDeformRoute, CageDeformSkin)] + [_lpg, _vp], _i),
     "d3ga_fem_energy_fwd": ([_i] + [_vp] * 4 + [_vp], _i),
     "d3ga_fem_energy_bwd": ([_i, _i] + [_vp] * 5 + [_vp], _i),
     "d3ga_bary_interp_fwd": ([ctypes.c_int32] * 3 + [_vp] * 5 + [_vp], _i),
@@ -180,11 +184,14 @@ _SIGNATURES = {
     "d3ga_raster_composite_fwd2": ([_prm, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i),
     "d3ga_raster_composite_bwd2": ([_prm, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i),
     "d3ga_raster_preprocess_bwd": ([_prm] + [_vp] * 18 + [_vp], _i),
+    "d3ga_raster_preprocess_bwd_deform": ([_prm] + [_vp] * 18 + _deform_tail + [_vp], _i),
     "d3ga_raster_forward": ([_prm] + [_vp] * 14 + [_i64, _vp, _vp, _vp, _vp], _i),
     "d3ga_raster_backward": ([_prm] + [_vp] * 11 + [_i64] + [_vp] * 11 + [_vp], _i),
+    "d3ga_raster_backward_deform": ([_prm] + [_vp] * 11 + [_i64] + [_vp] * 11 + _deform_tail + [_vp], _i),
     "d3ga_raster_composite_fwd_l1": ([_prm, _vp, _vp, _vp, _i64] + [_vp] * 7 + [_vp], _i),
     "d3ga_raster_composite_bwd_l1": ([_prm, _vp, _vp, _vp, _i64] + [_vp] * 7 + [_vp], _i),
     "d3ga_raster_backward_l1": ([_prm] + [_vp] * 11 + [_i64] + [_vp] * 15 + [_vp], _i),
+    "d3ga_raster_backward_l1_deform": ([_prm] + [_vp] * 11 + [_i64] + [_vp] * 15 + _deform_tail + [_vp], _i),
     "d3ga_raster_recolor": ([_prm] + [_vp] * 6 + [_vp], _i),
     "d3ga_raster_mark_visible": ([ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
     "d3ga_sh_grad_from_views": ([ctypes.c_int32] * 4 + [_vp, _vp, _i64, _vp, _i64, ctypes.c_float, _vp, _vp], _i),

@@ -133,34 +133,47 @@ def _deform_saved(saved, has_delta_barys):
     return inputs
 
 
-def _deform_bwd(inputs, flags, g_means, g_cov6, *, want_tetpoints=False, want_barys, want_scales, want_rotations, skin=None, pose=None):
-    """The one call of d3ga_cage_deform_bwd.  inputs: _deform_saved(...); want_*: which gradients to form.
-    skin = dict(joint_mats, skin_idx, skin_w, Rh | None, g_extra | None): the skinning tail, whose g_delta stands in for the vertex
-    gradient; pose = dict(template, delta | None) adds the pose gradients to it.
-    -> dict(vertices = g_tetpoints | g_delta, barys, scales, rotations, pose = (gA, gRh, gTh)), None where not wanted."""
+def _route(tetras, tetra_id, P, V, dev, merged, records=None):
+    """struct d3ga_cage_deform_route over the static binding, with fresh records unless given: the block-merge plan (`merged`) or
+    the per-corner records.  -> (struct, records, merged); the tensors must stay alive until the launches are queued."""
+    new = lambda n: torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if merged:
+        plan = merge_plan(tetras, tetra_id, V)
+        records = new(max(plan["n_segments"], 1)) if records is None else records
+        return _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=plan["n_segments"], item_pos=dptr(plan["item_pos"]),
+                                    seg_ptr=dptr(plan["seg_ptr"]), seg_begin=dptr(plan["seg_begin"]),
+                                    vert_start=dptr(plan["vert_start"]), vert_items=dptr(plan["vert_parts"]),
+                                    records=dptr(records)), records, True
+    vstart, vitems = vertex_adjacency(tetras, tetra_id, V)
+    records = new(4 * P) if records is None else records
+    return _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_CORNERS, vert_start=dptr(vstart), vert_items=dptr(vitems),
+                                records=dptr(records)), records, False
+
+
+def _route_choice(P, want_vertices, skinned):
+    """Which route a backward takes -> None (no vertex gradient wanted) | True (block merge) | False (per-corner records).
+    (P == 0 without the skinning tail: the library zeroes g_tetpoints without a route.)"""
+    if skinned or (want_vertices and P > 0 and _merge_policy["enabled"]):
+        return True
+    return False if (want_vertices and P > 0) else None
+
+
+def _deform_call(entry, inputs, flags, g_means, g_cov6, g_b, g_s, g_r, *, want_tetpoints, skin, pose, route_records=None):
+    """One call of d3ga_cage_deform_bwd (`entry`) or d3ga_cage_deform_bwd_tail (on `route_records` = (records, merged) that a
+    render's backward filled) -> (g_tetpoints | g_delta | None, (gA, gRh, gTh) | None, the route's records | None)."""
     tetras, tetra_id = inputs["tetras"], inputs["tetra_id"]
     st = _deform_in(flags=flags, **inputs)
     P, V, dev = st.P, st.V, inputs["barys"].device
-
-    def new(n, c, on=True):
-        return torch.empty((n, c), dtype=torch.float32, device=dev) if on else None
-    g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
-    g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
-    g_v, g_b, g_s, g_r = new(V, 3, want_tetpoints or skin is not None), new(P, 4, want_barys), new(P, 3, want_scales), new(P, 4, want_rotations)
+    g_v = torch.empty((V, 3), dtype=torch.float32, device=dev) if (want_tetpoints or skin is not None) else None
     grads = _lib.CageDeformGrads(g_means=dptr(g_means), g_cov6=dptr(g_cov6), g_tetpoints=dptr(None if skin is not None else g_v),
                                  g_barys=dptr(g_b), g_scales=dptr(g_s), g_rots=dptr(g_r))
-    route = tail = pose_st = pose_out = None
-    if skin is not None or (g_v is not None and P > 0 and _merge_policy["enabled"]):
-        plan = merge_plan(tetras, tetra_id, V)
-        records = new(max(plan["n_segments"], 1), 3)
-        route = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_MERGE, n_segments=plan["n_segments"], item_pos=dptr(plan["item_pos"]),
-                                     seg_ptr=dptr(plan["seg_ptr"]), seg_begin=dptr(plan["seg_begin"]),
-                                     vert_start=dptr(plan["vert_start"]), vert_items=dptr(plan["vert_parts"]), records=dptr(records))
-    elif g_v is not None and P > 0:          # (P == 0: the library zeroes g_tetpoints without a route)
-        vstart, vitems = vertex_adjacency(tetras, tetra_id, V)
-        records = new(4 * P, 3)
-        route = _lib.CageDeformRoute(kind=_lib.DEFORM_ROUTE_CORNERS, vert_start=dptr(vstart), vert_items=dptr(vitems),
-                                     records=dptr(records))
+    route = tail = pose_st = pose_out = records = None
+    if route_records is not None:
+        route, records, _ = _route(tetras, tetra_id, P, V, dev, route_records[1], route_records[0])
+    else:
+        merged = _route_choice(P, g_v is not None, skin is not None)
+        if merged is not None:
+            route, records, _ = _route(tetras, tetra_id, P, V, dev, merged)
     if skin is not None:
         g_extra = _f32c(skin["g_extra"])
         tail = _lib.CageDeformSkin(K=skin["skin_w"].shape[1], joint_mats=dptr(skin["joint_mats"]), skin_idx=dptr(skin["skin_idx"]),
@@ -169,9 +182,184 @@ def _deform_bwd(inputs, flags, g_means, g_cov6, *, want_tetpoints=False, want_ba
             plan_p = lbs_pose_plan(skin["skin_idx"], skin["joint_mats"].shape[0])
             pose_st, pose_out, scratch = _pose_grad_struct(plan_p, V, 1, pose["template"], pose["delta"], dev)
     ref = lambda x: None if x is None else ctypes.byref(x)
-    check(_lib.lib().d3ga_cage_deform_bwd(ctypes.byref(st), ctypes.byref(grads), ref(route), ref(tail), ref(pose_st),
-                                          stream_handle()), "d3ga_cage_deform_bwd")
+    check(getattr(_lib.lib(), entry)(ctypes.byref(st), ctypes.byref(grads), ref(route), ref(tail), ref(pose_st), stream_handle()), entry)
+    return g_v, pose_out, records
+
+
+def _deform_bwd(inputs, flags, g_means, g_cov6, *, want_tetpoints=False, want_barys, want_scales, want_rotations, skin=None, pose=None,
+                deposit=None):
+    """The one call of d3ga_cage_deform_bwd.  inputs: _deform_saved(...); want_*: which gradients to form.
+    skin = dict(joint_mats, skin_idx, skin_w, Rh | None, g_extra | None): the skinning tail, whose g_delta stands in for the vertex
+    gradient; pose = dict(template, delta | None) adds the pose gradients to it.
+    deposit: what a claimed render's backward left on the node (render fusion, below) -- the per-Gaussian gradients and the
+    route's records of the render's share.  Without incoming gradients only the tails run, on the deposited records
+    (d3ga_cage_deform_bwd_tail); with incoming gradients (a second consumer of the node's outputs) the kernel runs on them as
+    always and the deposit's share is added: the backward is linear.
+    -> dict(vertices = g_tetpoints | g_delta, barys, scales, rotations, pose = (gA, gRh, gTh)), None where not wanted."""
+    P, dev = inputs["barys"].shape[0], inputs["barys"].device
+    wants_v = want_tetpoints or skin is not None
+
+    def tail_of_deposit(skin):
+        if not wants_v or deposit["records"] is None:
+            return None, None
+        return _deform_call("d3ga_cage_deform_bwd_tail", inputs, flags, None, None, None, None, None, want_tetpoints=want_tetpoints,
+                            skin=skin, pose=pose, route_records=(deposit["records"], deposit["merged"]))[:2]
+    if deposit is not None and g_means is None and g_cov6 is None:
+        _last_path[0] = "fused-tail"
+        g_v, pose_out = tail_of_deposit(skin)
+        return dict(vertices=g_v, barys=deposit["barys"], scales=deposit["scales"], rotations=deposit["rotations"], pose=pose_out)
+
+    def new(n, c, on=True):
+        return torch.empty((n, c), dtype=torch.float32, device=dev) if on else None
+    g_means = torch.zeros((P, 3), device=dev) if g_means is None else _f32c(g_means)
+    g_cov6 = torch.zeros((P, 6), device=dev) if g_cov6 is None else _f32c(g_cov6)
+    g_b, g_s, g_r = new(P, 4, want_barys), new(P, 3, want_scales), new(P, 4, want_rotations)
+    g_v, pose_out, _ = _deform_call("d3ga_cage_deform_bwd", inputs, flags, g_means, g_cov6, g_b, g_s, g_r, want_tetpoints=want_tetpoints,
+                                    skin=skin, pose=pose)
+    _last_path[0] = "kernel" if deposit is None else "kernel+deposit"
+    if deposit is not None:
+        deposit["binding"]._render_fusion_demoted = _fusion["epoch"]
+        # the render's share: its per-Gaussian gradients as deposited, its vertex / pose gradients from the tails on its records
+        # (g_extra has joined above, once)
+        d_v, d_pose = tail_of_deposit(None if skin is None else dict(skin, g_extra=None))
+        for mine, theirs in ((g_b, deposit["barys"]), (g_s, deposit["scales"]), (g_r, deposit["rotations"]), (g_v, d_v)):
+            if mine is not None and theirs is not None:
+                mine.add_(theirs)
+        if pose_out is not None and d_pose is not None:
+            for mine, theirs in zip(pose_out, d_pose):
+                mine.add_(theirs)
     return dict(vertices=g_v, barys=g_b, scales=g_s, rotations=g_r, pose=pose_out)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# render fusion: the per-Gaussian part of this backward as the tail of the rasterizer's per-Gaussian backward
+# ------------------------------------------------------------------------------------------------------------
+# When a render's means3D and cov3D_precomp ARE the two outputs of one deform node (models/cage_net.py:213-230 feeding the
+# renderer), the rasterizer's backward need not write dL/dmeans3D and dL/dcov3D for this node to read back: its per-Gaussian kernel
+# runs the deform backward on them while they are in registers (d3ga_raster_*_deform).  The handshake: renderer.render CLAIMS the
+# node before its operator is applied (claim_for_render); the claimed render's backward fills the node's per-Gaussian gradients
+# and route records (fused_tail_structs) and DEPOSITS them on the node, returning no gradient for the two tensors; the node's
+# backward then runs only its tails on the deposit -- or, when another consumer of its outputs did send gradients, its kernel
+# on those and adds the deposit.  One render per node and forward pass: a second render of the same package (the silhouette pass of
+# models/trainer.py:102-110) goes the usual way AND revokes the first one's claim -- its gradients make the node run its kernel
+# anyway, and kernel + tails on a deposit + the sums cost more launches than the fusion saves.  Both renders then take the
+# two-kernel path, as with fusion off.  The same holds for any other consumer of the node's outputs that sends gradients (view
+# directions for a colour network): that cannot be known when the render claims, so a binding whose node once ran "kernel+deposit"
+# is DEMOTED -- not claimed again until set_render_fusion() is called -- and a training loop pays for it in its first step only
+# (the warm-up steps of a graph capture included: the captured step is then the two-kernel one).  The mark is an attribute of the
+# binding's `tetra_id` tensor (the int32 buffer the operator was handed, or its cached int32 copy): it lives and dies with it.
+_fusion = {"enabled": True, "epoch": 0}      # epoch: marks of an earlier one no longer count
+_last_path = [None]
+_REVOKED = "revoked"      # node.claimed: False | the key of the claiming render's token | _REVOKED (until the node's backward clears it)
+
+
+def set_render_fusion(enabled):
+    """Switch the render fusion (on by default).  Off: every backward takes the two-kernel path.  Either way demoted bindings
+    (see above) are re-armed."""
+    _fusion["enabled"] = bool(enabled)
+    _fusion["epoch"] += 1
+
+
+def last_backward_path():
+    """How the most recent deform backward of this process ran: "fused-tail" (only the tails, on a render's deposit), "kernel"
+    (the per-Gaussian kernel on incoming gradients) or "kernel+deposit" (both, added); None before the first.  Tests and tools."""
+    return _last_path[0]
+
+
+def _node_state(node):
+    """(inputs, flags, wants, skinned, vertex gradient wanted) of a deform node, from what its forward saved."""
+    lbs = isinstance(node, _LbsCageDeform._backward_cls)
+    need = node.needs_input_grad
+    inputs = _deform_saved(node.saved_tensors, node.has_dbary if lbs else node.has_delta)
+    o = 6 if lbs else 0                     # _LbsCageDeform: lbs_cage's seven inputs stand where _CageDeform has tetpoints
+    wants = dict(want_barys=need[o + 3] or need[o + 7], want_scales=need[o + 5], want_rotations=need[o + 6])
+    return inputs, node.flags, wants, lbs, (True if lbs else need[0])
+
+
+def claim_for_render(means3D, cov3D_precomp):
+    """-> (node, token): the deform node that made both tensors, claimed for the calling render, or (None, None) -- the render
+    then goes the usual way: fusion is on, gradients are recorded, the two tensors are outputs 0 and 1 of ONE _CageDeform /
+    _LbsCageDeform node that no earlier render of this forward pass has claimed (a second one revokes the first one's claim), and
+    nobody asked for their own gradients (retain_grad, tensor hooks).  The claim holds while `holds_claim(node, token)`: the
+    token remembers the two tensors, and a retain_grad() or hook that arrives between the render and its backward ends the claim
+    there (the render then returns their gradients as always)."""
+    none = (None, None)
+    if not _fusion["enabled"] or means3D is None or cov3D_precomp is None or not torch.is_grad_enabled():
+        return none
+    node = means3D.grad_fn
+    if node is None or node is not cov3D_precomp.grad_fn or means3D.shape[0] == 0:
+        return none
+    if not isinstance(node, (_CageDeform._backward_cls, _LbsCageDeform._backward_cls)):
+        return none
+    if means3D.output_nr != 0 or cov3D_precomp.output_nr != 1:
+        return none
+    if getattr(node, "claimed", _REVOKED) is not False:
+        node.claimed = _REVOKED
+        return none
+    if getattr(node.binding, "_render_fusion_demoted", None) == _fusion["epoch"]:
+        return none
+    if _wants_own_gradient(means3D, cov3D_precomp):
+        return none
+    token = _Claim(means3D, cov3D_precomp)
+    node.claimed = token.key
+    return node, token
+
+
+class _Claim:
+    """A render's claim: the key the node carries while it holds, and the two tensors (kept by the render alone -- the node must
+    not reference its own outputs)."""
+
+    def __init__(self, *tensors):
+        self.key, self.tensors = object(), tensors
+
+
+def _wants_own_gradient(*tensors):
+    return any(t.retains_grad or t._backward_hooks for t in tensors)
+
+
+def holds_claim(node, token):
+    """Asked by the claimed render's backward: is the node still its own, and does still nobody want the two tensors' gradients?"""
+    if node is None or token is None or getattr(node, "claimed", None) is not token.key:
+        return False
+    if _wants_own_gradient(*token.tensors):
+        node.claimed = False
+        return False
+    return True
+
+
+def release_claim(node, token):
+    """A claimed render that cannot take the fused path after all (its operator found a reason) gives the node back."""
+    if node is not None and token is not None and getattr(node, "claimed", None) is token.key:
+        node.claimed = False
+
+
+def fused_tail_structs(node):
+    """For the claimed render's backward: (struct d3ga_cage_deform_in, struct d3ga_cage_deform_grads, struct d3ga_cage_deform_route
+    | None, deposit) of `node` with fresh outputs.  The caller passes the three structs to a d3ga_raster_*_deform entry and then
+    hands `deposit` (which keeps every tensor alive) to `deposit_on`."""
+    inputs, flags, wants, skinned, want_v = _node_state(node)
+    st = _deform_in(flags=flags, **inputs)
+    P, V, dev = st.P, st.V, inputs["barys"].device
+    new = lambda c, on: torch.empty((P, c), dtype=torch.float32, device=dev) if on else None
+    g_b, g_s, g_r = new(4, wants["want_barys"]), new(3, wants["want_scales"]), new(4, wants["want_rotations"])
+    grads = _lib.CageDeformGrads(g_means=None, g_cov6=None, g_tetpoints=None, g_barys=dptr(g_b), g_scales=dptr(g_s), g_rots=dptr(g_r))
+    merged = _route_choice(P, want_v, skinned)
+    route = records = None
+    if merged is not None:
+        route, records, merged = _route(inputs["tetras"], inputs["tetra_id"], P, V, dev, merged)
+    return st, grads, route, dict(barys=g_b, scales=g_s, rotations=g_r, records=records, merged=merged, pins=inputs, binding=node.binding)
+
+
+def deposit_on(node, deposit):
+    node.deposit = deposit
+
+
+def _take_deposit(ctx):
+    """The node's deposit, if a claimed render left one; deposit and claim are cleared whatever happens next."""
+    deposit, ctx.deposit, ctx.claimed = getattr(ctx, "deposit", None), None, False
+    if deposit is not None:
+        deposit.pop("pins", None)
+    return deposit
 
 
 class _CageDeform(torch.autograd.Function):
@@ -182,6 +370,7 @@ class _CageDeform(torch.autograd.Function):
             _f32c, (tetpoints, barys, canon_grad, scales, rotations, delta_barys))
         ctx.flags = flags
         ctx.has_delta = delta_barys is not None
+        ctx.claimed, ctx.deposit, ctx.binding = False, None, tetra_id          # render fusion (above)
         means, cov6 = _deform_fwd(_deform_in(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, flags),
                                   barys.device)
         ctx.set_materialize_grads(False)                 # backward() fills in the gradient of an unused output itself
@@ -192,8 +381,9 @@ class _CageDeform(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_means, g_cov6):
         need = ctx.needs_input_grad
+        deposit = _take_deposit(ctx)
         g = _deform_bwd(_deform_saved(ctx.saved_tensors, ctx.has_delta), ctx.flags, g_means, g_cov6, want_tetpoints=need[0],
-                        want_barys=need[3] or need[7], want_scales=need[5], want_rotations=need[6])
+                        want_barys=need[3] or need[7], want_scales=need[5], want_rotations=need[6], deposit=deposit)
         return (g["vertices"], None, None, g["barys"] if need[3] else None, None, g["scales"], g["rotations"],
                 g["barys"] if need[7] else None, None)
 
@@ -461,6 +651,7 @@ class _LbsCageDeform(torch.autograd.Function):
         tetpoints, lbs_saved = _lbs_fwd(ctx, template, delta, joint_mats, skin_idx, skin_w, Rh, Th)
         barys, canon_grad, scales, rotations, delta_barys = map(_f32c, (barys, canon_grad, scales, rotations, delta_barys))
         ctx.flags, ctx.has_dbary = flags, delta_barys is not None
+        ctx.claimed, ctx.deposit, ctx.binding = False, None, tetra_id          # render fusion (above)
         means, cov6 = _deform_fwd(_deform_in(tetpoints, tetras, tetra_id, barys, canon_grad, scales, rotations, delta_barys, flags),
                                   barys.device)
         ctx.set_materialize_grads(False)
@@ -471,6 +662,7 @@ class _LbsCageDeform(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_means, g_cov6, g_tp_extra):
         need = ctx.needs_input_grad
+        deposit = _take_deposit(ctx)
         inputs = _deform_saved(ctx.saved_tensors, ctx.has_dbary)
         skin, pose = _lbs_saved(ctx, ctx.saved_tensors[8:])
         P, V, dev = inputs["barys"].shape[0], inputs["tetpoints"].shape[0], inputs["barys"].device
@@ -480,7 +672,7 @@ class _LbsCageDeform(torch.autograd.Function):
             g = dict(vertices=torch.empty((0, 3), device=dev), pose=_pose_zeros(skin["joint_mats"].shape[0], dev),
                      barys=zeros(4, want["want_barys"]), scales=zeros(3, want["want_scales"]), rotations=zeros(4, want["want_rotations"]))
         else:
-            g = _deform_bwd(inputs, ctx.flags, g_means, g_cov6, skin=dict(skin, g_extra=g_tp_extra), pose=pose, **want)
+            g = _deform_bwd(inputs, ctx.flags, g_means, g_cov6, skin=dict(skin, g_extra=g_tp_extra), pose=pose, deposit=deposit, **want)
         return _lbs_returns(ctx, g["vertices"], g["pose"]) + (None, None, g["barys"] if need[9] else None, None, g["scales"],
                                                               g["rotations"], g["barys"] if need[13] else None, None)
 

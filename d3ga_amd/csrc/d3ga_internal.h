@@ -13,6 +13,9 @@ constexpr int kBlock = 256;
 // the library's debug knobs (include/d3ga.h: D3GA_KNOB_*, d3ga_debug_set): value in effect.  No environment is read anywhere.
 int debug_knob(int key);
 
+// deform.hip: the argument rules of the deform backward that runs as the tail of the per-Gaussian raster backward
+int deform_tail_check(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr, const d3ga_cage_deform_route *route);
+
 static inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 // Per-Gaussian state written by the preprocess kernel (structure of arrays, 256-byte aligned sections).

@@ -7,10 +7,11 @@
 // lane-contiguous addresses.  Gaussians are expected sorted by tet id (static during training), so the four
 // corner gathers of neighbouring lanes hit the same cache lines.
 #include "d3ga_internal.h"
+#include "deform_tail.h"
 
 namespace d3ga {
 
-__device__ __forceinline__ V3 load3(const float *p, int i) { return v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
+static_assert(kMergeBlock == kBlock, "the block merge is laid out for the workgroup size");
 
 // 64-lane sum through DPP (see raster_composite.hip); result broadcast from lane 63
 template <int CTRL, int ROW_MASK>
@@ -196,35 +197,7 @@ __global__ __launch_bounds__(kBlock) void lbs_pose_reduce_kernel(
 // ---------------------------------------------------------------------------------------------------------
 // D1-D5
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load_deform_in(int i, const float *__restrict__ tetpoints,
-                                               const int32_t *__restrict__ tetras, const int32_t *__restrict__ tetra_id,
-                                               const float *__restrict__ barys, const float *__restrict__ canon_grad,
-                                               const float *__restrict__ scales, const float *__restrict__ rots,
-                                               const float *__restrict__ delta_barys, int flags, DeformIn &in,
-                                               int4 &vid) {
-    const int t = tetra_id[i];
-    vid = reinterpret_cast<const int4 *>(tetras)[t];
-    in.x0 = load3(tetpoints, vid.x); in.x1 = load3(tetpoints, vid.y);
-    in.x2 = load3(tetpoints, vid.z); in.x3 = load3(tetpoints, vid.w);
-    const float4 b = reinterpret_cast<const float4 *>(barys)[i];
-    in.bary[0] = b.x; in.bary[1] = b.y; in.bary[2] = b.z; in.bary[3] = b.w;
-    if (delta_barys) {                       // canon_barys = barys + delta_bary (models/cage_net.py:213), fused
-        const float4 d = reinterpret_cast<const float4 *>(delta_barys)[i];
-        in.bary[0] += d.x; in.bary[1] += d.y; in.bary[2] += d.z; in.bary[3] += d.w;
-    }
-    // the canonical gradient is a property of the TETRAHEDRON: per Gaussian as the reference stores it (lib/cage.py:329,
-    // 36 B x P streamed per pass), or -- D3GA_DEFORM_GRAD_PER_TET -- one (T,3,3) table read through tetra_id (L2-resident)
-    const size_t gi = (flags & D3GA_DEFORM_GRAD_PER_TET) ? (size_t)t : (size_t)i;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) in.G.m[k] = canon_grad[9 * gi + k];
-    in.s[0] = scales[3 * (size_t)i]; in.s[1] = scales[3 * (size_t)i + 1]; in.s[2] = scales[3 * (size_t)i + 2];
-    if (flags & D3GA_DEFORM_LOG_SCALES) {    // scales = exp(scaling) (models/cage_net.py:214), fused
-        in.s[0] = expf(in.s[0]); in.s[1] = expf(in.s[1]); in.s[2] = expf(in.s[2]);
-    }
-    const float4 q = reinterpret_cast<const float4 *>(rots)[i];
-    in.q[0] = q.x; in.q[1] = q.y; in.q[2] = q.z; in.q[3] = q.w;
-}
-
+// (load_deform_in and DeformMerge: deform_tail.h, which also holds the stores and routes below as functions for raster_pre.hip)
 __global__ __launch_bounds__(kBlock) void cage_deform_fwd_kernel(int P, const float *__restrict__ tetpoints,
                                                                  const int32_t *__restrict__ tetras,
                                                                  const int32_t *__restrict__ tetra_id,
@@ -246,20 +219,6 @@ __global__ __launch_bounds__(kBlock) void cage_deform_fwd_kernel(int P, const fl
     for (int k = 0; k < 6; ++k) cov6[6 * (size_t)i + k] = c[k];
 }
 
-// Block-level merge of the corner gradients (round 4; D3GA_DEFORM_ROUTE_MERGE).  The binding is static, so for every
-// workgroup of 256 consecutive Gaussians the positions of its 1024 (Gaussian, corner) items in vertex-sorted order
-// (item_pos), the segments of equal vertex (seg_ptr / seg_begin) and where each segment's sum goes (partial g = global
-// segment index) are built ONCE (cage_deform.py: merge_plan).  The kernel drops its corner gradients into LDS at those
-// positions, sums every segment in a fixed order (no atomics: bit-reproducible) and writes one partial per (workgroup,
-// vertex) -- with spatially coherent numbering a few hundred per workgroup instead of 1024 corner records; the vertex
-// gather then runs over the partials.
-struct DeformMerge {
-    const uint16_t *item_pos;      // (P,4)  position of item 4 i + c among its workgroup's items sorted by vertex
-    const int32_t *seg_ptr;        // (workgroups + 1)  first global segment of each workgroup
-    const uint16_t *seg_begin;     // (segments)  first position of the segment inside its workgroup
-    float *partials;               // (segments,3)
-};
-
 __global__ __launch_bounds__(kBlock) void cage_deform_bwd_kernel(
     int P, const float *__restrict__ tetpoints, const int32_t *__restrict__ tetras, const int32_t *__restrict__ tetra_id,
     const float *__restrict__ barys, const float *__restrict__ canon_grad, const float *__restrict__ scales,
@@ -280,6 +239,9 @@ __global__ __launch_bounds__(kBlock) void cage_deform_bwd_kernel(
 #pragma unroll
         for (int k = 0; k < 6; ++k) gc[k] = g_cov6[6 * (size_t)i + k];
         deform_bwd(in, gm, gc, o);
+        // (the stores and the two routes written out, not called through deform_tail.h's store_deform_grads / deform_merge_epilogue /
+        // store_corner_records as the fused raster kernel does: through the calls this kernel compiled to other instruction text --
+        // two registers less, another null test and address form -- and it is to stay the kernel it was)
         if (g_barys) reinterpret_cast<float4 *>(g_barys)[i] = make_float4(o.gbary[0], o.gbary[1], o.gbary[2], o.gbary[3]);
         if (g_scales) {
             if (flags & D3GA_DEFORM_LOG_SCALES) {    // d/d(log s) = s * d/ds
@@ -495,10 +457,10 @@ extern "C" int d3ga_cage_deform_fwd(const d3ga_cage_deform_in *in, float *means3
 }
 
 // One validation, one launch of cage_deform_bwd_kernel, then the vertex gather the route asks for (with the skinning backward in
-// it when `skin` is given) and the by-joint reduction of `pose`.
-extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr,
-                                    const d3ga_cage_deform_route *route, const d3ga_cage_deform_skin *skin,
-                                    const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream) {
+// it when `skin` is given) and the by-joint reduction of `pose`.  tail_only (d3ga_cage_deform_bwd_tail): the route's records are
+// already filled -- by the per-Gaussian raster backward that ran the deform backward as its tail -- and the kernel is not launched.
+static int cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr, const d3ga_cage_deform_route *route,
+                           const d3ga_cage_deform_skin *skin, const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream, bool tail_only) {
     if (!in || !gr) return D3GA_E_NULL;
     const int P = in->P, V = in->V;
     const bool merge = route && route->kind == D3GA_DEFORM_ROUTE_MERGE, corners = route && route->kind == D3GA_DEFORM_ROUTE_CORNERS;
@@ -525,6 +487,8 @@ extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_ca
         // empty tensor
         if (route->n_segments != 0) return D3GA_E_SIZE;
         if (!route->vert_start) return D3GA_E_NULL;
+    } else if (tail_only) {
+        if (route && (!route->vert_start || !route->vert_items || !route->records)) return D3GA_E_NULL;
     } else {
         D3GA_TRY(deform_in_check(in));
         if (!gr->g_means || !gr->g_cov6 || (route && (!route->vert_start || !route->vert_items || !route->records)) ||
@@ -553,6 +517,32 @@ extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_ca
                            (const float *)route->records, gv);
     D3GA_TRY(check_launch(s, 0));
     return pose ? pose_reduce(V, skin->K, skin->joint_mats, skin->skin_idx, skin->skin_w, skin->Rh, gv, pose, s) : D3GA_OK;
+}
+
+extern "C" int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr,
+                                    const d3ga_cage_deform_route *route, const d3ga_cage_deform_skin *skin,
+                                    const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream) {
+    return cage_deform_bwd(in, gr, route, skin, pose, stream, false);
+}
+
+extern "C" int d3ga_cage_deform_bwd_tail(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr,
+                                         const d3ga_cage_deform_route *route, const d3ga_cage_deform_skin *skin,
+                                         const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream) {
+    return cage_deform_bwd(in, gr, route, skin, pose, stream, true);
+}
+
+// What the fused raster backward checks of its deform arguments before it launches (d3ga_raster_preprocess_bwd_deform): the
+// rules of d3ga_cage_deform_bwd for the kernel's own inputs, outputs and route.
+int d3ga::deform_tail_check(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *gr, const d3ga_cage_deform_route *route) {
+    if (!in || !gr) return D3GA_E_NULL;
+    const bool merge = route && route->kind == D3GA_DEFORM_ROUTE_MERGE, corners = route && route->kind == D3GA_DEFORM_ROUTE_CORNERS;
+    if (in->P < 0 || in->V < 0 || (merge && route->n_segments < 0)) return D3GA_E_SIZE;
+    if ((in->flags & ~(D3GA_DEFORM_LOG_SCALES | D3GA_DEFORM_GRAD_PER_TET)) || (route && !merge && !corners)) return D3GA_E_CONFIG;
+    if (in->P == 0) return D3GA_OK;
+    D3GA_TRY(deform_in_check(in));
+    if ((route && !route->records) || (merge && (!route->item_pos || !route->seg_ptr || !route->seg_begin))) return D3GA_E_NULL;
+    if (merge && ((uintptr_t)route->item_pos & 7)) return D3GA_E_CONFIG;  // read 8 bytes per Gaussian
+    return D3GA_OK;
 }
 
 extern "C" int d3ga_fem_energy_fwd(int T, const float *tetpoints, const int32_t *tetras, const float *Dn_inv,

@@ -184,3 +184,53 @@ extern "C" int d3ga_raster_backward_l1(const d3ga_raster_params *prm, const floa
                                       campos, geom, acc, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh, dL_dcolors,
                                       dL_dcov3D, dL_dscales, dL_drots, stream);
 }
+
+// The two chained backwards with the deform backward as the tail of the per-Gaussian kernel (d3ga_raster_preprocess_bwd_deform):
+// the clear and the compositing backward as above, then the fused kernel.  Configurations it does not cover are refused before
+// anything is launched.
+static int deform_chain_check(const d3ga_raster_params *prm, const float *scales, const float *rotations, const float *cov3D_precomp,
+                              const d3ga_cage_deform_in *din, const d3ga_cage_deform_grads *dgr, const d3ga_cage_deform_route *route) {
+    if (!prm) return D3GA_E_NULL;
+    D3GA_TRY(deform_tail_check(din, dgr, route));
+    if (n_views_of(prm) > 1 || is_windowed(prm) || scales || rotations || din->P != prm->P) return D3GA_E_CONFIG;
+    if (prm->P > 0 && !cov3D_precomp) return D3GA_E_NULL;
+    return D3GA_OK;
+}
+
+extern "C" int d3ga_raster_backward_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs,
+                                           const float *scales, const float *rotations, const float *cov3D_precomp,
+                                           const float *viewmatrix, const float *projmatrix, const float *campos,
+                                           const float *bg, const void *geom, const void *binning, int64_t d_capacity,
+                                           const void *img, const float *dL_dpix, float *acc, float *dL_dmeans3D,
+                                           float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh, float *dL_dcolors,
+                                           float *dL_dcov3D, float *dL_dscales, float *dL_drots, const d3ga_cage_deform_in *din,
+                                           const d3ga_cage_deform_grads *dgr, const d3ga_cage_deform_route *route,
+                                           d3ga_stream_t stream) {
+    D3GA_TRY(deform_chain_check(prm, scales, rotations, cov3D_precomp, din, dgr, route));
+    if (prm->P > 0 && acc && !prm->acc_self_clearing)
+        D3GA_HIP(zero_async(acc, sizeof(float) * D3GA_ACC_STRIDE * (size_t)prm->P, (hipStream_t)stream));
+    D3GA_TRY(d3ga_raster_composite_bwd(prm, bg, geom, binning, d_capacity, img, dL_dpix, acc, stream));
+    return d3ga_raster_preprocess_bwd_deform(prm, means3D, shs, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, geom,
+                                             acc, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales,
+                                             dL_drots, din, dgr, route, stream);
+}
+
+extern "C" int d3ga_raster_backward_l1_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs,
+                                              const float *scales, const float *rotations, const float *cov3D_precomp,
+                                              const float *viewmatrix, const float *projmatrix, const float *campos,
+                                              const float *bg, const void *geom, const void *binning, int64_t d_capacity,
+                                              const void *img, const float *image, const float *target, const void *target_cell,
+                                              const float *g_loss, const float *dL_dpix, float *acc, float *dL_dmeans3D,
+                                              float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh, float *dL_dcolors,
+                                              float *dL_dcov3D, float *dL_dscales, float *dL_drots, const d3ga_cage_deform_in *din,
+                                              const d3ga_cage_deform_grads *dgr, const d3ga_cage_deform_route *route,
+                                              d3ga_stream_t stream) {
+    D3GA_TRY(deform_chain_check(prm, scales, rotations, cov3D_precomp, din, dgr, route));
+    if (prm->P > 0 && acc && !prm->acc_self_clearing)
+        D3GA_HIP(zero_async(acc, sizeof(float) * D3GA_ACC_STRIDE * (size_t)prm->P, (hipStream_t)stream));
+    D3GA_TRY(d3ga_raster_composite_bwd_l1(prm, bg, geom, binning, d_capacity, img, image, target, target_cell, g_loss, dL_dpix,
+                                          acc, stream));
+    return d3ga_raster_preprocess_bwd_deform(prm, means3D, shs, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, geom,
+                                             acc, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, dL_dscales,
+                                             dL_drots, din, dgr, route, stream);
+}

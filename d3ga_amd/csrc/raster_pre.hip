@@ -7,8 +7,11 @@
 // Gaussian: fwd 88 + 12 M).  The wide (P,M,3) SH arrays go through per-wavefront LDS slabs so that
 // global accesses are 16 B per lane and lane-contiguous; the camera matrices are wave-uniform and come through the
 // scalar cache.  No MFMA.
+#include <type_traits>
+
 #include "composite_common.h"
 #include "raster_pre_body.h"
+#include "deform_tail.h"
 
 namespace d3ga {
 
@@ -608,7 +611,36 @@ __device__ __forceinline__ ViewRecs view_recs(const GeomBuf &g, const float *acc
                     g.dcol_stride};
 }
 
-template <bool WIN>      // WIN: windowed camera slot -- the view's raster size from its camera row
+// What preprocess_bwd_kernel<., true> takes behind its own arguments: the deform backward's inputs and outputs (d3ga.h:
+// d3ga_cage_deform_in / _grads / _route, as cage_deform_bwd_kernel takes them).
+template <bool GEO>      // GEO: dL/dmean and dL/dcov are written as well (both arrays given)
+struct DeformTailT {
+    static constexpr bool kGeo = GEO;
+    const float *tetpoints;
+    const int32_t *tetras, *tetra_id;
+    const float *barys, *canon_grad, *scales, *rots, *delta_barys;
+    int flags;
+    float *g_barys, *g_scales, *g_rots, *corner_grads;
+    DeformMerge mg;
+};
+using DeformTail = DeformTailT<false>;
+using DeformTailGeo = DeformTailT<true>;
+static_assert(kMergeBlock == kBlock, "the block merge is laid out for the workgroup size");
+static_assert(sizeof(float) * 3 * kMergeItems <= kShLdsBytes, "the merge planes take the place of the SH slabs");
+template <class T>
+__device__ __forceinline__ const T &first_of(const T &t) { return t; }
+
+// DEFORM (single view, precomputed covariance produced by the cage deformation; d3ga_raster_preprocess_bwd_deform): the thread
+// keeps dL/dmean and dL/dcov of its Gaussian in registers and runs the deform backward on them -- what cage_deform_bwd_kernel
+// would read back from memory in the next launch -- from the DeformTail `tail` behind the arguments.  The two arrays are written
+// only where their pointers are given: both or neither, and given (DeformTailT<true>, an instantiation of its own) the thread
+// writes them through the plain kernel's own calls and goes on from the values written -- every output is then the two-kernel
+// path's bit for bit, where the register variant differs in the last bit of dL/dmean (the compiler contracts its multiply-adds
+// differently; docs/LOG.md).  Source order: the dependent chain tetra_id -> tetras -> tetpoints is issued with the record
+// loads; the streaming deform inputs are loaded behind the SH phase, so the register peak is the larger of the two phases;
+// the merge planes reuse the SH slabs' LDS once every wavefront has read its slab (one workgroup barrier more than the merge's
+// own).  Every thread reaches both barriers: i >= P and culled Gaussians go through with zero gradients.
+template <bool WIN, bool DEFORM = false, class... TAIL>      // WIN: windowed camera slot -- the view's raster size from its camera row
 __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ viewmatrix,
@@ -616,7 +648,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
     const float *__restrict__ acc, float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D,
     float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors,
     float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscales, float *__restrict__ dL_drots,
-    const float *__restrict__ cov3D_precomp, int accum /* views > 0 of a batch: add to the gradients of inputs the views share (raster_pre_body.h) */) {
+    const float *__restrict__ cov3D_precomp, int accum /* views > 0 of a batch: add to the gradients of inputs the views share (raster_pre_body.h) */,
+    TAIL... tail) {
     const ViewCam cam = view_cam(prm, viewmatrix, projmatrix, campos, WIN);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_sh = reinterpret_cast<float *>(smem);
@@ -643,6 +676,16 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
         clampmask = geom.clamped[i];
         act_opacity = geom.conic_o[i].w;
     }
+    // (DEFORM) the tail's dependent chain, three round trips deep, in flight with the records: this Gaussian's tet and its corners
+    DeformIn din;
+    int tet = 0;
+    if constexpr (DEFORM) {
+        const auto &dt = first_of(tail...);
+        din.x0 = din.x1 = din.x2 = din.x3 = v3(0.f, 0.f, 0.f);
+        int4 vid;
+        if (i < prm.P) tet = load_deform_corners(i, dt.tetpoints, dt.tetras, dt.tetra_id, din, vid);
+    }
+    float g9[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (DEFORM) dL/dmean, dL/dcov of this Gaussian
     // Round 5: the forward left d(colour)/d(direction) of every Gaussian (geom.dcol, 36 bytes) when it staged the coefficients and
     // a backward was to follow: the coefficients themselves (192 bytes per Gaussian) are then not read here at all -- the slab
     // only collects the gradient rows for the coalesced store.
@@ -665,7 +708,37 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
         }
         // two call sites so that each inlined copy sees ONE address space (LDS row vs global row, never flat);
         // staged: the gradient row overwrites the coefficient row in place
-        if (staged)
+        if constexpr (DEFORM) {
+            if constexpr (std::decay_t<decltype(first_of(tail...))>::kGeo) {
+                // the two arrays are wanted as well: written as the plain kernel writes them, by the same calls, and taken from there
+                if (staged)
+                    preprocess_bwd_one(prm, cam, i, visible, means3D, slab + lane * kShRow, scales, rotations, c6, clampmask, ar.a,
+                                       dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh ? slab + lane * kShRow : nullptr, dL_dcolors,
+                                       dL_dcov3D, dL_dscales, dL_drots, act_opacity, have_j, jd, accum);
+                else
+                    preprocess_bwd_one(prm, cam, i, visible, means3D, shs ? shs + (size_t)M3 * i : nullptr, scales, rotations, c6,
+                                       clampmask, ar.a, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh ? dL_dsh + (size_t)M3 * i : nullptr,
+                                       dL_dcolors, dL_dcov3D, dL_dscales, dL_drots, act_opacity, false, ShColJ(), accum);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) g9[k] = dL_dmeans3D[3 * (size_t)i + k];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) g9[3 + k] = dL_dcov3D[6 * (size_t)i + k];
+            } else {
+                // preprocess_bwd_one itself, as Gaussian 0 of arrays that begin at this Gaussian's rows, with g9 as its dL/dmean
+                // and dL/dcov arrays: the nine values stay in registers
+                const size_t u = (size_t)i;
+                float *const m2d = dL_dmeans2D ? dL_dmeans2D + 3 * u : nullptr, *const dop = dL_dopacity ? dL_dopacity + u : nullptr;
+                float *const dcl = dL_dcolors ? dL_dcolors + 3 * u : nullptr;
+                if (staged)
+                    preprocess_bwd_one(prm, cam, 0, visible, means3D + 3 * u, slab + lane * kShRow, nullptr, nullptr, c6, clampmask, ar.a,
+                                       g9, m2d, dop, dL_dsh ? slab + lane * kShRow : nullptr, dcl, g9 + 3, nullptr, nullptr, act_opacity,
+                                       have_j, jd, 0);
+                else
+                    preprocess_bwd_one(prm, cam, 0, visible, means3D + 3 * u, shs ? shs + (size_t)M3 * i : nullptr, nullptr, nullptr, c6,
+                                       clampmask, ar.a, g9, m2d, dop, dL_dsh ? dL_dsh + (size_t)M3 * i : nullptr, dcl, g9 + 3, nullptr,
+                                       nullptr, act_opacity, false, ShColJ(), 0);
+            }
+        } else if (staged)
             preprocess_bwd_one(prm, cam, i, visible, means3D, slab + lane * kShRow, scales, rotations, c6, clampmask, ar.a, dL_dmeans3D,
                                dL_dmeans2D, dL_dopacity, dL_dsh ? slab + lane * kShRow : nullptr, dL_dcolors, dL_dcov3D, dL_dscales,
                                dL_drots, act_opacity, have_j, jd, accum);
@@ -678,6 +751,21 @@ __global__ __launch_bounds__(kBlock) void preprocess_bwd_kernel(
         __builtin_amdgcn_wave_barrier();          // the slab is private to the wavefront: program order suffices
         if (full48) sh_rows48_store<64>(slab, dL_dsh + (size_t)48 * row0, lane);
         else if (rows > 0) sh_slab_store(slab, dL_dsh + (size_t)M3 * row0, rows, M3, lane);
+    }
+    if constexpr (DEFORM) {
+        const auto &dt = first_of(tail...);
+        DeformGrad o;
+        if (i < prm.P) {
+            load_deform_streams(i, tet, dt.barys, dt.canon_grad, dt.scales, dt.rots, dt.delta_barys, dt.flags, din);
+            deform_bwd(din, g9, g9 + 3, o);
+            store_deform_grads(i, dt.flags, din, o, dt.g_barys, dt.g_scales, dt.g_rots);
+        }
+        if (dt.mg.item_pos) {
+            __syncthreads();                      // every wavefront has read its slab: the merge planes take the slabs' place
+            deform_merge_epilogue(*reinterpret_cast<float (*)[3][kMergeItems]>(smem), dt.mg, prm.P, i, i < prm.P, o);
+        } else if (dt.corner_grads && i < prm.P) {
+            store_corner_records(dt.corner_grads, i, o);
+        }
     }
 }
 
@@ -911,6 +999,46 @@ extern "C" int d3ga_raster_recolor(const d3ga_raster_params *prm, const float *m
     hipLaunchKernelGGL(leaves_dcol(prm, shs) ? recolor_kernel<true> : recolor_kernel<false>, dim3((prm->P + kBlock - 1) / kBlock),
                        dim3(kBlock), lds_bytes(staged(prm, shs), kShHalfLdsBytes), s, *prm, means3D, shs, colors_precomp, campos, src, dst);
     return check_launch(s, prm->debug & 0xff);
+}
+
+// R6 with the deform backward as its tail (preprocess_bwd_kernel<false, true>): one view on the full raster, a precomputed
+// covariance -- the deform's output.  dL_dmeans3D / dL_dcov3D may be null (not written).  The vertex gather and the skinning / pose
+// tails are d3ga_cage_deform_bwd_tail's, on the records this leaves.
+extern "C" int d3ga_raster_preprocess_bwd_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs,
+                                                 const float *scales, const float *rotations, const float *cov3D_precomp,
+                                                 const float *viewmatrix, const float *projmatrix, const float *campos,
+                                                 const void *geom, const float *acc, float *dL_dmeans3D, float *dL_dmeans2D,
+                                                 float *dL_dopacity, float *dL_dsh, float *dL_dcolors, float *dL_dcov3D,
+                                                 float *dL_dscales, float *dL_drots, const d3ga_cage_deform_in *din,
+                                                 const d3ga_cage_deform_grads *dgr, const d3ga_cage_deform_route *route,
+                                                 d3ga_stream_t stream) {
+    D3GA_TRY(validate(prm));
+    D3GA_TRY(deform_tail_check(din, dgr, route));
+    if (n_views_of(prm) > 1 || is_windowed(prm) || scales || rotations || dL_dscales || dL_drots || din->P != prm->P) return D3GA_E_CONFIG;
+    if ((dL_dmeans3D != nullptr) != (dL_dcov3D != nullptr)) return D3GA_E_CONFIG;      // both arrays or neither
+    if (prm->P == 0) return D3GA_OK;
+    if (!means3D || !viewmatrix || !projmatrix || !campos || !geom || !acc || !cov3D_precomp) return D3GA_E_NULL;
+    if (dL_dsh && !shs) return D3GA_E_NULL;
+    if (shs && !dL_dsh && !dL_dcolors) return D3GA_E_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const GeomBuf g = carve_geom(const_cast<void *>(geom), prm->P);
+    const bool merge = route && route->kind == D3GA_DEFORM_ROUTE_MERGE;
+    // the SH slabs, and in their place the merge planes
+    const size_t lds = lds_bytes(staged(prm, shs), kShLdsBytes, merge ? sizeof(float) * 3 * kMergeItems : 0);
+    const ViewCams<1> c = view_cams<1>(viewmatrix, projmatrix, campos, cam_stride(prm), 0, 1);
+    auto launch = [&](auto dt) {
+        using Tail = decltype(dt);
+        dt = Tail{din->tetpoints, din->tetras, din->tetra_id, din->barys, din->canon_grad, din->scales, din->rots, din->delta_barys,
+                  (int)din->flags, dgr->g_barys, dgr->g_scales, dgr->g_rots, (route && !merge) ? route->records : nullptr,
+                  merge ? DeformMerge{route->item_pos, route->seg_ptr, route->seg_begin, route->records}
+                        : DeformMerge{nullptr, nullptr, nullptr, nullptr}};
+        hipLaunchKernelGGL((preprocess_bwd_kernel<false, true, Tail>), dim3((prm->P + kBlock - 1) / kBlock), dim3(kBlock), lds, s, *prm,
+                           means3D, shs, (const float *)nullptr, (const float *)nullptr, c.vm[0], c.pm[0], c.cp[0], g, acc, dL_dmeans3D,
+                           dL_dmeans2D, dL_dopacity, dL_dsh, dL_dcolors, dL_dcov3D, (float *)nullptr, (float *)nullptr, cov3D_precomp, 0, dt);
+    };
+    if (dL_dmeans3D) launch(DeformTailGeo{});
+    else launch(DeformTail{});
+    return check_launch(s, prm->debug);
 }
 
 extern "C" int d3ga_raster_preprocess_bwd(const d3ga_raster_params *prm, const float *means3D, const float *shs,

@@ -316,21 +316,22 @@ def _launch_forward(prm, cap, windowed, gauss, cam, bg, color, radii, invdepth, 
     return geom, binning, img
 
 
-def _grad_buffers(prm, has_sh, from_sr, dev, exchanged, geo, opac, col, lead):
+def _grad_buffers(prm, has_sh, from_sr, dev, exchanged, geo, opac, col, lead, geometry=True):
     """The gradients the per-Gaussian backward writes.  Plain: dL/dmeans3D, dL/dcov3D | dL/dscales, dL/drots of shape
     (*geo, .), dL/dopacity `opac`, dL/dcolour `col` (None: no such buffer).  `exchanged` (view-sharded training, dist.py:
     ViewShardedGrads): every gradient that leaves the op is summed over the ranks at this cut -- ONE planar buffer `flat` for
     the all-reduce and, on the SH path, the (P + 1, 3) factor of every view's rank-1 SH gradient (row P: the view's camera
     position) for ONE all-gather of (*lead, P + 1, 3) per rank.
+    geometry=False (render fusion, never exchanged): no dL/dmeans3D and dL/dcov3D buffers -- the kernel keeps them in registers.
     -> (g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm); cut: None, or what `_exchange_gradients` moves --
     (flat, factor, rasterizer input name -> its gradient, a view of `flat`)."""
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     P, cut = prm.P, None
     if not exchanged:
-        g_means3D, g_opac = new(*geo, 3), new(*opac)
+        g_means3D, g_opac = new(*geo, 3) if geometry else None, new(*opac)
         g_sh = new(P, prm.M, 3) if has_sh else None
         g_col = None if col is None else new(*col)
-        g_cov = None if from_sr else new(*geo, 6)
+        g_cov = None if (from_sr or not geometry) else new(*geo, 6)
         g_scales = new(*geo, 3) if from_sr else None
         g_rots = new(*geo, 4) if from_sr else None
     else:
@@ -357,10 +358,12 @@ def _grad_buffers(prm, has_sh, from_sr, dev, exchanged, geo, opac, col, lead):
     return g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm
 
 
-def _launch_backward(prm, cap, gauss, cam, bg, geom, binning, img, grad_color, grads, pair=None, g_invd=None, l1=None):
+def _launch_backward(prm, cap, gauss, cam, bg, geom, binning, img, grad_color, grads, pair=None, g_invd=None, l1=None, deform=None):
     """composite_bwd -> preprocess_bwd.  gauss: (means3D, sh, scales, rotations, cov3D_precomp); grads: (g_means3D, g_means2D,
     g_opac, g_sh, g_col, g_cov, g_scales, g_rots); pair = (colors2, bg2, grad_color2); g_invd: the gradient of the inverse-depth
-    image; l1 = (image, target, target cell, g_loss): the gradient of the fused L1 loss, formed per pixel inside the kernel."""
+    image; l1 = (image, target, target cell, g_loss): the gradient of the fused L1 loss, formed per pixel inside the kernel.  deform = the
+    (struct d3ga_cage_deform_in, _grads, _route | None) of the deform node that made means3D and the covariance (single view): the
+    per-Gaussian kernel runs that node's backward as its tail (the *_deform entries); g_means3D and g_cov may then be None."""
     means3D, sh, scales, rotations, cov3Ds_precomp = gauss
     view, proj, campos = cam
     g_means3D, g_means2D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots = grads
@@ -371,6 +374,8 @@ def _launch_backward(prm, cap, gauss, cam, bg, geom, binning, img, grad_color, g
     if self_clearing != bool(prm.acc_self_clearing):
         prm = _prm_variant(prm, acc_self_clearing=int(self_clearing))
     L = _lib.lib()
+    tail = () if deform is None else tuple(None if x is None else ctypes.byref(x) for x in deform)
+    sfx = "" if deform is None else "_deform"
     if stage_timer.enabled or k > 1 or pair is not None or g_invd is not None:
         st, pp = stream_handle(), ctypes.byref(prm)
         if not self_clearing:
@@ -393,24 +398,24 @@ def _launch_backward(prm, cap, gauss, cam, bg, geom, binning, img, grad_color, g
             stage_timer.stage("composite_bwd", lambda: check(L.d3ga_raster_composite_bwd(
                 pp, dptr(bg), dptr(geom), dptr(binning), cap, dptr(img), dptr(grad_color), dptr(acc), st),
                 "d3ga_raster_composite_bwd"))
-        stage_timer.stage("preprocess_bwd", lambda: check(L.d3ga_raster_preprocess_bwd(
+        stage_timer.stage("preprocess_bwd", lambda: check(getattr(L, "d3ga_raster_preprocess_bwd" + sfx)(
             pp, dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp), dptr(view), dptr(proj),
             dptr(campos), dptr(geom), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh),
-            dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), st), "d3ga_raster_preprocess_bwd"))
+            dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), *tail, st), "d3ga_raster_preprocess_bwd" + sfx))
     elif l1 is not None:
         image, target, cell, g_loss = l1
-        check(L.d3ga_raster_backward_l1(
+        check(getattr(L, "d3ga_raster_backward_l1" + sfx)(
             ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
             dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), cap, dptr(img),
             dptr(image), dptr(target), dptr(cell), dptr(g_loss), dptr(grad_color), dptr(acc), dptr(g_means3D),
-            dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots),
-            stream_handle()), "d3ga_raster_backward_l1")
+            dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col), dptr(g_cov), dptr(g_scales), dptr(g_rots), *tail,
+            stream_handle()), "d3ga_raster_backward_l1" + sfx)
     else:
-        check(L.d3ga_raster_backward(
+        check(getattr(L, "d3ga_raster_backward" + sfx)(
             ctypes.byref(prm), dptr(means3D), dptr(sh), dptr(scales), dptr(rotations), dptr(cov3Ds_precomp),
             dptr(view), dptr(proj), dptr(campos), dptr(bg), dptr(geom), dptr(binning), cap, dptr(img),
             dptr(grad_color), dptr(acc), dptr(g_means3D), dptr(g_means2D), dptr(g_opac), dptr(g_sh), dptr(g_col),
-            dptr(g_cov), dptr(g_scales), dptr(g_rots), stream_handle()), "d3ga_raster_backward")
+            dptr(g_cov), dptr(g_scales), dptr(g_rots), *tail, stream_handle()), "d3ga_raster_backward" + sfx)
 
 
 def _sh_grad_from_factors(gathered, P, M, sh_degree, means3D, scale):
@@ -527,7 +532,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, grad_sync=None, colors2=None, bg2=None, opacity_activation=None, l1_target=None,
-                want_invdepth=True):
+                want_invdepth=True, deform_node=None):
         s = raster_settings
         require_cuda(means3D)
         dev = means3D.device
@@ -608,6 +613,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         _verify_sync_inputs(ctx.grad_sync, means3D, opacities, colors_precomp, sh, cov3Ds_precomp, scales, rotations)
         ctx.dual = dual
         ctx.l1 = l1_target is not None and P > 0 and not dual
+        # render fusion (cage_deform.claim_for_render): the deform node that made means3D and the covariance runs the per-Gaussian
+        # part of its backward as the tail of this operator's.  Single view on the full raster, gradients not exchanged.
+        if deform_node is not None and (windowed or ctx.grad_sync is not None or P == 0 or cov3Ds_precomp is None or fwd_only):
+            from .cage_deform import release_claim
+            release_claim(*deform_node)
+            deform_node = None
+        ctx.deform_node = deform_node                    # (node, the claim's token) | None
         if l1_target is not None and l1 is None:
             l1_mean_forward(color, l1_t, l1_cell, loss, dev)
         _last_img[dev.index] = (img, W, H, geom, P)
@@ -647,50 +659,68 @@ class _RasterizeGaussians(torch.autograd.Function):
         if dual:
             grad_color2 = (torch.zeros_like(grad_color) if grad_color2 is None else _f32(grad_color2, dev))
         has_sh, from_sr, sync = sh is not None, cov3Ds_precomp is None, ctx.grad_sync
+        deform = deposit = node = None
+        if ctx.deform_node is not None:
+            from .cage_deform import deposit_on, fused_tail_structs, holds_claim
+            # (a later render of the package may have revoked the claim; a retain_grad() or hook since the render ends it here)
+            node = ctx.deform_node[0] if holds_claim(*ctx.deform_node) else None
+        # a held claim: dL/dmeans3D and dL/dcov stay in the kernel's registers (no buffers), the node's share is deposited on it
         g_means3D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots, cut, prm = _grad_buffers(
-            prm, has_sh, from_sr, dev, exchanged=sync is not None, geo=(P,), opac=(P, 1), col=None if has_sh else (P, 3), lead=())
+            prm, has_sh, from_sr, dev, exchanged=sync is not None, geo=(P,), opac=(P, 1), col=None if has_sh else (P, 3), lead=(),
+            geometry=node is None)
         g_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        if node is not None:
+            *deform, deposit = fused_tail_structs(node)
         _launch_backward(prm, ctx.cap, (means3D, sh, scales, rotations, cov3Ds_precomp), (view, proj, campos), bg, geom, binning, img,
                          grad_color, (g_means3D, g_means2D, g_opac, g_sh, g_col, g_cov, g_scales, g_rots),
                          (colors2, bg2, grad_color2) if dual else None, g_invd,
-                         (image, l1_t, l1_cell, g_loss) if g_loss is not None else None)
+                         (image, l1_t, l1_cell, g_loss) if g_loss is not None else None, deform)
+        if deposit is not None:
+            deposit_on(node, deposit)
         if sync is not None:
             parked, g_sh = _exchange_gradients(sync, prm, cut, campos, means3D)
             if parked:
-                return (None, g_means2D if ctx.has_means2D else None) + (None,) * 13
+                return (None, g_means2D if ctx.has_means2D else None) + (None,) * 14
             if has_sh:
                 g_col = None
         return (g_means3D, g_means2D if ctx.has_means2D else None, g_sh, g_col, g_opac, g_scales, g_rots, g_cov, None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 _ACTIVATIONS = {None: 0, "none": 0, "sigmoid": 1}       # D3GA_OPACITY_SIGMOID
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, grad_sync=None, opacity_activation=None, want_invdepth=True):
+                        raster_settings, grad_sync=None, opacity_activation=None, want_invdepth=True, deform_node=None):
     """opacity_activation="sigmoid" (extension over upstream): `opacities` holds the raw logits and the sigmoid of
-    models/cage_net.py:247 runs inside the per-Gaussian kernels, forward and backward."""
+    models/cage_net.py:247 runs inside the per-Gaussian kernels, forward and backward.
+    deform_node (all three operators; renderer.render passes it): (node, token) -- the deform node claimed for this render
+    (cage_deform.claim_for_render) -- its backward's per-Gaussian part then runs as the tail of this operator's, and means3D and
+    cov3Ds_precomp receive no gradient of their own."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, grad_sync, None, None, opacity_activation, None, want_invdepth)
+                                     cov3Ds_precomp, raster_settings, grad_sync, None, None, opacity_activation, None, want_invdepth,
+                                     deform_node)
 
 
 def rasterize_gaussians_l1(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                           raster_settings, target, grad_sync=None, opacity_activation=None, want_invdepth=True):
+                           raster_settings, target, grad_sync=None, opacity_activation=None, want_invdepth=True, deform_node=None):
     """The render AND its L1 image loss (utils/loss_utils.py:29: mean |image - target|) from one operator (extension):
     returns (color, radii, invdepth, loss).  The gradient of `loss` is formed per pixel inside the compositing backward,
     so no (3,H,W) gradient image is written or read (one full-image kernel and 50 MB of traffic less per frame at 1080p);
     `color` stays differentiable as usual and both gradients add.  `target`: (3,H,W) tensor or a `graph.TensorSlot`."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, grad_sync, None, None, opacity_activation, target, want_invdepth)
+                                     cov3Ds_precomp, raster_settings, grad_sync, None, None, opacity_activation, target, want_invdepth,
+                                     deform_node)
 
 
 def rasterize_gaussians_pair(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, colors2, bg2, grad_sync=None, opacity_activation=None, want_invdepth=True):
+                             raster_settings, colors2, bg2, grad_sync=None, opacity_activation=None, want_invdepth=True,
+                             deform_node=None):
     """Two images from ONE pass: the usual one and `colors2` (P,3; constants, no gradient) blended with the same alphas over
     `bg2`.  Returns (color, radii, invdepth, color2).  Gradients of both images reach the geometry and the opacities."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, grad_sync, colors2, bg2, opacity_activation, None, want_invdepth)
+                                     cov3Ds_precomp, raster_settings, grad_sync, colors2, bg2, opacity_activation, None, want_invdepth,
+                                     deform_node)
 
 
 class GaussianRasterizer(nn.Module):

@@ -188,6 +188,13 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
     # screen-space points: a zero tensor whose .grad receives dL/d(mean2D) (renderer.py:122-128).  A fresh leaf over a
     # cached block of zeros: no fill kernel per render (the rasterizer never reads or writes its values)
     means2D = _zero_leaf(means3D)
+    # render fusion: when means3D and the covariance are the outputs of one cage-deform node, that node's per-Gaussian backward
+    # runs inside the rasterizer's (cage_deform.claim_for_render states the conditions; one render per node and forward pass)
+    node = None
+    if grad_sync is None and not windowed and scales is None and rotations is None:
+        from .cage_deform import claim_for_render
+        node = claim_for_render(means3D, cov3D_precomp)
+        node = node if node[0] is not None else None
     try:
         means2D.retain_grad()
     except Exception:
@@ -196,13 +203,14 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
     if _pair is not None:
         img, _radii, _invd, img2 = rasterize_gaussians_pair(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                             cov3D_precomp, settings, _pair[0], _pair[1], grad_sync, act,
-                                                            want_invdepth=False)
+                                                            want_invdepth=False, deform_node=node)
         if crop is None:
             return {"render": img, "render2": img2}
         return {"render": paste(img, crop), "render2": paste(img2, crop)}
     if _l1 is not None:
         img, _radii, _invd, loss = rasterize_gaussians_l1(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                          cov3D_precomp, settings, _l1, grad_sync, act, want_invdepth=False)
+                                                          cov3D_precomp, settings, _l1, grad_sync, act, want_invdepth=False,
+                                                          deform_node=node)
         return {"render": img, "l1": loss}
     # the operator behind upstream's `GaussianRasterizer(raster_settings)(...)` module call (renderer.py:130-141), without
     # building an nn.Module per render: its constructor and attribute writes cost ~25 us of host time per call, a sixth of an
@@ -210,7 +218,7 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
     if measure_time:
         torch.cuda.synchronize()
     rendered = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings,
-                                   grad_sync, act, want_invdepth=False)[0]     # only [0] of the rasterizer's outputs is used here (renderer.py:141)
+                                   grad_sync, act, want_invdepth=False, deform_node=node)[0]     # only [0] of the rasterizer's outputs is used here (renderer.py:141)
     if measure_time:
         torch.cuda.synchronize()
     return {"render": rendered if crop is None else paste(rendered, crop)}

@@ -186,6 +186,13 @@ typedef struct d3ga_cage_deform_skin {
 int d3ga_cage_deform_fwd(const d3ga_cage_deform_in *in, float *means3D, float *cov6, d3ga_stream_t stream);
 int d3ga_cage_deform_bwd(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *grads, const d3ga_cage_deform_route *route,
                          const d3ga_cage_deform_skin *skin, const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream);
+/* The tails of d3ga_cage_deform_bwd alone -- the vertex gather the route asks for, with the skinning backward in it when `skin`
+ * is given, and the by-joint reduction of `pose` -- on records that are ALREADY filled: by d3ga_raster_preprocess_bwd_deform (and
+ * the two chained backwards built on it), which runs the per-Gaussian part of this backward inside the rasterizer's.  Same
+ * arguments and status codes as d3ga_cage_deform_bwd; in->P, in->V and the route, skin and pose are read, grads->g_tetpoints is
+ * written as there, and no other pointer of `in` / `grads` is looked at. */
+int d3ga_cage_deform_bwd_tail(const d3ga_cage_deform_in *in, const d3ga_cage_deform_grads *grads, const d3ga_cage_deform_route *route,
+                              const d3ga_cage_deform_skin *skin, const d3ga_lbs_pose_grad *pose, d3ga_stream_t stream);
 
 /* D6  FEM regulariser (lib/cage.py:349-361): per-tet energy 0.5(det F-1)^2 + 0.5(|F|_F^2-3), F = Ds Dn^-1.
  *   fwd: energy (T).  bwd: g_energy (T) -> g_tetpoints (V,3) [zeroed by the call]. */
@@ -533,6 +540,45 @@ int d3ga_raster_backward(const d3ga_raster_params *prm, const float *means3D, co
                          float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh,
                          float *dL_dcolors, float *dL_dcov3D, float *dL_dscales, float *dL_drots,
                          d3ga_stream_t stream);
+
+/* R6 with the per-Gaussian part of the cage deformation's backward as its TAIL, for a render whose means3D and cov3D_precomp are
+ * the outputs of d3ga_cage_deform_fwd (models/cage_net.py:213-230 feeding the renderer): the thread of Gaussian i keeps dL/dmean
+ * and dL/dcov in registers and runs the deform backward on them, instead of writing 36 B that d3ga_cage_deform_bwd reads back in
+ * the next launch.  Arguments of the parent entry, then `deform` (the inputs d3ga_cage_deform_fwd was given; deform->P == prm->P),
+ * `dgrads` (g_barys / g_scales / g_rots, each | NULL; g_means, g_cov6 and g_tetpoints are not read) and `route` | NULL, whose
+ * records are filled as d3ga_cage_deform_bwd fills them.  The vertex gather and the skinning / pose tails are NOT launched:
+ * d3ga_cage_deform_bwd_tail runs them on these records.  dL_dmeans3D and dL_dcov3D may BOTH be NULL here (not written; one without
+ * the other is D3GA_E_CONFIG); dL/dSH, dL/dopacity and dL/dmean2D are the parent's bit for bit.  g_barys, g_scales, g_rots and the
+ * records are those of the two calls up to the last bit of dL/dmean and dL/dcov (the compiler contracts the multiply-adds of values
+ * that stay in registers differently) -- and bit for bit when the two arrays are requested, which are then written by the parent's
+ * own code and taken from there.  One view on the full raster with a precomputed covariance only: n_views > 1, a windowed camera
+ * slot, scales / rotations (or their gradients) return D3GA_E_CONFIG, as does every deform argument d3ga_cage_deform_bwd
+ * refuses.  d3ga_raster_backward_deform / _l1_deform: the clear and the compositing backward of their parents, then this. */
+int d3ga_raster_preprocess_bwd_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs,
+                                      const float *scales, const float *rotations, const float *cov3D_precomp,
+                                      const float *viewmatrix, const float *projmatrix, const float *campos,
+                                      const void *geom, const float *acc, float *dL_dmeans3D, float *dL_dmeans2D,
+                                      float *dL_dopacity, float *dL_dsh, float *dL_dcolors, float *dL_dcov3D,
+                                      float *dL_dscales, float *dL_drots, const d3ga_cage_deform_in *deform,
+                                      const d3ga_cage_deform_grads *dgrads, const d3ga_cage_deform_route *route,
+                                      d3ga_stream_t stream);
+int d3ga_raster_backward_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs, const float *scales,
+                                const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                                const float *projmatrix, const float *campos, const float *bg, const void *geom,
+                                const void *binning, int64_t d_capacity, const void *img, const float *dL_dpix, float *acc,
+                                float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh,
+                                float *dL_dcolors, float *dL_dcov3D, float *dL_dscales, float *dL_drots,
+                                const d3ga_cage_deform_in *deform, const d3ga_cage_deform_grads *dgrads,
+                                const d3ga_cage_deform_route *route, d3ga_stream_t stream);
+int d3ga_raster_backward_l1_deform(const d3ga_raster_params *prm, const float *means3D, const float *shs, const float *scales,
+                                   const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                                   const float *projmatrix, const float *campos, const float *bg, const void *geom,
+                                   const void *binning, int64_t d_capacity, const void *img, const float *image,
+                                   const float *target, const void *target_cell, const float *g_loss, const float *dL_dpix,
+                                   float *acc, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dopacity, float *dL_dsh,
+                                   float *dL_dcolors, float *dL_dcov3D, float *dL_dscales, float *dL_drots,
+                                   const d3ga_cage_deform_in *deform, const d3ga_cage_deform_grads *dgrads,
+                                   const d3ga_cage_deform_route *route, d3ga_stream_t stream);
 
 /* View-sharded training (no reference counterpart: the reference trains on one GPU).  Per view v
  * the SH gradient is rank-1 per Gaussian: dL/dsh[i][k][c] = Y_k(normalize(means3D[i] - campos_v)) * g_v[i][c] with g_v the
