@@ -10,6 +10,7 @@ from .frame_state import Embedding, FramePoses, RowCache, code_lookup, convert_o
 from .knn import knn_points  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
 from .objective import TrainingObjective, scale_energy  # noqa: F401
+from .pose_prior import PosePCA  # noqa: F401
 from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, interpolate_face_attributes,  # noqa: F401
                           rasterize_meshes, to_cameras, vertex_normals)
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
@@ -18,4 +19,4 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "Fragments", "MeshCameras", "MeshScratch", "MeshTopology", "Renderer", "rasterize_meshes", "to_cameras", "vertex_normals",
            "PCRenderer", "PointFragments", "PointScratch", "rasterize_points", "knn_points", "interpolate_face_attributes",
            "BaryBinding", "bary_interp", "cage_attr", "mesh_means", "code_lookup", "Embedding", "RowCache", "FramePoses",
-           "convert_optimizer_state", "scale_energy", "TrainingObjective"]
+           "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA"]

@@ -131,6 +131,10 @@ OBJ_MAX_FRAMES, OBJ_SLOTS, OBJ_MAX_LEN, OBJ_TERMS = 16, 9, 4096, 9    # D3GA_OBJ
 OBJ_STATUS_NAN_SEEN, OBJ_STATUS_FIRST_BAD, OBJ_STATUS_STEPS, OBJ_STATUS_TERMS, OBJ_STATUS_WORDS = 0, 1, 2, 4, 16
 
 
+POSE_MAX_D, POSE_FIT_CHUNK = 256, 256    # D3GA_POSE_MAX_D, D3GA_POSE_FIT_CHUNK (include/d3ga.h): widest pose / most components, rows per reduction chunk of the fit
+POSE_STAGE_PROJECT, POSE_STAGE_CLIP, POSE_STAGE_RECONSTRUCT = 1, 2, 4    # D3GA_POSE_STAGE_*: stages of d3ga_pose_clamp
+
+
 class ObjectiveEntry(ctypes.Structure):
     """struct d3ga_objective_entry (include/d3ga.h): one input of one frame, and where its gradient goes."""
     _fields_ = [("ptr", ctypes.c_void_p), ("len", ctypes.c_int32), ("goff", ctypes.c_int32)]
@@ -284,6 +288,9 @@ _SIGNATURES = {
     "d3ga_scale_energy_bwd": ([_i64, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp], _i),
     "d3ga_objective_fwd": ([ctypes.POINTER(ObjectiveDesc), _vp, _vp, _vp], _i),
     "d3ga_objective_bwd": ([ctypes.POINTER(ObjectiveDesc), _vp, _vp, _i64, _vp], _i),
+    "d3ga_pose_fit_scratch_bytes": ([ctypes.c_int32] * 2 + [ctypes.POINTER(_i64)], _i),
+    "d3ga_pose_fit": ([_vp] + [ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
+    "d3ga_pose_clamp": ([_vp, _vp] + [ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

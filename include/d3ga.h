@@ -1281,6 +1281,39 @@ int d3ga_scale_energy_bwd(int64_t n, const float *scaling, const float *delta, i
 int d3ga_objective_fwd(const d3ga_objective_desc *desc, float *out, int32_t *status, d3ga_stream_t stream);
 int d3ga_objective_bwd(const d3ga_objective_desc *desc, const float *g, float *grads, int64_t n_grads, d3ga_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The pose prior: the PCA over the refined poses that test.py:264-274 builds once per run, and the clamp of
+ * test.py:49-56 that every driven frame goes through.  All arithmetic is float64 (csrc/pose_prior_math.h holds it and its
+ * summation orders); poses enter and leave as float32.  No entry point allocates or synchronises; all are capturable; no
+ * atomics, every sum in a fixed order that does not depend on the launch geometry: results are reproducible bit for bit.
+ *
+ * d3ga_pose_fit: table (N,D) float32 -> out (D + D D doubles): the column mean, then the covariance of the centred rows
+ *   C = sum_n (x_n - mean)(x_n - mean)^T / (N - 1), row-major and symmetric bit for bit.  Two passes (mean, then covariance) of
+ *   two launches each: rows in ascending order inside a chunk of D3GA_POSE_FIT_CHUNK rows, then the chunks in ascending
+ *   order.  scratch: d3ga_pose_fit_scratch_bytes(N, D) bytes, 8-byte aligned like out (else D3GA_E_CONFIG).  2 <= N,
+ *   1 <= D <= D3GA_POSE_MAX_D, N D <= INT32_MAX (else D3GA_E_SIZE).
+ * d3ga_pose_clamp: B >= 1 poses, one workgroup each, in ONE launch.  mean (D), comp (k,D), comp_t (D,k) = its transpose and
+ *   std (k) are doubles on the device, 1 <= k <= D3GA_POSE_MAX_D.  stages:
+ *     PROJECT | CLIP | RECONSTRUCT   in (B,D) -> out (B,D):   z_j = sum_d (x_d - mean_d) V_jd, d ascending;
+ *                                    zc_j = min(max(z_j, -sigma std_j), sigma std_j) (a NaN stays one);
+ *                                    out_d = float32((sum_j zc_j V_jd) + mean_d), j ascending
+ *     PROJECT                        in (B,D) -> out (B,k) = float32(z)
+ *     RECONSTRUCT                    in (B,k) = z -> out (B,D)
+ *   (any other combination: D3GA_E_CONFIG).  rows == NULL: pose b is row b of `in`.  rows (B int32 ON THE DEVICE; needs
+ *   PROJECT, else D3GA_E_CONFIG): pose b is row rows[b] of the table `in` (n_rows, D); a row outside [0, n_rows) leaves output
+ *   row b untouched and sets flag[0] = 1 (sticky: nobody clears it but the caller).  flag must not be NULL with rows.
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_POSE_MAX_D 256
+#define D3GA_POSE_FIT_CHUNK 256
+#define D3GA_POSE_STAGE_PROJECT 1
+#define D3GA_POSE_STAGE_CLIP 2
+#define D3GA_POSE_STAGE_RECONSTRUCT 4
+int d3ga_pose_fit_scratch_bytes(int32_t N, int32_t D, int64_t *bytes);
+int d3ga_pose_fit(const float *table, int32_t N, int32_t D, double *out, void *scratch, d3ga_stream_t stream);
+int d3ga_pose_clamp(const float *in, const int32_t *rows, int32_t n_rows, int32_t B, int32_t D, int32_t k, const double *mean,
+                    const double *comp, const double *comp_t, const double *std, double sigma, int32_t stages, float *out,
+                    int32_t *flag, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
