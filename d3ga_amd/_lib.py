@@ -49,6 +49,7 @@ class RasterParams(ctypes.Structure):
                 ("antialiasing", ctypes.c_int32), ("prefiltered", ctypes.c_int32), ("debug", ctypes.c_int32),
                 ("opacity_activation", ctypes.c_int32), ("forward_only", ctypes.c_int32),
                 ("acc_self_clearing", ctypes.c_int32), ("n_views", ctypes.c_int32), ("per_view_geometry", ctypes.c_int32),
+                ("tile_cull", ctypes.c_int32),
                 ("factor_rows", ctypes.c_int32), ("per_view_appearance", ctypes.c_int32), ("per_view_background", ctypes.c_int32)]
 
 

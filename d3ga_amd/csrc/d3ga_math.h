@@ -311,6 +311,41 @@ D3GA_HD void tile_rect(float px, float py, float radius, int gx, int gy, int rec
     rect[3] = clampi((int)((py + radius + kTile - 1) / kTile), 0, gy);
 }
 
+// One axis of tile_rect_tight: the tiles t of [r0, r1) whose pixels [16 t, 16 t + 15] meet [c - h, c + h], i.e. those for which
+// the compositing forward's stage-one test, !(c + h < x0) && !(c - h > x0 + 7) with x0 = 16 t or 16 t + 8, can pass for one of the
+// tile's two quadrants: every such t has !(c + h < 16 t) && !(c - h > 16 t + 15).  lo and hi are the forward's own float
+// expressions (rounding is monotone, so a pixel inside the exact interval is inside the rounded one); a NaN end restricts
+// nothing, as in the forward.  Tile edges are exact in float, and the ends are clamped as floats, so any magnitude is safe.
+D3GA_HD void tile_span_tight(float c, float h, int r0, int r1, int &o0, int &o1) {
+    D3GA_NO_CONTRACT
+    const float lo = c - h, hi = c + h;
+    o0 = r0; o1 = r1;
+    if (lo == lo) {                               // first tile with !(lo > 16 t + 15)
+        float t = floorf(lo * (1.0f / kTile));
+        if (lo > t * kTile + (kTile - 1)) t += 1.0f;
+        o0 = (int)fminf(fmaxf(t, (float)r0), (float)r1);
+    }
+    if (hi == hi) {                               // one past the last tile with !(hi < 16 t)
+        const float t = floorf(hi * (1.0f / kTile)) + 1.0f;
+        o1 = (int)fminf(fmaxf(t, (float)r0), (float)r1);
+    }
+}
+// The reference rectangle `ref` (tile_rect; not empty) of a splat centred at (px, py) cut down to the tiles its alpha >= 1/255 box
+// (half extents hx, hy: splat_cull) can reach.  Never larger than `ref`, never empty: where the box reaches no tile of `ref` --
+// hx < 0 (opacity x 255 < 1), or a box that lies between two pixel rows or columns -- the one tile of `ref` nearest the centre is
+// kept, so that the Gaussian stays visible (a non-empty rectangle is what the scatter pass and the backward test).  out may be ref.
+D3GA_HD void tile_rect_tight(const int ref[4], float px, float py, float hx, float hy, int out[4]) {
+    int x0, x1, y0, y1;
+    tile_span_tight(px, hx, ref[0], ref[2], x0, x1);
+    tile_span_tight(py, hy, ref[1], ref[3], y0, y1);
+    if (hx < 0.0f || x1 <= x0 || y1 <= y0) {
+        const float tx = floorf(px * (1.0f / kTile)), ty = floorf(py * (1.0f / kTile));
+        x0 = (int)fminf(fmaxf(tx, (float)ref[0]), (float)(ref[2] - 1)); x1 = x0 + 1;
+        y0 = (int)fminf(fmaxf(ty, (float)ref[1]), (float)(ref[3] - 1)); y1 = y0 + 1;
+    }
+    out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1;
+}
+
 constexpr float kAaFloor = 0.000025f;   // [UPSTREAM-RECALL] branch dr_aa: h_convolution_scaling = sqrt(max(0.000025, det_cov / det_cov_plus_h_cov))
 D3GA_HD Splat project_gaussian(V3 mean, const float c6[6], const float *view, const float *proj, int W, int H,
                                float tanfovx, float tanfovy, bool antialiasing = false) {

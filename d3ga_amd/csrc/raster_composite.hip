@@ -14,7 +14,10 @@
 //      list, straight-line and front to back (records through per-row broadcast ds_reads, offsets read one iteration ahead);
 //      the wavefront stops when all 64 pixels are saturated (T < 1e-4).
 // Culled entries provably contribute nothing (alpha < 1/255 on every pixel of the block), so the result is identical to
-// walking the full tile list; list positions (n_contrib) stay positions in the FULL list.
+// walking the full tile list; list positions (n_contrib) stay positions in the FULL list -- the list binning built: with
+// d3ga_raster_params::tile_cull that list is the reference's without the entries whose alpha >= 1/255 box misses the whole tile
+// (stage one would have dropped them for all four quadrants), and n_contrib and the positions in the blocks' culled lists are
+// positions in that SHORTER list; the survivors, their order and the image are the same.
 // Dispatch: quad_of_block_ordered() hands the quadrants out heaviest tile first (tile_order of the bin stage), the four
 // quadrants of a tile on one XCD (workgroup b lands on XCD b % 8: observed, speed only).
 // Numbers, history and the negative results (persistent workers, dispatch orders, occupancy): DESIGN.md sec. 4.

@@ -191,6 +191,16 @@ __device__ __forceinline__ TileRect view_tile_rect(const PreOut &o, int tile_row
     const Splat &sp = o.sp;
     return TileRect{sp.visible, sp.rect[0], sp.rect[1] + tile_row0, sp.rect[2], sp.rect[3] + tile_row0};
 }
+// d3ga_raster_params::tile_cull (the TC instantiations): the rectangle that goes to the reservation and into geom.rect is the
+// reference's cut down to the tiles the splat's alpha >= 1/255 box reaches (d3ga_math.h: tile_rect_tight), from the half extents
+// the compositing forward's stage one tests with -- the splat_cull() whose result write_geom_records_splat stores.  On the view's
+// own raster, so in front of a window clip.  Nothing else of the splat moves.
+__device__ __forceinline__ void tile_tighten(PreOut &o) {
+    Splat &sp = o.sp;
+    if (!sp.visible) return;
+    const SplatCull sc = splat_cull(sp.conic[0], sp.conic[1], sp.conic[2], o.opacity);
+    tile_rect_tight(sp.rect, sp.px, sp.py, sc.hx, sc.hy, sp.rect);
+}
 // what preprocess leaves per Gaussian (GeomBuf records of ITS view, radius), in two parts: what the projection alone decides, and
 // what needs the colour.  preprocess_kernel's full wavefronts store the first part before the SH passes, so that the splat does not
 // sit in registers through them; 1 / depth and the visibility are what the second part keeps of it.
@@ -312,7 +322,7 @@ __device__ __forceinline__ void tile_reserve_store(const TileResv &r, uint32_t *
 
 // The per-view tail of both forward kernels: R1 of Gaussian i in view `cam` from what the kernel has in registers (staged: the SH
 // colour sum in cj.a0..a2; pre: the covariance row and raw opacity; mean: its means3D row).  WIN: the rectangle is clipped to the window's gx x gy tiles.
-template <bool WIN>
+template <bool WIN, bool TC = false>
 __device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm, const ViewCam &cam, int i, V3 mean,
                                                     const float *sh_row, bool staged, const ShColJ &cj, bool pre, const float (&pc6)[6],
                                                     float pop, const float *colors_precomp, const float *opacities, const float *scales,
@@ -325,6 +335,7 @@ __device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm,
     pl.op = pop;
     pl.has_mean = true; pl.mean = mean;
     PreOut o = preprocess_one(prm, cam, i, nullptr, sh_row, colors_precomp, opacities, scales, rotations, cov3D_precomp, pl);
+    if constexpr (TC) tile_tighten(o);
     if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
     return o;
 }
@@ -341,7 +352,7 @@ __device__ __forceinline__ PreOut preprocess_view(const d3ga_raster_params &prm,
 // under the mean's and the covariance's round trips, not under the projection.  Then projection, eight returning atomics and the
 // record stores with nothing waited for, the slab writes of half 0 (vmcnt(10)..(5): the atomics stay out), first pass, half 1.
 // Per wavefront: mean | covariance (+ half 0) | half 1, against the parent's mean | half 0 | half 1 | mean again.  slab: its LDS.
-template <bool WIN>
+template <bool WIN, bool TC = false>
 __device__ __forceinline__ void preprocess_full_wavefront(
     const d3ga_raster_params &prm, const ViewCam &cam, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ opacities, const float *__restrict__ cov3D_precomp, const float *__restrict__ campos, const GeomBuf &geom,
@@ -366,6 +377,7 @@ __device__ __forceinline__ void preprocess_full_wavefront(
     sh_two_pass48(slab, shs + (size_t)48 * row0, lane, [&]() __attribute__((always_inline)) {
         PreOut o = preprocess_geom(prm, cam, i, pl.mean, opacities, nullptr, nullptr, cov3D_precomp, pl);
         if constexpr (WIN) visible = o.sp.visible;   // before the window clip: what the colour is formed for
+        if constexpr (TC) tile_tighten(o);
         if constexpr (WIN) o = window_clip(o, cam.ox / kTile, cam.oy / kTile, gx, gy);
         rs = tile_reserve_issue<true>(reinterpret_cast<uint32_t *>(slab), view_tile_rect(o, tile_row0), gx, tile_count, tile_count2, vis_part);
         invd = write_geom_records_splat(geom, i, o, false, tile_row0, radii);
@@ -384,7 +396,7 @@ __device__ __forceinline__ void preprocess_full_wavefront(
 }
 
 // WIN: windowed camera slot (campos: 9 floats, d3ga.h): project with the view's raster size, histogram over the window's tiles
-template <bool WANT_J, bool WIN>      // WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
+template <bool WANT_J, bool WIN, bool TC = false>      // TC: tile_tighten() in front of the reservation (d3ga_raster_params::tile_cull); WANT_J: a backward will follow (forward_only == 0) and the SH coefficients are staged: leave d(colour)/d(direction) for it
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
@@ -408,8 +420,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     // (Training forward with precomputed covariances only.  The forward-only kernel is lighter in its SH passes: carrying the reservation's bases and 1 / depth
     // through them costs it registers, 71 -> 85 VGPRs and from 7 to 5 wavefronts per SIMD.  It keeps the order below.)
     if (WANT_J && staged && cov3D_precomp && M3 == 48 && prm.P - row0 >= 64) {   // wave-uniform: a full wavefront of full rows (M = 16)
-        preprocess_full_wavefront<WIN>(prm, cam, means3D, shs, opacities, cov3D_precomp, campos, geom, tile_count, tile_count2, vis_part, rec,
-                                       radii, tile_row0, gx, gy, s_sh + wave * kShHalfSlab);
+        preprocess_full_wavefront<WIN, TC>(prm, cam, means3D, shs, opacities, cov3D_precomp, campos, geom, tile_count, tile_count2, vis_part, rec,
+                                           radii, tile_row0, gx, gy, s_sh + wave * kShHalfSlab);
         return;
     }
     // mean (ONE load per Gaussian: the direction and the projection both take the value), covariance row and opacity
@@ -435,10 +447,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     PreOut o = {};
     if (i < prm.P) {
         // two call sites so that each inlined copy sees ONE address space (registers vs global_load, never flat)
-        o = staged ? preprocess_view<WIN>(prm, cam, i, mean, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
-                                          rotations, cov3D_precomp, gx, gy)
-                   : preprocess_view<WIN>(prm, cam, i, mean, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
-                                          colors_precomp, opacities, scales, rotations, cov3D_precomp, gx, gy);
+        o = staged ? preprocess_view<WIN, TC>(prm, cam, i, mean, nullptr, true, cj, pre, pc6, pop, colors_precomp, opacities, scales,
+                                              rotations, cov3D_precomp, gx, gy)
+                   : preprocess_view<WIN, TC>(prm, cam, i, mean, shs ? shs + (size_t)M3 * i : nullptr, false, cj, false, pc6, pop,
+                                              colors_precomp, opacities, scales, rotations, cov3D_precomp, gx, gy);
         tr = view_tile_rect(o, tile_row0);
     }
     // the slab is dead now; the reservation's atomics are in flight while the records are stored
@@ -505,7 +517,7 @@ __device__ __forceinline__ void staged_sh_colour_views(const d3ga_raster_params 
     }
 }
 
-template <bool WANT_J, int KV>
+template <bool WANT_J, int KV, bool TC = false>
 __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
     d3ga_raster_params prm, const float *__restrict__ means3D, const float *__restrict__ shs,
     const float *__restrict__ colors_precomp, const float *__restrict__ opacities, const float *__restrict__ scales,
@@ -538,9 +550,9 @@ __global__ __launch_bounds__(kBlock) void preprocess_views_kernel(
         PreOut o = {};
         if (i < prm.P) {
             const size_t og = pv * v;
-            o = preprocess_view<false>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, ld3(means3D + 3 * og, i), nullptr, true,
-                                       cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
-                                       rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, gx, 0);
+            o = preprocess_view<false, TC>(prm, view_cam(prm, cams.vm[v], cams.pm[v], cams.cp[v], false), i, ld3(means3D + 3 * og, i), nullptr, true,
+                                           cj[v], pre, pc6, pop, colors_precomp, opacities, scales ? scales + 3 * og : nullptr,
+                                           rotations ? rotations + 4 * og : nullptr, cov3D_precomp ? cov3D_precomp + 6 * og : nullptr, gx, 0);
             tr = view_tile_rect(o, tile_row0 + v * gyv);
         }
         const TileResv rs = tile_reserve_issue(s_win, tr, gx, tile_count, tile_count2, vis_part);
@@ -944,6 +956,7 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     uint32_t *const resv = resv_records(binning, tiles, d_capacity, views, wnd);
     const size_t resv_view = (size_t)resv_waves(prm->P) * kResvStride;                 // words between the views' records
     const bool want_j = leaves_dcol(prm, shs);
+    const bool tc = prm->tile_cull != 0;      // the instantiations that bin by the alpha >= 1/255 box (tile_tighten)
     const int cs = cam_stride(prm);
     // a batch of views writes view v's records at v P + i of the batch's buffers: grouped launches below when the SH row can be
     // shared, else one launch per view (a streaming kernel at the copy rate gains nothing from a taller grid)
@@ -958,7 +971,9 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
     auto launch_group = [&](auto kv) {        // views [v0, v0 + KV)
         constexpr int KV = decltype(kv)::value;
         const size_t og = pv * v0;
-        hipLaunchKernelGGL((want_j ? preprocess_views_kernel<true, KV> : preprocess_views_kernel<false, KV>), grid, block, lds, s, *prm,
+        const auto kernel = tc ? (want_j ? preprocess_views_kernel<true, KV, true> : preprocess_views_kernel<false, KV, true>)
+                               : (want_j ? preprocess_views_kernel<true, KV> : preprocess_views_kernel<false, KV>);
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, *prm,
                            at(means3D, 3, og), shs, colors_precomp, opacities, at(scales, 3, og), at(rotations, 4, og),
                            at(cov3D_precomp, 6, og), view_cams<KV>(viewmatrix, projmatrix, campos, cs, v0, KV), geom_view(g, prm->P, v0),
                            bin.tile_count, bin.tile_count2, bin.vis_part, resv + resv_view * v0, radii + (size_t)prm->P * v0, v0 * gyv,
@@ -971,8 +986,10 @@ extern "C" int d3ga_raster_preprocess(const d3ga_raster_params *prm, const float
         else if (left == 3 || left == 5) launch_group(std::integral_constant<int, 3>());
         else launch_group(std::integral_constant<int, 2>());
     }
-    const auto kernel = want_j ? (wnd ? preprocess_kernel<true, true> : preprocess_kernel<true, false>)
-                               : (wnd ? preprocess_kernel<false, true> : preprocess_kernel<false, false>);
+    const auto kernel = tc ? (want_j ? (wnd ? preprocess_kernel<true, true, true> : preprocess_kernel<true, false, true>)
+                                      : (wnd ? preprocess_kernel<false, true, true> : preprocess_kernel<false, false, true>))
+                            : (want_j ? (wnd ? preprocess_kernel<true, true> : preprocess_kernel<true, false>)
+                                      : (wnd ? preprocess_kernel<false, true> : preprocess_kernel<false, false>));
     for (int v = v0; v < views; ++v) {
         const ViewCams<1> c = view_cams<1>(viewmatrix, projmatrix, campos, cs, v, 1);
         const size_t og = pv * v, oa = pa * v;

@@ -80,7 +80,7 @@ class CameraBatch:
 class _RasterizeViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cams, bg, sh_degree,
-                scale_modifier, antialiasing, opacity_activation, l1_targets, colors2=None, bg2=None, grad_sync=None):
+                scale_modifier, antialiasing, opacity_activation, l1_targets, colors2=None, bg2=None, grad_sync=None, tile_cull=False):
         require_cuda(means3D)
         dev = means3D.device
         f32 = lambda t: _R._f32(t, dev)
@@ -117,7 +117,7 @@ class _RasterizeViews(torch.autograd.Function):
                 raise ValueError("rasterize_gaussians_views: colors2 is (P,3) and bg2 (3,), shared by the views")
         marker = _lib.CAMERA_SLOT_WINDOWED if windowed else 0.0         # camera slots: tangents (and windows) from the device rows
         prm = _R._params(P, M, int(sh_degree), W, H, marker, marker, float(scale_modifier), bool(antialiasing), False, False,
-                         opacity_activation, fwd_only, k, per_view, pva, pvb)
+                         opacity_activation, fwd_only, k, per_view, pva, pvb, _R._tile_cull_of(tile_cull))
         colors2_img = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev) if dual else None
         colors = torch.empty((k, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((k, P), dtype=torch.int32, device=dev)
@@ -161,7 +161,7 @@ class _RasterizeViews(torch.autograd.Function):
         means3D, sh, scales, rotations, cov3Ds_precomp, bg, geom, binning, img, image, tgt, colors2, bg2 = ctx.saved_tensors
         prm, cams, dev, P, k = ctx.prm, ctx.cams, means3D.device, ctx.prm.P, ctx.prm.n_views
         if P == 0:
-            return (None,) * 17
+            return (None,) * 18
         g_loss = grad_colors2 = None
         if ctx.l1 and grad_third is not None:
             g_loss = _R._f32(grad_third, dev).reshape(1)
@@ -183,9 +183,9 @@ class _RasterizeViews(torch.autograd.Function):
         if sync is not None:
             parked, g_sh = _R._exchange_gradients(sync, prm, cut, cams.campos, means3D)
             if parked:
-                return (None,) * 17
+                return (None,) * 18
         return (g_means3D, g_sh, g_col if sh is None else None, g_opac, g_scales, g_rots, g_cov,
-                None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None)
 
 
 def _appearance_per_view(opacities, colors_precomp, sh, k, P):
@@ -222,7 +222,7 @@ def _background_per_view(bg, k):
 
 def rasterize_gaussians_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cameras, bg, sh_degree=0,
                               scale_modifier=1.0, antialiasing=False, opacity_activation=None, l1_targets=None, colors2=None, bg2=None,
-                              grad_sync=None):
+                              grad_sync=None, tile_cull=False):
     """k views in one grid per stage.  cameras: a CameraBatch; bg (3,) shared by the views or (k,3), one per view (the reference
     draws a background per frame, models/trainer.py:95-100).
     Geometry: means3D (P,3) with cov3Ds_precomp (P,6) | scales + rotations -- k CAMERAS of one set of Gaussians -- or all of them
@@ -235,7 +235,8 @@ def rasterize_gaussians_views(means3D, sh, colors_precomp, opacities, scales, ro
     backward; with colors2 (P,3) + bg2: (colors, radii, colors2_image (k,3,H,W)) -- the reference's RGB + silhouette pair
     (models/trainer.py:102-110) from one pass, colors2 constant.  Gradients as `rasterize_gaussians`: summed over the views for
     shared inputs, per view for (k,P,.) geometry.  grad_sync: a dist.ViewShardedGrads -- the returned gradients are then already
-    averaged over the ranks of a camera-sharded run (every rank renders its own k cameras of the pose); not with per-view appearance."""
+    averaged over the ranks of a camera-sharded run (every rank renders its own k cameras of the pose); not with per-view appearance.
+    tile_cull: bin by the alpha >= 1/255 box (GaussianRasterizationSettings.tile_cull; rasterizer.set_tile_cull overrides it)."""
     k = cameras.n_views
     if k > 1 and opacities is not None and colors_precomp is not None:
         P = means3D.shape[-2]
@@ -245,4 +246,4 @@ def rasterize_gaussians_views(means3D, sh, colors_precomp, opacities, scales, ro
         elif colors_precomp.dim() == 3 and not op_pv:
             opacities = opacities.reshape(1, P, 1).expand(k, P, 1)
     return _RasterizeViews.apply(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, cameras, bg,
-                                 sh_degree, scale_modifier, antialiasing, opacity_activation, l1_targets, colors2, bg2, grad_sync)
+                                 sh_degree, scale_modifier, antialiasing, opacity_activation, l1_targets, colors2, bg2, grad_sync, tile_cull)

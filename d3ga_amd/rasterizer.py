@@ -38,6 +38,10 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool
     debug: bool
     antialiasing: bool = False
+    # extension (not in upstream): bin every Gaussian by its alpha >= 1/255 box instead of the reference's 3-sigma square
+    # (d3ga_raster_params::tile_cull).  Off: tile lists, D and max_tile are upstream's.  On: the same image bit for bit from
+    # shorter lists -- every tile's list a subsequence of upstream's.  renderer.render / render_l1 / render_pair turn it on.
+    tile_cull: bool = False
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -104,6 +108,26 @@ def set_accumulator_policy(mode):
     _acc_policy["persistent"] = mode == "persistent"
     if mode == "fresh":
         _acc_cache.clear()
+
+
+# ------------------------------------------------------------------------------------------------------------
+# tile lists from the alpha >= 1/255 box
+# ------------------------------------------------------------------------------------------------------------
+_tile_cull = {"override": None}
+
+
+def set_tile_cull(mode):
+    """None (default): every render follows its settings' `tile_cull` (off for the drop-in classes, on for renderer.render /
+    render_l1 / render_pair).  True / False: process-wide override of that field for every render issued from now on -- a way
+    back to the reference's lists, and an A/B switch within one build.  A captured step keeps the rule it was captured with."""
+    if mode not in (None, True, False):
+        raise ValueError(mode)
+    _tile_cull["override"] = mode
+
+
+def _tile_cull_of(requested):
+    o = _tile_cull["override"]
+    return bool(requested) if o is None else o
 
 
 # D3GA_L1_VALUE=separate: the L1 value from its own pass over the finished image (rounds 1-3; kept for A/B runs)
@@ -216,12 +240,12 @@ def _scratch(P, W, H, k, cap, device, forward_only, windowed, binning=True):
 
 
 def _params(P, M, sh_degree, W, H, tanfovx, tanfovy, scale_modifier, antialiasing, prefiltered, debug, opacity_activation,
-            forward_only, n_views=0, per_view_geometry=False, per_view_appearance=False, per_view_background=False):
+            forward_only, n_views=0, per_view_geometry=False, per_view_appearance=False, per_view_background=False, tile_cull=False):
     """The parameter block with these field values, built once per distinct value: the block of a training loop repeats, and
     building the ctypes structure costs ~6 us of an ~80 us host-bound render.  Shared (a retained graph, this cache): never
     written to -- `_prm_variant` gives the block that differs in a field."""
     key = (P, M, sh_degree, W, H, tanfovx, tanfovy, scale_modifier, antialiasing, prefiltered, debug, opacity_activation,
-           forward_only, n_views, per_view_geometry, per_view_appearance, per_view_background)
+           forward_only, n_views, per_view_geometry, per_view_appearance, per_view_background, tile_cull)
     prm = _prm_cache.get(key)
     if prm is None:
         if len(_prm_cache) > 64:
@@ -231,7 +255,7 @@ def _params(P, M, sh_degree, W, H, tanfovx, tanfovy, scale_modifier, antialiasin
             antialiasing=int(antialiasing), prefiltered=int(prefiltered), debug=int(debug),
             opacity_activation=_ACTIVATIONS[opacity_activation], forward_only=int(forward_only), n_views=n_views,
             per_view_geometry=int(per_view_geometry), per_view_appearance=int(per_view_appearance),
-            per_view_background=int(per_view_background))
+            per_view_background=int(per_view_background), tile_cull=int(tile_cull))
         prm.cache_key = key          # (a Python attribute on the ctypes instance, not a field of the C structure: _prm_variant's key)
     return prm
 
@@ -496,7 +520,7 @@ def _tkey(t):
 
 
 def _geometry_key(prm, cap_mode, tensors):
-    return (prm.P, prm.W, prm.H, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.prefiltered, prm.opacity_activation, prm.antialiasing, cap_mode) + tuple(
+    return (prm.P, prm.W, prm.H, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.prefiltered, prm.opacity_activation, prm.antialiasing, prm.tile_cull, cap_mode) + tuple(
         _tkey(t) for t in tensors)
 
 
@@ -561,7 +585,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # no input requires a gradient (inference, torch.no_grad): the forward skips the per-block lists of the backward
         fwd_only = not any(ctx.needs_input_grad[:8])
         prm = _params(P, M, int(s.sh_degree), W, H, tfx, tfy, float(s.scale_modifier), bool(s.antialiasing), bool(s.prefiltered),
-                      bool(s.debug), opacity_activation, fwd_only)
+                      bool(s.debug), opacity_activation, fwd_only, tile_cull=_tile_cull_of(getattr(s, "tile_cull", False)))
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         # fused L1 image loss (rasterize_gaussians_l1): the loss VALUE is formed by the compositing forward while the colours
         # are in registers (d3ga_raster_composite_fwd_l1: one partial per quadrant, then one small sum), its gradient inside

@@ -64,7 +64,7 @@ def _windowed_slot(batch):
     return slot is not None and getattr(slot, "windowed", False)
 
 
-def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=None, bg_color2=None, grad_sync=None):
+def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=None, bg_color2=None, grad_sync=None, tile_cull=False):
     """k views in one pass (extension; the reference renders one camera per call and averages the losses of a batch of frames,
     train.py:218-221): -> {"render": (k,3,H,W)}; with targets (k,3,H,W) also "l1" = the mean over the views of `l1_loss(render,
     target)` (its gradient formed inside the compositing backward); with colors2 (P,3) + bg_color2 (3,) also "render2" (k,3,H,W), the
@@ -80,7 +80,9 @@ def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=Non
     through their crop windows (CameraBatch(windowed=True), include/d3ga.h: D3GA_CAMERA_SLOT_WINDOWED): every image is then
     `paste(render(batch_v, ...)["render"], crop_v)`, (k,3,H,W) with (W,H) = crop[4], crop[5], which must be the same for all views;
     targets are (k,3,H,W) windows.  Centred views of one raster size take the full-raster path.  cameras: a `raster_views.CameraBatch`
-    to reuse (a captured step keeps one and calls `cameras.set(batches)` before every replay); batches may then be None."""
+    to reuse (a captured step keeps one and calls `cameras.set(batches)` before every replay); batches may then be None.
+    tile_cull: bin by the alpha >= 1/255 box as `render` does (GaussianRasterizationSettings.tile_cull).  Off by default here: the
+    batch's tile lists are then the reference's, view by view."""
     from .raster_views import CameraBatch, rasterize_gaussians_views
     frames = pkg if isinstance(pkg, (list, tuple)) else None
     if frames is not None:
@@ -119,7 +121,7 @@ def render_views(batches, pkg, bg_color, targets=None, cameras=None, colors2=Non
     out = rasterize_gaussians_views(means3D, shs, None if shs is not None else pkg["rgb"], opacities, pkg.get("scales"),
                                     pkg.get("rotations"), pkg.get("cov3D_precomp"), cameras, bg_color,
                                     sh_degree=pkg["sh_degree"] if "sh_degree" in pkg else 0, opacity_activation=act, l1_targets=targets,
-                                    colors2=colors2, bg2=bg_color2, grad_sync=grad_sync)
+                                    colors2=colors2, bg2=bg_color2, grad_sync=grad_sync, tile_cull=tile_cull)
     if colors2 is not None:
         return {"render": out[0], "render2": out[2]}
     return {"render": out[0], "l1": out[2]} if targets is not None else {"render": out[0]}
@@ -164,6 +166,7 @@ def render(batch, pkg, bg_color, colors_precomp=None, measure_time=False, solid_
         prefiltered=False,
         debug=False,
         antialiasing=False,
+        tile_cull=True,                   # (extension) lists from the alpha >= 1/255 box: the same image from shorter lists
     )
 
     # what the rasterizer is handed (renderer.py:95-120): geometry as packaged; `detach` names inputs whose gradient is cut

@@ -28,7 +28,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define D3GA_VERSION 112 /* (the d3ga_vgg_*, d3ga_bary_interp_* and the frame-state entry points d3ga_code_lookup_*, d3ga_table_mean*, d3ga_row_cache_*, and the objective's d3ga_scale_energy_*, d3ga_objective_* were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
+#define D3GA_VERSION 112 /* (d3ga_raster_params::tile_cull was added under 112 behind per_view_geometry, 0 = the behaviour before it: factor_rows, per_view_appearance and per_view_background move up by four bytes, so callers must be rebuilt against this header; no entry point changed) (the d3ga_vgg_*, d3ga_bary_interp_* and the frame-state entry points d3ga_code_lookup_*, d3ga_table_mean*, d3ga_row_cache_*, and the objective's d3ga_scale_energy_*, d3ga_objective_* were added under 112: additions only, nothing existing changed) the cage deformation takes descriptor structs: d3ga_cage_deform_{fwd,bwd} replace the seven entry points of ABI 111, d3ga_lbs_cage_bwd takes the pose plan (d3ga_lbs_cage_bwd_pose is gone), no float-atomic vertex gradient; 111: per-view appearance and backgrounds for view-batched rendering (d3ga_raster_params::per_view_appearance, ::per_view_background: the ColorField configuration's batch of frames); 110 (round 6): view-batched rendering (d3ga_raster_params::n_views, d3ga_raster_scratch_bytes_views), d3ga_debug_set / D3GA_KNOB_* replace every environment knob, the opt-in list forwards of round 5 are gone (d3ga_raster_bin_sort_lists, d3ga_raster_params::block_lists), only the functions declared here are exported */
 
 #define D3GA_OK 0
 #define D3GA_E_NULL (-1)     /* required pointer is NULL */
@@ -347,6 +347,15 @@ typedef struct d3ga_raster_params {
      * (k,P,.), not summed; opacities and shs | colors_precomp stay (P,.) with gradients summed over the views unless
      * per_view_appearance is set. */
     int32_t per_view_geometry;
+    /* (added under ABI 112, in front of the fields that only batches of views read)  0: a Gaussian is listed in every tile of the reference's rectangle, the square of ceil(3 sqrt(lambda_max)) around
+     * its centre -- tile lists, the duplicate count D and the longest list are upstream's.  != 0: d3ga_raster_preprocess cuts that
+     * rectangle down to the tiles the Gaussian's alpha >= 1/255 box reaches (the half extents the compositing forward culls with,
+     * GeomBuf::xyh), so the entries that the forward would reject for every pixel of the tile are never scattered, sorted or read.
+     * Images, radii and the visible count are unchanged bit for bit (a visible Gaussian keeps at least one tile); every tile's
+     * list is a subsequence of the reference's, so D, the longest list, per-pixel n_contrib and the positions in the per-block
+     * lists are those of the SHORTER lists.  Gradients agree up to the summation order of float atomics.  Read by
+     * d3ga_raster_preprocess (and d3ga_raster_forward) only; the other stages follow the lists they are given. */
+    int32_t tile_cull;
     /* n_views > 1, SH colours: rows between consecutive views' factors in the dL_dcolors handed to d3ga_raster_preprocess_bwd (0 = P).
      * The camera-sharded exchange keeps one extra row per view (the view's camera position) so that factors and positions travel in
      * ONE all-gather (d3ga_amd/dist.py): P + 1. */
