@@ -6,6 +6,7 @@ There is NO CPU fallback: every op raises if the library is missing or the tenso
 from ._lib import D3GAError, lib, library_path  # noqa: F401
 from .bary_interp import BaryBinding, bary_interp, cage_attr, mesh_means  # noqa: F401
 from .evaluation import Evaluator, compute_errors, compute_heatmap, error_heatmap, psnr  # noqa: F401
+from .frame_grid import GridWriter, Panel, compose_grid, compose_panels, to_uint8, write_text  # noqa: F401
 from .frame_state import Embedding, FramePoses, RowCache, code_lookup, convert_optimizer_state  # noqa: F401
 from .knn import knn_points  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
@@ -19,4 +20,5 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "Fragments", "MeshCameras", "MeshScratch", "MeshTopology", "Renderer", "rasterize_meshes", "to_cameras", "vertex_normals",
            "PCRenderer", "PointFragments", "PointScratch", "rasterize_points", "knn_points", "interpolate_face_attributes",
            "BaryBinding", "bary_interp", "cage_attr", "mesh_means", "code_lookup", "Embedding", "RowCache", "FramePoses",
-           "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA"]
+           "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA",
+           "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter"]

@@ -136,6 +136,27 @@ POSE_MAX_D, POSE_FIT_CHUNK = 256, 256    # D3GA_POSE_MAX_D, D3GA_POSE_FIT_CHUNK 
 POSE_STAGE_PROJECT, POSE_STAGE_CLIP, POSE_STAGE_RECONSTRUCT = 1, 2, 4    # D3GA_POSE_STAGE_*: stages of d3ga_pose_clamp
 
 
+GRID_MAX_PANELS, GRID_MAX_LABEL, GRID_MAX_SIDE = 16, 64, 32768    # D3GA_GRID_MAX_* (include/d3ga.h)
+GRID_OUT_F32_CHW, GRID_OUT_F32_HWC, GRID_OUT_U8_SAVE_IMAGE, GRID_OUT_U8_CLIP = 0, 1, 2, 3    # D3GA_GRID_OUT_*: modes of d3ga_frame_grid
+GRID_BGR, GRID_FORCE_SCALAR = 1, 2       # D3GA_GRID_*: flags of the grid
+PANEL_BOTTOM, PANEL_BOLD = 1, 2          # D3GA_PANEL_*: flags of a panel
+
+
+class GridPanel(ctypes.Structure):
+    """struct d3ga_grid_panel (include/d3ga.h): a source view, where it goes on the canvas, and its label."""
+    _fields_ = [("src", ctypes.c_void_p), ("value", ctypes.c_void_p), ("sc", ctypes.c_int64), ("sh", ctypes.c_int64),
+                ("sw", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("C", "h", "w", "y0", "x0", "flags", "label_len", "X")] + \
+               [("color", ctypes.c_float * 3), ("label", ctypes.c_char * GRID_MAX_LABEL)]
+
+
+class GridDesc(ctypes.Structure):
+    """struct d3ga_grid_desc (include/d3ga.h): the canvas, the output mode and the panel table."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_panels", "out_H", "out_W", "mode", "channels", "flags")] + \
+               [("pad_value", ctypes.c_float), ("reserved", ctypes.c_int32), ("pitch", ctypes.c_int64),
+                ("panel", GridPanel * GRID_MAX_PANELS)]
+
+
 class ObjectiveEntry(ctypes.Structure):
     """struct d3ga_objective_entry (include/d3ga.h): one input of one frame, and where its gradient goes."""
     _fields_ = [("ptr", ctypes.c_void_p), ("len", ctypes.c_int32), ("goff", ctypes.c_int32)]
@@ -292,6 +313,8 @@ _SIGNATURES = {
     "d3ga_pose_fit_scratch_bytes": ([ctypes.c_int32] * 2 + [ctypes.POINTER(_i64)], _i),
     "d3ga_pose_fit": ([_vp] + [ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
     "d3ga_pose_clamp": ([_vp, _vp] + [ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_frame_grid_check": ([ctypes.POINTER(GridDesc), _vp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "d3ga_frame_grid": ([ctypes.POINTER(GridDesc), _vp, ctypes.POINTER(ctypes.c_int32), _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

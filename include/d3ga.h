@@ -1323,6 +1323,67 @@ int d3ga_pose_clamp(const float *in, const int32_t *rows, int32_t n_rows, int32_
                     const double *comp, const double *comp_t, const double *std, double sigma, int32_t stages, float *out,
                     int32_t *flag, d3ga_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The recorder's frame grid: utils/text_helpers.py:27-50 write_text, the th.cat rows and grid of
+ * test.py:145-169 / train.py:344-364, the even-size padding of test.py:176-179 and the uint8 conversions of
+ * torchvision.utils.save_image (test.py:182-195) and of train.py:365, as ONE launch that writes every output element exactly
+ * once.  No entry point allocates or synchronises; d3ga_frame_grid is capturable; no LDS, no atomics.  The arithmetic is
+ * float32, written down in csrc/frame_grid_math.h; the label font is csrc/frame_grid_font.h.
+ *
+ * desc (HOST, copied into the launch: the panel table and the label bytes travel in the kernel arguments): a canvas
+ *   (out_H, out_W), 1..D3GA_GRID_MAX_SIDE each, and 1 <= n_panels <= D3GA_GRID_MAX_PANELS panels.  Panel: src float32 with
+ *   ELEMENT strides (sc, sh, sw) >= 0 of channel, row and column, C in {1, 3, 4} source channels (1 is replicated to RGB; a
+ *   missing alpha is 1), size (h, w) >= 1 at (y0, x0) inside the canvas; two panels that share a pixel: D3GA_E_CONFIG.  Canvas
+ *   pixels that no panel covers get pad_value in every channel.
+ * label: label_len <= D3GA_GRID_MAX_LABEL bytes (0: none), drawn in `color` (RGB) from x = X pixels, its baseline
+ *   int(10 u) below the panel's top or, with D3GA_PANEL_BOTTOM, int(5 u) above its bottom, u = min(w / 150, 17.7) the unit (25
+ *   cells of 6 u fit in the panel's width); D3GA_PANEL_BOLD unites the glyphs with themselves half a unit to the right.  Bytes
+ *   outside 32..126 draw as '?'.  Text never leaves its panel and never touches the alpha channel.  One "{:.3f}" in the label
+ *   is replaced by value[0] (a float32 ON THE DEVICE, read by the launch) as Python formats it; two of them, or one without
+ *   value, or value without one: D3GA_E_CONFIG.
+ * mode: D3GA_GRID_OUT_F32_CHW (channels, out_H, out_W) | D3GA_GRID_OUT_F32_HWC (out_H, out_W, channels), dense float32,
+ *   unquantised; D3GA_GRID_OUT_U8_SAVE_IMAGE | D3GA_GRID_OUT_U8_CLIP: uint8 (out_H, out_W, channels) with rows `pitch`
+ *   bytes apart (>= out_W * channels), quantised as uint8(clamp(x * 255 + 0.5, 0, 255)) (two float32 roundings) |
+ *   uint8(clamp(x * 255, 0, 255)); a NaN gives 0.  channels 3 | 4.  flags: D3GA_GRID_BGR writes the colour channels in the
+ *   order B, G, R; D3GA_GRID_FORCE_SCALAR takes the one-pixel-per-thread path whatever the alignment.
+ * path (HOST, may be NULL): 1 if the launch handles four adjacent pixels per thread with 16-byte loads (out_W, every x0 and
+ *   w multiples of 4, every sw = 1, src 16-byte aligned with sc and sh multiples of 4, out 16-byte aligned (uint8: 4-byte
+ *   aligned with pitch a multiple of 4)), else 0.  Both paths give the same bytes.
+ * d3ga_frame_grid_check: the same tests and the same `path`, no launch (out is not read and may be any non-NULL address).
+ * ------------------------------------------------------------------------------------------------------- */
+#define D3GA_GRID_MAX_PANELS 16
+#define D3GA_GRID_MAX_LABEL 64
+#define D3GA_GRID_MAX_SIDE 32768
+#define D3GA_GRID_OUT_F32_CHW 0
+#define D3GA_GRID_OUT_F32_HWC 1
+#define D3GA_GRID_OUT_U8_SAVE_IMAGE 2
+#define D3GA_GRID_OUT_U8_CLIP 3
+#define D3GA_GRID_BGR 1
+#define D3GA_GRID_FORCE_SCALAR 2
+#define D3GA_PANEL_BOTTOM 1
+#define D3GA_PANEL_BOLD 2
+typedef struct d3ga_grid_panel {
+    const float *src;
+    const float *value; /* NULL unless the label has a "{:.3f}" */
+    int64_t sc, sh, sw;
+    int32_t C, h, w, y0, x0;
+    int32_t flags; /* D3GA_PANEL_* */
+    int32_t label_len;
+    int32_t X;
+    float color[3];
+    char label[D3GA_GRID_MAX_LABEL];
+} d3ga_grid_panel;
+typedef struct d3ga_grid_desc {
+    int32_t n_panels, out_H, out_W;
+    int32_t mode, channels, flags; /* D3GA_GRID_OUT_*, 3 | 4, D3GA_GRID_* */
+    float pad_value;
+    int32_t reserved;
+    int64_t pitch; /* bytes per output row of the uint8 modes */
+    d3ga_grid_panel panel[D3GA_GRID_MAX_PANELS];
+} d3ga_grid_desc;
+int d3ga_frame_grid_check(const d3ga_grid_desc *desc, const void *out, int32_t *path);
+int d3ga_frame_grid(const d3ga_grid_desc *desc, void *out, int32_t *path, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
