@@ -9,7 +9,7 @@ namespace d3ga {
 // Debug knobs of the compositing kernels (d3ga_debug_set; include/d3ga.h D3GA_KNOB_*; defaults in raster_api.hip):
 //   composite variant: bit 5 (32) work-ordered dispatch -- quadrants / tiles are handed out heaviest tile first (tile_order of
 //     the bin stage); bit 7 (128) exact ellipse / block-rectangle test behind the bounding-box test of the forward's culling;
-//   merge slots: slots of the backward's tile-level merge cache (256 | 512 | 1024);
+//   merge slots: slots of the backward's tile-level merge cache (256 | 512, the default: the two sizes the dispatch instantiates);
 //   tile assign: block -> wavefront assignment of the backward's tile kernel: 0 quadrants, 1 interleaved (blocks 8 px apart),
 //     2 by list length (the default: DESIGN.md sec. 4);
 //   bwd split: the heaviest tiles (in work order) get two workgroups each (raster_composite_scan.hip): -1 (default) = as many as

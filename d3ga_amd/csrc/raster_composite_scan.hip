@@ -10,7 +10,7 @@
 //     four pixels interleaved by hand), the pixel's running (T, S) carried from group to group in a 32-byte LDS record;
 //     dL/dalpha_i = T_i (c_i . g) - (S_i + T_final (bg . g)) / (1 - alpha_i): algebraically upstream's accum_rec recurrence;
 //   * every lane accumulates the nine moments of ITS entry over the 16 pixels in registers (no cross-lane reduction); the
-//     geometric ones as per-line constant-offset sums, centred once per group;
+//     geometric ones centred as they are summed (the pixels' own dx, the line's own dy);
 //   * the records of a tile's 16 blocks meet in a position-keyed MERGE CACHE in LDS (S slots of 12 dwords, slot =
 //     (position - 1) mod S; the tag word is the slot's lock, taken with ONE returning integer LDS atomic per attempt --
 //     float LDS atomics are 46x slower on this part) before one 64-byte accumulator line per (tile, Gaussian) leaves the CU
@@ -225,12 +225,15 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
         const bool act = e.pos != 0u;
         const float exr = e.xy.x - bxr, eyr = e.xy.y - byr;
         const ConicQ cq = conic_q(e.co.x, e.co.y, e.co.z);
-        // Geometric moments with the weight gop = o G dL/dalpha (dL/do = sum G dL/dalpha: divided by o once per entry) and the pixel
-        // offsets k = 0..3 of a block line as compile-time constants: per line  A = sum gop, B = sum k gop, C = sum k^2 gop
-        // (7 instructions for 4 pixels), accumulated as sums of A, B, C, ky A, ky B, ky^2 A; the centred moments follow at the
-        // end of the group from dx = exr - k, dy = eyr - ky:  sum gop dx = exr SA - SB,  sum gop dx^2 = exr^2 SA - 2 exr SB + SC, ...
-        // (3.5 instructions per pixel step instead of 9: w, wx, wy and six accumulations).
-        float SA = 0.f, SB = 0.f, SC = 0.f, TyA = 0.f, TyB = 0.f, TyyA = 0.f, M6 = 0.f, M7 = 0.f, M8 = 0.f, M9 = 0.f;
+        // Geometric moments with the weight gop = o G dL/dalpha (dL/do = sum G dL/dalpha: divided by o once per entry), CENTRED as they
+        // are summed: a block line adds  A = sum gop,  Bx = sum dx gop,  Cx = sum dx^2 gop  with the pixels' own dx = exr - k (and their
+        // squares, formed once per group), and the line's own dy = eyr - ky weighs them into sum dy A, sum dy Bx, sum dy^2 A.  Every
+        // sum is then a sum of its own terms and its rounding error is a few ulp of sum |terms|.  (Until this change the sums were
+        // taken about the block's origin with k, ky as immediates and centred at the end of the group -- exr^2 SA - 2 exr SB + SC --,
+        // six instructions per line fewer, but with an error of (offset of the centre from the block origin)^2 x sum gop whatever
+        // the moment's own size: for a splat half a pixel thin, dL/dconic.c came out 6e-4 of itself off, LOG "Compositing: every
+        // launch path under test".)
+        float SA = 0.f, M0 = 0.f, M1 = 0.f, M2 = 0.f, M3 = 0.f, M4 = 0.f, M6 = 0.f, M7 = 0.f, M8 = 0.f, M9 = 0.f;
 #if D3GA_TILE_PRIO
         {   // (the priority is an immediate)
             const int left = ngroups - g;
@@ -243,6 +246,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
         float dx[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) dx[k] = exr - (float)k;
+        const float dxx[4] = {dx[0] * dx[0], dx[1] * dx[1], dx[2] * dx[2], dx[3] * dx[3]};
         // The four block lines, unrolled (record offsets and k, ky are immediates; no loop bookkeeping).  Per pixel step:
         //   * one select: an invalid pair gets o G = 0, so alpha = 0 (r = 1) and the pair's weight Gr = o G r is 0 too --
         //     its gradient terms vanish through the products that are already there;
@@ -306,22 +310,15 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
                 *reinterpret_cast<float2 *>(wq + k * PIXF) = make_float2(Ti[k], Sin);
             }
             const float A = (gop[0] + gop[1]) + (gop[2] + gop[3]);
-            const float B = fmaf(3.0f, gop[3], fmaf(2.0f, gop[2], gop[1]));
-            const float C = fmaf(9.0f, gop[3], fmaf(4.0f, gop[2], gop[1]));
-            // (the lines are unrolled: the first one sets the sums, and the y moments are taken about the block's first line
-            // with ky, ky^2 as immediates -- sums of ky A, ky B, ky^2 A -- and centred at the end of the group like the x ones)
-            if (ky == 0) { SA = A; SB = B; SC = C; }
-            else { SA += A; SB += B; SC += C; }
-            if (ky == 1) { TyA = A; TyB = B; TyyA = A; }
-            if (ky >= 2) { TyA = fmaf((float)ky, A, TyA); TyB = fmaf((float)ky, B, TyB); TyyA = fmaf((float)(ky * ky), A, TyyA); }
+            const float Bx = fmaf(dx[3], gop[3], fmaf(dx[2], gop[2], fmaf(dx[1], gop[1], dx[0] * gop[0])));
+            const float Cx = fmaf(dxx[3], gop[3], fmaf(dxx[2], gop[2], fmaf(dxx[1], gop[1], dxx[0] * gop[0])));
+            const float dyy = dy * dy;
+            // (the lines are unrolled: the first one sets the sums)
+            if (ky == 0) { SA = A; M0 = Bx; M2 = Cx; M1 = dy * A; M3 = dy * Bx; M4 = dyy * A; }
+            else { SA += A; M0 += Bx; M2 += Cx; M1 = fmaf(dy, A, M1); M3 = fmaf(dy, Bx, M3); M4 = fmaf(dyy, A, M4); }
         }
-        // dy = eyr - ky:  sum dy A = eyr SA - sum ky A,  sum dy^2 A = eyr (eyr SA - 2 sum ky A) + sum ky^2 A
-        const float eSA = eyr * SA;
-        const float SyA = eSA - TyA, SyB = fmaf(eyr, SB, -TyB), SyyA = fmaf(eyr, fmaf(-2.0f, TyA, eSA), TyyA);
         // dL/do = sum G dL/dalpha = SA / o (a lane whose opacity is below 1/255 has no valid pair: SA = 0)
         const float M5 = SA * __builtin_amdgcn_rcpf(fmaxf(e.co.w, kAlphaMin));
-        const float M0 = exr * SA - SB, M1 = SyA;
-        const float M2 = exr * (exr * SA - 2.0f * SB) + SC, M3 = exr * SyA - SyB, M4 = SyyA;
         const float v0 = -(e.co.x * M0 + e.co.y * M1) * ddelx_dx;
         const float v1 = -(e.co.z * M1 + e.co.y * M0) * ddely_dy;
         const float4 va = make_float4(v0, v1, -0.5f * M2, -0.5f * M3), vb = make_float4(-0.5f * M4, M5, M6, M7);
@@ -333,7 +330,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
         // lock holder owns it; a loser discards them.  Stores + the releasing tag store likewise need no wait.
         const uint32_t saddr = (uint32_t)(uintptr_t)(lds_u32 *)(s_cache + ((e.pos - 1u) & (uint32_t)(S - 1)) * kSlot);
         // an entry that touched no pixel has nothing but (exact) zeros: it stays out of the cache
-        const uint32_t anybits = (__float_as_uint(SA) | __float_as_uint(SB) | __float_as_uint(SC)) | (__float_as_uint(TyA) | __float_as_uint(TyB) | __float_as_uint(TyyA)) |
+        const uint32_t anybits = (__float_as_uint(SA) | __float_as_uint(M0) | __float_as_uint(M2)) | (__float_as_uint(M1) | __float_as_uint(M3) | __float_as_uint(M4)) |
                                  (__float_as_uint(M6) | __float_as_uint(M7) | __float_as_uint(M8) | __float_as_uint(M9));
         bool pending = D3GA_SCAN_ABL == 1 ? (anybits == 0x12345u) : (D3GA_SCAN_ABL == 8 ? act : (anybits << 1) != 0u);
 #ifdef D3GA_DIAG_TIMELINE
@@ -401,7 +398,7 @@ __device__ __forceinline__ void bwd_tile_wave(const BwdArgs &A, const int tile, 
             const unsigned long long em = __builtin_amdgcn_ballot_w64(evi);
             if (em != 0ull) {
                 // wave-uniform and rare (the window of live positions exceeded S): the displaced records leave through the
-                // dump area, up to 24 at a time, nine consecutive lanes per record like every publish of this kernel
+                // dump area, up to 20 at a time, nine (INVD: ten) consecutive lanes per record like every publish of this kernel
                 const int rank = lanes_below(em), total = (int)__popcll(em);
                 for (int c0 = 0; c0 < total; c0 += 20) {
                     if (evi && rank >= c0 && rank < c0 + 20) {

@@ -467,7 +467,9 @@ int d3ga_raster_composite_bwd(const d3ga_raster_params *prm, const float *bg, co
 /* The same with the gradient of the inverse-depth image of branch dr_aa [UPSTREAM-RECALL]: dL_dinvdepth (H,W) | NULL, dL_dpix
  * (3,H,W) | NULL (at least one).  The inverse depth takes part as a fourth channel whose per-Gaussian "colour" is 1 / depth:
  * acc[10] receives dL/d(1/depth) = sum alpha T dL/dinvdepth, which d3ga_raster_preprocess_bwd chains into dL/dmeans3D
- * (always: the slot is zero otherwise). */
+ * (always: the slot is zero otherwise).  A batch of views (n_views = k > 1, with or without per_view_background, full rasters or
+ * windowed camera slots) takes dL_dinvdepth (k,H,W) next to dL_dpix (k,3,H,W): view v's plane is dL_dinvdepth + v H W, H x W the
+ * window of a windowed slot (tests/test_gpu_composite_paths.py holds all six batched / windowed launches to the oracle). */
 int d3ga_raster_composite_bwd_depth(const d3ga_raster_params *prm, const float *bg, const void *geom, const void *binning,
                                     int64_t d_capacity, const void *img, const float *dL_dpix, const float *dL_dinvdepth,
                                     float *acc, d3ga_stream_t stream);
