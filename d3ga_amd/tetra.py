@@ -101,12 +101,35 @@ def _grid_csr(lo_cells, hi_cells, dims):
     return start.int().contiguous(), item[order].int().contiguous()
 
 
+def _tet_grid(cor):
+    """The uniform grid `compute_bary` prunes with: cell edge ~ twice the mean tet box edge, at most 128 cells per axis, every tet
+    listed in the cells its (slightly inflated) box overlaps.  cor (T,4,3) float32, any device ->
+    (cell_start, cell_tets, origin_h, dims) as d3ga_compute_bary_grid takes them."""
+    import ctypes
+    lo, hi = cor.amin(1), cor.amax(1)                                       # (T,3) tet boxes
+    glo, ghi = lo.amin(0), hi.amax(0)
+    mean_edge = float((hi - lo).mean())
+    span = (ghi - glo).cpu()
+    h = max(2.0 * mean_edge, float(span.max()) / 128.0, 1e-12)
+    dims = [max(1, int(math.ceil(float(span[a]) / h)) + 1) for a in range(3)]
+    pad = 1e-5 * float(span.max()) + 1e-9                                   # a point ON a face is inside the inflated box
+    origin = (glo - pad).cpu()
+    o = origin.to(cor.device)
+    lo_c = ((lo - pad - o) / h).floor().long().clamp_min(0)
+    hi_c = ((hi + pad - o) / h).floor().long()
+    hi_c = torch.minimum(hi_c, torch.tensor([d - 1 for d in dims], device=cor.device))
+    cell_start, cell_tets = _grid_csr(lo_c, hi_c, dims)
+    origin_h = (ctypes.c_float * 4)(float(origin[0]), float(origin[1]), float(origin[2]), h)
+    return cell_start, cell_tets, origin_h, (ctypes.c_int32 * 3)(*dims)
+
+
 def compute_bary(points, tetras, triangles=None, tri_to_tetra=None, cage=None, method="grid"):
     """(points (P,3), tetras (T,4,3) corner coordinates, ...) -> (barys (P,4) f32, tetra_id (P,) int64, active (P,) bool).
     `triangles`, `tri_to_tetra` and `cage` are accepted for signature compatibility (lib/cage.py:325-327).
     method="grid" (default): a uniform grid over the cage prunes the candidates of every point to the tets whose bounding
     boxes overlap its cell; the few points no candidate contains (outside the cage) go through the exhaustive search, so
-    the result equals method="exhaustive" (O(P T)) bit for bit."""
+    the result equals method="exhaustive" (O(P T)) bit for bit.  A tet of zero volume is never chosen, and a point with a
+    coordinate that is not finite gets (0, 0, False) (csrc/bary_math.h)."""
     require_cuda(points, tetras)
     pts = points.detach().float().contiguous()
     cor = tetras.detach().float().contiguous()
@@ -119,23 +142,7 @@ def compute_bary(points, tetras, triangles=None, tri_to_tetra=None, cage=None, m
         check(L.d3ga_compute_bary(P, T, dptr(pts), dptr(cor), dptr(barys), dptr(tid), dptr(act), stream_handle()),
               "d3ga_compute_bary")
         return barys, tid.long(), act.bool()
-    # grid over the cage: cell edge ~ twice the mean tet box edge, at most 128 cells per axis
-    lo, hi = cor.amin(1), cor.amax(1)                                       # (T,3) tet boxes
-    glo, ghi = lo.amin(0), hi.amax(0)
-    mean_edge = float((hi - lo).mean())
-    span = (ghi - glo).cpu()
-    h = max(2.0 * mean_edge, float(span.max()) / 128.0, 1e-12)
-    dims = [max(1, int(math.ceil(float(span[a]) / h)) + 1) for a in range(3)]
-    pad = 1e-5 * float(span.max()) + 1e-9                                   # a point ON a face is inside the inflated box
-    origin = (glo - pad).cpu()
-    o = origin.to(pts.device)
-    lo_c = ((lo - pad - o) / h).floor().long().clamp_min(0)
-    hi_c = ((hi + pad - o) / h).floor().long()
-    hi_c = torch.minimum(hi_c, torch.tensor([d - 1 for d in dims], device=pts.device))
-    cell_start, cell_tets = _grid_csr(lo_c, hi_c, dims)
-    import ctypes
-    origin_h = (ctypes.c_float * 4)(float(origin[0]), float(origin[1]), float(origin[2]), h)
-    cdims = (ctypes.c_int32 * 3)(*dims)
+    cell_start, cell_tets, origin_h, cdims = _tet_grid(cor)
     minw = torch.empty((P,), dtype=torch.float32, device=pts.device)
     check(L.d3ga_compute_bary_grid(P, dptr(pts), dptr(cor), dptr(cell_start), dptr(cell_tets), origin_h, cdims, dptr(barys),
                                    dptr(tid), dptr(minw), stream_handle()), "d3ga_compute_bary_grid")
@@ -154,30 +161,45 @@ def compute_bary(points, tetras, triangles=None, tri_to_tetra=None, cage=None, m
     return barys, tid.long(), act
 
 
+KNN3_GRID_FROM = 2048        # knn_mean_dist2, method="grid": points from which the grid search is taken
+
+
+def _point_grid(pts):
+    """The uniform grid `knn_mean_dist2` buckets its points into (~4 per cell, at most ~256 cells per axis).  pts (P,3) float32,
+    any device -> (cell_start, cell_points, origin_h, dims) as d3ga_knn3_mean_dist2_grid takes them."""
+    import ctypes
+    glo, ghi = pts.amin(0), pts.amax(0)
+    box = torch.stack([glo, ghi]).cpu()                                     # the one host read of this path
+    if not bool(torch.isfinite(box).all()):
+        raise ValueError("knn_mean_dist2: points hold coordinates that are not finite")
+    span = box[1] - box[0]
+    P = pts.shape[0]
+    vol = float(torch.clamp(span, min=1e-9).prod())
+    h = max((vol / (P / 4.0)) ** (1.0 / 3.0), float(span.max()) / 256.0, 1e-12)
+    dims = [max(1, int(math.ceil(float(span[a]) / h)) + 1) for a in range(3)]
+    c = ((pts - glo) / h).floor().long()
+    c = torch.minimum(c.clamp_min(0), torch.tensor([d - 1 for d in dims], device=pts.device))
+    cell_start, cell_points = _grid_csr(c, c, dims)
+    origin_h = (ctypes.c_float * 4)(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h)
+    return cell_start, cell_points, origin_h, (ctypes.c_int32 * 3)(*dims)
+
+
 def knn_mean_dist2(points, method="grid"):
     """(P,3) -> (P,) mean squared distance to the 3 nearest neighbours: `simple_knn._C.distCUDA2(points)`
-    (models/mesh_net.py:66) == `knn_points(p[None], p[None], K=4)[0][0, :, 1:].mean(-1)` (models/cage_net.py:66).
-    method="grid" (default): points bucketed into a uniform grid (~4 per cell), exact ring search; "exhaustive": O(P^2)."""
+    (models/mesh_net.py:66) == `knn_points(p[None], p[None], K=4)[0][0, :, 1:].mean(-1)` (models/cage_net.py:66): the same
+    squared distances as `d3ga_amd.knn.knn_points`, the mean as ((d0 + d1) + d2) / 3 -- within 2 float32 ulps of torch's mean.
+    method="grid" (default): points bucketed into a uniform grid (~4 per cell), exact ring search; "exhaustive": O(P^2).
+    The grid search (taken from 2048 points) raises ValueError for coordinates that are not finite; below that the exhaustive
+    kernel gives such a row 0 and leaves every other row as it would be without it."""
     require_cuda(points)
     pts = points.detach().float().contiguous()
     P = pts.shape[0]
     out = torch.empty((P,), dtype=torch.float32, device=pts.device)
     L = _lib.lib()
-    if method == "exhaustive" or P < 2048:
+    if method == "exhaustive" or P < KNN3_GRID_FROM:
         check(L.d3ga_knn3_mean_dist2(P, dptr(pts), dptr(out), stream_handle()), "d3ga_knn3_mean_dist2")
         return out
-    glo, ghi = pts.amin(0), pts.amax(0)
-    span = (ghi - glo).cpu()
-    vol = float(torch.clamp(span, min=1e-9).prod())
-    h = max((vol / (P / 4.0)) ** (1.0 / 3.0), float(span.max()) / 256.0, 1e-12)
-    dims = [max(1, int(math.ceil(float(span[a]) / h)) + 1) for a in range(3)]
-    origin = glo.cpu()
-    c = ((pts - glo) / h).floor().long()
-    c = torch.minimum(c.clamp_min(0), torch.tensor([d - 1 for d in dims], device=pts.device))
-    cell_start, cell_points = _grid_csr(c, c, dims)
-    import ctypes
-    origin_h = (ctypes.c_float * 4)(float(origin[0]), float(origin[1]), float(origin[2]), h)
-    cdims = (ctypes.c_int32 * 3)(*dims)
+    cell_start, cell_points, origin_h, cdims = _point_grid(pts)
     check(L.d3ga_knn3_mean_dist2_grid(P, dptr(pts), dptr(cell_start), dptr(cell_points), origin_h, cdims, dptr(out),
                                       stream_handle()), "d3ga_knn3_mean_dist2_grid")
     return out

@@ -949,6 +949,10 @@ int d3ga_selftest_row_scan(int n, const float *in, float *out, d3ga_stream_t str
 int d3ga_selftest_alpha(int32_t P, const void *geom, int n, const int32_t *gid, const int32_t *px, const int32_t *py,
                         uint8_t *ok, float *alpha, d3ga_stream_t stream);
 
+/* Init-time point location: for each of P points the tet (of T, corners (T,4,3)) with the largest minimum barycentric weight,
+ * the lowest index among equals (csrc/bary_math.h); active = that minimum >= 0.  A tet whose volume evaluates to 0 or whose
+ * weights are not finite is never chosen; if none can be, the row is (0, 0, 0).  barys (P,4) is stored 16 bytes at a time:
+ * D3GA_E_CONFIG unless it is 16-byte aligned (d3ga_compute_bary_grid as well). */
 int d3ga_compute_bary(int P, int T, const float *points, const float *tetra_corners, float *barys,
                       int32_t *tetra_id, uint8_t *active, d3ga_stream_t stream);
 
@@ -963,7 +967,8 @@ int d3ga_compute_bary_grid(int P, const float *points, const float *tetra_corner
 /* Init-time scale seed.  Replaces simple_knn._C.distCUDA2 (models/mesh_net.py:22,66) and
  * pytorch3d knn_points(p, p, K=4)[0][0,:,1:].mean(-1) (models/cage_net.py:66): out[i] = mean squared distance of
  * point i to its 3 nearest other points (sum / 3; missing neighbours count as 0, like pytorch3d's padding).  points (P,3) -> out (P).
- * Exhaustive O(P^2). */
+ * The squared distance is d3ga_knn_points' (csrc/knn_math.h: knn_dist2), so the two forms agree up to the rounding of the mean.
+ * A point with a coordinate that is not finite gets 0 and is nobody's neighbour.  Exhaustive O(P^2). */
 int d3ga_knn3_mean_dist2(int P, const float *points, float *out, d3ga_stream_t stream);
 /* The same with a uniform grid over the points (cell_start / cell_points: CSR of point indices per cell; origin_h, dims as
  * above, HOST arrays): ring search outwards from the point's cell, exact. */

@@ -40,14 +40,17 @@ def point_in_tet(v1, v2, v3, v4, p):
             & same_side(v4, v1, v2, v3, p))
 
 
-def compute_bary(points, corners, chunk=256):
-    """points (P,3), corners (T,4,3) -> barys (P,4), tetra_id (P,), active (P,) [inside some tet]."""
+def compute_bary(points, corners, chunk=256, margins=False):
+    """points (P,3), corners (T,4,3) -> barys (P,4), tetra_id (P,), active (P,) [inside some tet].
+    margins=True appends (m1, m2): the winner's minimum weight and the best minimum weight among the OTHER tets (-inf if there
+    is none) -- m1 - m2 says how firmly the winner won, |m1| how firmly `active` is decided."""
     points = np.asarray(points, np.float64)
     corners = np.asarray(corners, np.float64)
     P = points.shape[0]
     barys = np.zeros((P, 4))
     tid = np.zeros(P, np.int64)
     best = np.full(P, -np.inf)
+    second = np.full(P, -np.inf)
     a, b, c, d = (corners[None, :, k] for k in range(4))
     for s in range(0, P, chunk):
         p = points[s:s + chunk, None, :]
@@ -58,4 +61,16 @@ def compute_bary(points, corners, chunk=256):
         barys[s:s + chunk] = w[r, j]
         tid[s:s + chunk] = j
         best[s:s + chunk] = mn[r, j]
+        if margins:
+            mn[r, j] = -np.inf
+            second[s:s + chunk] = mn.max(1)
+    if margins:
+        return barys, tid, best >= 0, best, second
     return barys, tid, best >= 0
+
+
+def min_weight(points, corners, tetra_id):
+    """The float64 weights (P,4) and minimum weight (P,) of point i in the tet tetra_id[i]."""
+    c = np.asarray(corners, np.float64)[np.asarray(tetra_id)]
+    w = barycentric(c[:, 0], c[:, 1], c[:, 2], c[:, 3], np.asarray(points, np.float64))
+    return w, w.min(-1)

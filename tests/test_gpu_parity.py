@@ -1364,10 +1364,7 @@ def test_init_helpers_fuzz(seed):
         d.fill_diagonal_(float("inf"))
         k = min(3, n - 1)
         ref = d.topk(k, largest=False).values.sum(1) / 3.0 if k < 3 else d.topk(3, largest=False).values.mean(1)
-        if k == 3:
-            np.testing.assert_allclose(_np(out), ref.numpy(), rtol=1e-4, atol=1e-7)
-        else:
-            assert bool(torch.isfinite(out).all())
+        np.testing.assert_allclose(_np(out), ref.numpy(), rtol=1e-4, atol=1e-7)     # k < 3: the sum of what exists, over three
     # compute_bary: points generated INSIDE random (well-shaped) tets reconstruct from the returned tet and weights
     T = int(rng.choice([1, 2, 255, 256, 257, int(rng.integers(1, 2000))]))
     base = torch.randn(T, 1, 3, generator=g) * 3.0
