@@ -31,7 +31,9 @@ DEFAULT_COLOR = np.array([154.0, 205.0, 50.0]) / 255.0
 # pointcheck.cpp) from this oracle on the non-marginal pixels of ALL cases below, rounded up to two digits
 # (tests/test_point_render_host.py::test_host_build_equals_the_oracle prints the measured values and holds the host build to
 # bar / 8).  zbuf relative to the depth, dists relative to radius^2 (so both are dimensionless), image in colour units.
-MEASURED = {"zbuf_rel": 9.2e-8, "dists": 1.8e-5, "image": 1.3e-5}
+# image was 1.3e-5 (the 0.6-pixel discs) until the 256-pixel frames came: tiles256 measures 1.64e-5 there (its dists 1.65e-5: u
+# and v near 250 carry twice the rounding error they carry in a 90-pixel frame), tiles272 1.36e-5.  The other two are unchanged.
+MEASURED = {"zbuf_rel": 9.2e-8, "dists": 1.8e-5, "image": 1.7e-5}
 BARS = {k: 8 * v for k, v in MEASURED.items()}
 
 
@@ -107,11 +109,55 @@ def make_case(name):
         pts = np.stack([shell(1000, 41), solid(1000, 42), shell(1000, 43)])
         cams = np.stack([camera(37, 53, 3.0, d) for d in ((0.3, 0.4, -1.0), (-1.0, 0.1, 0.3), (0.1, -0.8, 0.7))])
         return dict(points=pts, cams=cams, H=37, W=53, radius=radius_of(2.6, 37, 53), K=5)
+    if name in ("k2", "k3", "k4", "k6", "k7"):                # every instantiation of the tile kernel: k8's cloud and camera
+        return _one(solid(3000, 32), camera(70, 90), 70, 90, 2.6, K=int(name[1]))
+    # The tile table is built in workgroups of 256 tiles (TABLE_BLOCK): a tile's list begins at block_start[t / 256] + local[t]
+    # and ends where tile t + 1's begins, or at block_start[nblk] behind the very last padded slot.
+    if name == "tiles256":                                    # 16 x 16 tiles: one full table workgroup, the last tile ends at block_start[nblk]
+        return _one(shell(6000, 51), camera(256, 256), 256, 256, 2.6)
+    if name == "tiles272":                                    # 17 x 16 tiles: two table workgroups, tile 255 ends where the second begins
+        return _one(shell(6000, 52), camera(272, 256), 272, 256, 2.6)
+    if name == "views3_330":                                  # 3 views of 10 x 11 tiles: the table boundary (tile 256) inside view 2,
+        pts = np.stack([shell(3000, 61), solid(3000, 62), shell(3000, 63)])                    # the view boundaries inside workgroup 0
+        cams = np.stack([camera(160, 176, 3.0, d) for d in ((0.3, 0.4, -1.0), (-1.0, 0.1, 0.3), (0.1, -0.8, 0.7))])
+        return dict(points=pts, cams=cams, H=160, W=176, radius=radius_of(2.6, 160, 176), K=5)
+    if name == "views257":                                    # 257 views of one tile each: the second table workgroup holds one tile
+        dirs = np.random.default_rng(99).standard_normal((257, 3))
+        pts = np.stack([shell(40, 100 + b) for b in range(257)])
+        cams = np.stack([camera(16, 16, 3.0, d) for d in dirs])
+        return dict(points=pts, cams=cams, H=16, W=16, radius=radius_of(1.5, 16, 16), K=5)
+    # Not in CASES (no full oracle: tests/test_gpu_point_render.py::test_a_quarter_million_one_pixel_views samples them).
+    if name == "pixels262400":                                # 262 400 views of one pixel: 1025 table workgroups (the scan kernel's second
+        B, P = PIXEL_VIEWS, 4                                 # trip, with a carry), four to five grid-stride trips of the tile kernel
+        rng = np.random.default_rng(71)
+        pts = (PIXEL_SPREAD * rng.standard_normal((B, P, 3))).astype(np.float32)
+        cams = np.repeat(camera(1, 1, fill=0.6)[None], B, 0)
+        cams[:, 14] += rng.uniform(-0.3, 0.3, B).astype(np.float32)
+        return dict(points=pts, cams=cams, H=1, W=1, radius=radius_of(0.6, 1, 1), K=5)
+    if name == "views257_k1":                                 # 257 x 256 = 65 792 tiles: 256 tile workgroups make a second trip
+        rng = np.random.default_rng(72)
+        dirs = rng.standard_normal((257, 3))
+        d = rng.standard_normal((257, 200, 3))
+        pts = (d / np.linalg.norm(d, axis=2, keepdims=True)).astype(np.float32)
+        cams = np.stack([camera(256, 256, 3.0, d) for d in dirs])
+        return dict(points=pts, cams=cams, H=256, W=256, radius=radius_of(2.6, 256, 256), K=1)
     raise KeyError(name)
 
 
+TABLE_BLOCK = 256            # tiles per workgroup of the tile table (kBlock of csrc/point_raster.hip)
+PIXEL_VIEWS = 1025 * 256     # more table workgroups than one trip of the scan kernel (1024), more tiles than tile workgroups (65 536)
+# sigma of the one-pixel views' clouds: between a quarter and three quarters of the views have their pixel covered
+# (tests/test_point_render_host.py::test_the_one_pixel_views_are_half_covered measures it with the host build)
+PIXEL_SPREAD = 2.0
+
 CASES = ("shell_70x90", "shell_90x70", "solid_70x90", "solid_90x70", "dense6000", "wide_discs", "wider_discs", "narrow_discs", "duplicates",
-         "behind_and_outside", "k1", "k8", "one_point", "batch3")
+         "behind_and_outside", "k1", "k8", "one_point", "batch3", "tiles256", "tiles272", "views3_330", "views257", "k2", "k3", "k4", "k6",
+         "k7")
+
+
+def n_tiles(case):
+    """tiles of a case, all views"""
+    return len(case["points"]) * ((case["H"] + 15) // 16) * ((case["W"] + 15) // 16)
 
 
 def point_colours(case, seed=3):
@@ -195,9 +241,9 @@ def composite_ref(idx, dists, radius, colors=None, white=True):
 class Reference:
     """The oracle's results of one case, element by element, and the checks the host build and the device share."""
 
-    def __init__(self, name):
+    def __init__(self, name, case=None):
         self.name = name
-        self.case = c = make_case(name)
+        self.case = c = make_case(name) if case is None else case
         self.B, self.P = c["points"].shape[:2]
         self.H, self.W, self.K, self.radius = c["H"], c["W"], c["K"], c["radius"]
         self.colours = point_colours(c)
@@ -255,6 +301,27 @@ def reference(name):
     return _REFS[name]
 
 
+def sampled_reference(name, every):
+    """-> (views, the oracle of every `every`-th view of a case too large for a full one), computed once per process."""
+    key = (name, every)
+    if key not in _REFS:
+        c = make_case(name)
+        views = np.arange(0, len(c["points"]), every)
+        _REFS[key] = (views, Reference(f"{name}[::{every}]", dict(c, points=c["points"][views], cams=c["cams"][views])))
+    return _REFS[key]
+
+
+_CASES = {}
+
+
+def big_case(name, values=True):
+    """make_case of one of the cases outside CASES with the host build's fragments (idx, zbuf, dists), once per process."""
+    if name not in _CASES:
+        c = make_case(name)
+        _CASES[name] = (c,) + host_fragments(c, values=values)[:3]
+    return _CASES[name]
+
+
 # ---- the host build -----------------------------------------------------------------------------------------------------
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 _HOST = []
@@ -281,14 +348,15 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def host_fragments(case, reversed_lists=False):
-    """The host build's fragments of a case -> (idx, zbuf, dists, the longest tile list)"""
+def host_fragments(case, reversed_lists=False, values=True):
+    """The host build's fragments of a case -> (idx, zbuf, dists, the longest tile list); values=False: idx alone, zbuf and
+    dists are None"""
     lib = host_lib()
     B, P = case["points"].shape[:2]
     H, W, K = case["H"], case["W"], case["K"]
     pts, cams = np.ascontiguousarray(case["points"]), np.ascontiguousarray(case["cams"])
     idx = np.full((B, H, W, K), -7, np.int32)
-    zbuf, dists = np.full((B, H, W, K), np.nan, np.float32), np.full((B, H, W, K), np.nan, np.float32)
+    zbuf, dists = (np.full((B, H, W, K), np.nan, np.float32), np.full((B, H, W, K), np.nan, np.float32)) if values else (None, None)
     longest = lib.hc_points_rasterize(B, P, H, W, K, ctypes.c_float(case["radius"]), _ptr(pts), _ptr(cams), int(reversed_lists), _ptr(idx),
                                       _ptr(zbuf), _ptr(dists))
     assert longest >= 0, longest

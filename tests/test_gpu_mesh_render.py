@@ -2,7 +2,9 @@
 (tests/mesh_ref.py), at the smallest shapes at which each mechanism can go wrong (mesh_ref.CASES): single triangles of both
 windings as face 0 and as face 1 (the mask quirk), two interpenetrating triangles, a triangle larger than the frame (clamped
 box, 15 chunks), triangles hanging off the four sides, a 1 x 1 and a 3 x 200 image, faces that must vanish (behind the near
-plane, zero area), bumpy spheres from 64 to 20000 faces (sub-pixel triangles, many faces per pixel), B = 3.
+plane, zero area), bumpy spheres from 64 to 20000 faces (sub-pixel triangles, many faces per pixel), B = 3; 53 spheres of
+20000 faces (more setup workgroups than one trip of the scan kernel and than two levels of the coverage kernel's search), and
+faces that name vertices outside the mesh, given to the raw entry points.
 
 pix_to_face equals the oracle's exactly away from the marginal pixels (|min b| < 1e-4 for some face whose box holds the pixel,
 or the two nearest depths within 1e-5 zbuf; at most 2 % of the covered pixels of a case, tests/test_mesh_render_host.py holds
@@ -268,3 +270,130 @@ def test_captured_render_and_maps_follow_their_vertices():
     assert torch.equal(out[0], eager[1][0])
     for a, b in zip(out[1], eager[1][1]):
         assert torch.equal(a, b)
+
+
+def test_batch_of_53_spheres_equals_its_single_calls():
+    """53 x 20 000 faces are 4141 setup workgroups: mesh_scan_kernel makes five trips of 1024 (each carries the total of those
+    before it) and the 64-ary ballot search of mesh_coverage_kernel takes three levels (4141 -> 65 -> 2 -> 1); sphere20000 alone
+    has 79 workgroups, one trip and two levels.  Every element must equal its own single call bit for bit."""
+    from d3ga_amd import MeshCameras, Renderer, rasterize_meshes
+    from d3ga_amd.mesh_render import MeshTopology
+    ref = mr.reference("sphere20000")
+    B, H, W = 53, ref.H, ref.W
+    assert (B * ref.F + 255) // 256 == 4141 > 4 * 1024 and 4141 > 64 * 64
+    dirs = np.random.default_rng(53).standard_normal((B, 3))
+    rows = np.stack([ref.case["cams"][0]] + [mr._sphere_cam(H, W, 2.5, d) for d in dirs[1:]])
+    cam = rows.astype(np.float64)
+    K = np.zeros((B, 3, 3))
+    K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = cam[:, 12], cam[:, 13], cam[:, 14], cam[:, 15], 1
+    cams = MeshCameras(cam[:, :9].reshape(-1, 3, 3), cam[:, 9:12], K, (H, W))
+    assert np.array_equal(cams.data.cpu().numpy(), rows)
+    one_v = torch.from_numpy(ref.case["verts"]).to(DEV)
+    verts = one_v.expand(B, -1, -1).contiguous()
+    topo = MeshTopology(torch.from_numpy(ref.case["faces"]))
+    r = Renderer()
+    frag, image, maps = rasterize_meshes(cams, verts, topo), r.render(cams, verts, topo), r.maps(cams, verts, topo)
+    frag = [t.clone() for t in frag]
+    dev = ref.check_fragments(*[t[:1] for t in _np(*frag)])                   # element 0 is sphere20000 itself
+    print("batch of 53, element 0: " + " ".join(f"{k} {v:.2e}" for k, v in sorted(dev.items())))
+    _within(dev)
+    covered = (frag[0] >= 0).reshape(B, -1).sum(1)
+    assert int(covered.min()) > 0.2 * H * W                                    # every camera sees the sphere
+    for b in range(B):
+        one = MeshCameras(cam[b, :9].reshape(3, 3), cam[b, 9:12], K[b], (H, W))
+        assert torch.equal(one.data[0], cams.data[b])
+        for a, w in zip(rasterize_meshes(one, one_v, topo), frag):
+            assert torch.equal(a[0], w[b]), b
+        assert torch.equal(r(one, one_v, topo), image[b]), b
+        for a, w in zip(r.map(one, one_v, topo), maps):
+            assert torch.equal(a, w[b]), b
+    assert len({frag[0][b].cpu().numpy().tobytes() for b in range(B)}) == B    # 53 different views
+
+
+def test_faces_naming_vertices_outside_the_mesh_are_dropped_on_the_device():
+    """The Python layer refuses such faces, so only the raw entry points can reach the kernels' own guard.  Four faces that name
+    vertex V, V + 1, -1 and -2 at positions 0, 1, the middle and the end of sphere64's face list must do what zero-area faces in
+    their places do: nothing.  The bad indices stay within the guard bands of the vertex buffers (64 words = 21 vertices each
+    side), so a guard that did not hold would read the band's pattern, not foreign memory."""
+    from d3ga_amd import _lib
+    L = _lib.lib()
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    ref = mr.reference("sphere64")
+    cams, verts, _ = _setup(ref)
+    B, V, H, W = 1, ref.V, ref.H, ref.W
+    base = ref.case["faces"]
+    bad = np.array([[V, 1, 2], [3, V + 1, 4], [5, 6, -1], [-2, 7, 8]], np.int32)
+    where = (0, 1, len(base) // 2 + 2, len(base) + 3)                          # positions in the list of F + 4
+    F = len(base) + 4
+    keep = np.ones(F, bool)
+    keep[list(where)] = False
+    with_bad, with_zero = np.zeros((F, 3), np.int32), np.zeros((F, 3), np.int32)
+    with_bad[keep], with_zero[keep] = base, base
+    with_bad[~keep] = bad
+    assert where == (0, 1, 34, 67) and ((with_bad < 0) | (with_bad >= V)).sum() == 4 and with_bad.min() == -2 and with_bad.max() == V + 1
+    assert 3 * 2 <= GUARD                                                      # the farthest word a broken guard would read: 6 off either end
+
+    def guarded(bufs, key, shape, dtype=torch.float32):
+        count = int(np.prod(shape))
+        raw = torch.full((count + 2 * GUARD,), NAN_BITS, dtype=torch.int32, device=DEV)
+        bufs[key] = raw
+        return raw[GUARD:GUARD + count].view(dtype).view(shape)
+
+    # The bands of the vertex buffer hold, word for word, the coordinates of a point half way between the camera and the sphere
+    # (as vertices -21 .. -1 and V .. V + 20 would): a guard that did not hold would draw a triangle in front of everything.
+    cam = ref.case["cams"][0].astype(np.float64)
+    eye = -cam[:9].reshape(3, 3).T @ cam[9:12]
+    lure = torch.tensor(0.6 * eye, dtype=torch.float32, device=DEV)
+    vraw = lure[(torch.arange(3 * V + 2 * GUARD, device=DEV) - GUARD) % 3].contiguous()
+    band = (vraw[:GUARD].clone(), vraw[-GUARD:].clone())
+    gv = vraw[GUARD:-GUARD].view(B, V, 3)
+    gv.copy_(verts)
+    inputs = {}
+    normals = guarded(inputs, "normals", (B, V, 3))
+    s = _lib.stream_handle()
+    # d3ga_mesh_vertex_normals reads faces through a CSR that only valid faces can build: the normals come from the oracle
+    normals.copy_(torch.from_numpy(mr.vertex_normals_ref(ref.case["verts"][0], base).astype(np.float32))[None])
+    n = ctypes.c_size_t()
+    assert L.d3ga_mesh_raster_scratch_bytes(B, V, F, H, W, ctypes.byref(n)) == 0
+    bg = (ctypes.c_float * 3)(1, 1, 1)
+    results = []
+    for faces_np in (with_zero, with_bad):
+        faces = torch.from_numpy(faces_np).to(DEV)
+        bufs = {}
+        scratch = guarded(bufs, "scratch", ((n.value + 3) // 4,), torch.int32)
+        pix, zbuf, bary = guarded(bufs, "pix", (B, H, W), torch.int32), guarded(bufs, "zbuf", (B, H, W)), guarded(bufs, "bary", (B, H, W, 3))
+        image = guarded(bufs, "image", (B, H, W, 3))
+        pos, nrm, depth, mask = (guarded(bufs, k, (B, H, W, c)) for k, c in (("pos", 3), ("nrm", 3), ("depth", 1), ("mask", 1)))
+        assert L.d3ga_mesh_rasterize(B, V, F, H, W, p(gv), p(faces), p(cams.data), p(scratch), p(pix), p(zbuf), p(bary), s) == 0
+        assert L.d3ga_mesh_shade_flat(B, V, F, H, W, p(gv), p(faces), None, p(cams.data), p(pix), p(bary), bg, p(image), s) == 0
+        assert L.d3ga_mesh_maps(B, V, F, H, W, p(gv), p(faces), p(normals), p(cams.data), p(pix), p(bary), p(pos), p(nrm), p(depth), p(mask), s) == 0
+        torch.cuda.synchronize()
+        for key, raw in list(bufs.items()) + list(inputs.items()):
+            assert (raw[:GUARD] == NAN_BITS).all() and (raw[-GUARD:] == NAN_BITS).all(), key
+            if key != "scratch":
+                assert not (raw[GUARD:-GUARD] == NAN_BITS).any(), key
+        results.append((pix, zbuf, bary, image, pos, nrm, depth, mask))
+    for key, a, b in zip(("pix", "zbuf", "bary", "image", "pos", "nrm", "depth", "mask"), *results):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), key     # bit for bit
+    pix = results[1][0].cpu().numpy()
+    assert not np.isin(pix, where).any() and (pix >= 0).sum() > 100
+    # the faces in between keep their numbers: the oracle's fragments of sphere64, shifted by the faces inserted before them
+    shift = np.cumsum(~keep)[keep]
+    want = ref.frag[0]["pix_to_face"]
+    m = ~ref.frag[0]["marginal"]
+    renumbered = np.where(want >= 0, want + shift[np.maximum(want, 0)], -1)
+    assert np.array_equal(pix[0][m], renumbered[m])
+    # a fragment list that names the four faces all the same: the shade and map kernels have the guard too
+    named = torch.from_numpy(np.resize(np.array(where, np.int32), (B, H, W))).to(DEV)
+    bufs = {}
+    image, pos, nrm, depth, mask = (guarded(bufs, k, (B, H, W, c)) for k, c in (("image", 3), ("pos", 3), ("nrm", 3), ("depth", 1), ("mask", 1)))
+    faces = torch.from_numpy(with_bad).to(DEV)
+    bary = torch.full((B, H, W, 3), 1 / 3, device=DEV)
+    assert L.d3ga_mesh_shade_flat(B, V, F, H, W, p(gv), p(faces), None, p(cams.data), p(named), p(bary), bg, p(image), s) == 0
+    assert L.d3ga_mesh_maps(B, V, F, H, W, p(gv), p(faces), p(normals), p(cams.data), p(named), p(bary), p(pos), p(nrm), p(depth), p(mask), s) == 0
+    torch.cuda.synchronize()
+    for key, raw in bufs.items():
+        assert (raw[:GUARD] == NAN_BITS).all() and (raw[-GUARD:] == NAN_BITS).all(), key
+    assert torch.equal(vraw[:GUARD], band[0]) and torch.equal(vraw[-GUARD:], band[1]) and torch.equal(gv, verts)
+    assert (image == 1).all() and (pos == 0).all() and (nrm == 0).all() and (depth == 0).all()
+    assert torch.equal(mask[..., 0], (named > 0).float())

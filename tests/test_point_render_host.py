@@ -175,6 +175,46 @@ def test_host_build_equals_the_oracle(name):
         assert twins > 200 and (a[pair] < b[pair]).all() and (pair.any(-1) & ~f["marginal"]).sum() > 100
 
 
+def test_the_table_cases_have_the_tile_counts_they_are_named_for():
+    """The tile table of csrc/point_raster.hip is built in workgroups of 256 tiles: one full workgroup, two, a boundary inside a
+    view, a second workgroup of one tile; then more workgroups than one trip of its scan kernel and more tiles than the tile
+    kernel has workgroups."""
+    want = {"tiles256": 256, "tiles272": 272, "views3_330": 330, "views257": 257, "pixels262400": 262400, "views257_k1": 65792}
+    for name, tiles in want.items():
+        c = pr.make_case(name)
+        assert pr.n_tiles(c) == tiles and (name in pr.CASES) == (tiles < 1000), name
+    assert pr.TABLE_BLOCK == 256 and 262400 == 1025 * pr.TABLE_BLOCK and 65792 == 65536 + 256
+    assert sorted(pr.make_case(n)["K"] for n in pr.CASES if n[0] == "k" or n == "solid_70x90") == list(range(1, 9))       # every points_tile_kernel<K>
+
+
+def test_the_one_pixel_views_are_half_covered_and_the_host_build_equals_the_oracle_on_every_997th():
+    c, idx, zbuf, dists = pr.big_case("pixels262400")
+    assert idx.shape == (262400, 1, 1, 5) and c["points"].shape == (262400, 4, 3)
+    covered = float((idx[..., 0] >= 0).mean())
+    print(f"pixels262400: {covered * 100:.1f} % of the views covered, {float((idx[..., 1] >= 0).mean()) * 100:.1f} % by two points or more")
+    assert 0.25 <= covered <= 0.75
+    assert (idx[..., 4] == -1).all() and (idx[..., 3] >= 0).any()                          # P = 4: slot 4 stays empty, slot 3 does not
+    views, ref = pr.sampled_reference("pixels262400", 997)
+    assert len(views) == 264 and views[-1] == 262211
+    share, n = ref.marginal_share()
+    dev = ref.check_fragments(idx[views], zbuf[views], dists[views])
+    print(f"pixels262400[::997]: {share * 100:.2f} % of {n} covered pixels are marginal " + " ".join(f"{k} {v:.2e}" for k, v in sorted(dev.items())))
+    assert 0.25 * len(views) <= n <= 0.75 * len(views) and share <= pr.MARGINAL_CAP
+    for k, v in dev.items():
+        assert 8 * v <= pr.BARS[k], (k, v)
+
+
+def test_the_second_trip_of_the_tile_kernel_meets_covered_tiles():
+    """views257_k1: the tiles past 65 536 are the last view's; its pixels must not all be background."""
+    c, idx, _, _ = pr.big_case("views257_k1", values=False)
+    assert idx.shape == (257, 256, 256, 1) and ((idx >= -1) & (idx < 200)).all()
+    per_view = (idx[..., 0] >= 0).reshape(257, -1).sum(1)
+    print(f"views257_k1: {int(per_view.min())} .. {int(per_view.max())} covered pixels per view, {int(per_view[-1])} in the last")
+    assert per_view.min() > 500
+    tiles = (idx[-1, ..., 0] >= 0).reshape(16, 16, 16, 16).any(axis=(1, 3))
+    assert tiles.sum() > 50                                                                # of the last view's 256 tiles
+
+
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------
 def test_new_abi_surface():
     from d3ga_amd import _lib
