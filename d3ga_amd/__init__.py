@@ -14,6 +14,7 @@ from .objective import TrainingObjective, scale_energy  # noqa: F401
 from .pose_prior import PosePCA  # noqa: F401
 from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, interpolate_face_attributes,  # noqa: F401
                           rasterize_meshes, to_cameras, vertex_normals)
+from .png import PngBuffer, encode_png, png_bytes, save_image  # noqa: F401
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
@@ -21,4 +22,5 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "PCRenderer", "PointFragments", "PointScratch", "rasterize_points", "knn_points", "interpolate_face_attributes",
            "BaryBinding", "bary_interp", "cage_attr", "mesh_means", "code_lookup", "Embedding", "RowCache", "FramePoses",
            "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA",
-           "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter"]
+           "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter",
+           "PngBuffer", "encode_png", "png_bytes", "save_image"]

@@ -140,6 +140,7 @@ GRID_MAX_PANELS, GRID_MAX_LABEL, GRID_MAX_SIDE = 16, 64, 32768    # D3GA_GRID_MA
 GRID_OUT_F32_CHW, GRID_OUT_F32_HWC, GRID_OUT_U8_SAVE_IMAGE, GRID_OUT_U8_CLIP = 0, 1, 2, 3    # D3GA_GRID_OUT_*: modes of d3ga_frame_grid
 GRID_BGR, GRID_FORCE_SCALAR = 1, 2       # D3GA_GRID_*: flags of the grid
 PANEL_BOTTOM, PANEL_BOLD = 1, 2          # D3GA_PANEL_*: flags of a panel
+PNG_FILTER_ADAPTIVE = 5                  # D3GA_PNG_FILTER_ADAPTIVE: filter argument of d3ga_png_encode (0..4 force a type)
 
 
 class GridPanel(ctypes.Structure):
@@ -315,6 +316,9 @@ _SIGNATURES = {
     "d3ga_pose_clamp": ([_vp, _vp] + [ctypes.c_int32] * 4 + [_vp] * 4 + [ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp], _i),
     "d3ga_frame_grid_check": ([ctypes.POINTER(GridDesc), _vp, ctypes.POINTER(ctypes.c_int32)], _i),
     "d3ga_frame_grid": ([ctypes.POINTER(GridDesc), _vp, ctypes.POINTER(ctypes.c_int32), _vp], _i),
+    "d3ga_png_capacity": ([ctypes.c_int32] * 4 + [ctypes.POINTER(_i64)], _i64),
+    "d3ga_png_check": ([ctypes.c_int32] * 3 + [_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _i64], _i),
+    "d3ga_png_encode": ([ctypes.c_int32] * 3 + [_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _i64, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -264,6 +264,48 @@ class _Handle:
             return self._detach_locked()
 
 
+class _PngHandle:
+    """One submitted PNG buffer: tobytes() / save() wait for ITS copy only.  Safe to use from any thread."""
+
+    def __init__(self, writer, slot, nbytes):
+        self._writer, self._slot, self._nbytes, self._data = writer, slot, nbytes, None
+
+    def _detach_locked(self):
+        """With the slot's lock held: wait for the copy, read the length word, take the file's bytes out, free the slot."""
+        if self._data is None:
+            w = self._writer
+            w._events[self._slot].synchronize()
+            host = w._buffers[self._slot][:self._nbytes].numpy()
+            n = int(host[:8].view(np.uint64)[0])
+            if n > self._nbytes - 8:
+                raise _lib.D3GAError(f"submit_png: the length word says {n} bytes, the buffer holds {self._nbytes - 8}: nothing was "
+                                     "encoded into it")
+            self._data = host[8:8 + n].tobytes()
+            if w._owners[self._slot] is self:
+                w._owners[self._slot] = None
+        return self._data
+
+    def done(self):
+        """True once tobytes() would not wait for the device."""
+        if self._data is not None:
+            return True
+        with self._writer._locks[self._slot]:
+            return self._data is not None or self._writer._events[self._slot].query()
+
+    def tobytes(self):
+        """The PNG file's bytes, the handle's own; the pinned slot is free afterwards."""
+        if self._data is not None:
+            return self._data
+        with self._writer._locks[self._slot]:
+            return self._detach_locked()
+
+    def save(self, path):
+        """Write the file: what the save pool's thread calls."""
+        data = self.tobytes()
+        with open(path, "wb") as f:
+            f.write(data)
+
+
 class GridWriter:
     """A ring of `depth` pinned host buffers between the frame loop and the threads that encode images.
 
@@ -304,5 +346,29 @@ class GridWriter:
             self._buffers[slot][:n].view(image.shape).copy_(image, non_blocking=True)
             self._events[slot].record()
             handle = _Handle(self, slot, tuple(image.shape))
+            self._owners[slot] = handle
+        return handle
+
+    def submit_png(self, buf):
+        """A PngBuffer (d3ga_amd.png.encode_png) instead of an image: ONE asynchronous copy of [length word | PNG bytes up to the
+        capacity] into a pinned slot of the same ring -- the length is not known on the host, and reading it first would be a
+        synchronisation.  The handle's tobytes() / save(path) wait for that copy only and take bytes[:length]."""
+        from .png import PngBuffer
+        if not isinstance(buf, PngBuffer):
+            raise TypeError(f"GridWriter.submit_png: expected a PngBuffer, got {type(buf).__name__}")
+        _lib.require_cuda(buf.buffer)
+        with self._ring:
+            slot, self._next = self._next, (self._next + 1) % self.depth
+        with self._locks[slot]:
+            if self._owners[slot] is not None:
+                self._owners[slot]._detach_locked()
+            n = buf.buffer.numel()
+            if self._buffers[slot] is None or self._buffers[slot].numel() < n:
+                self._buffers[slot] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            if self._events[slot] is None:
+                self._events[slot] = torch.cuda.Event()
+            self._buffers[slot][:n].copy_(buf.buffer, non_blocking=True)
+            self._events[slot].record()
+            handle = _PngHandle(self, slot, n)
             self._owners[slot] = handle
         return handle

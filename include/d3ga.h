@@ -1391,6 +1391,28 @@ typedef struct d3ga_grid_desc {
 int d3ga_frame_grid_check(const d3ga_grid_desc *desc, const void *out, int32_t *path);
 int d3ga_frame_grid(const d3ga_grid_desc *desc, void *out, int32_t *path, d3ga_stream_t stream);
 
+/* ---- PNG files of the written images (csrc/png.hip, csrc/png_math.h) --------------------------------------------
+ * A uint8 image (H, W, C), C in {1, 3, 4}, pixels dense and rows `pitch` >= W C bytes apart, becomes the bytes of a PNG file
+ * (colour type 0 / 2 / 6, depth 8, no interlace, no ancillary chunk) in two launches, without a host synchronisation and without
+ * an allocation; capturable.  The stream is pinned byte for byte by csrc/png_math.h: one IDAT chunk per strip of
+ * rows_per_strip rows (0: the default, a function of H, W, C), each a byte-aligned deflate segment of run tokens under its
+ * own Huffman table or the fixed one, whichever is smaller.
+ *   filter: 0..4 forces a PNG filter type, D3GA_PNG_FILTER_ADAPTIVE chooses per row by the smallest sum of absolute values.
+ *   out: 8-byte aligned, [uint64 length][PNG bytes]; out_bytes = room behind the length word, at least d3ga_png_capacity.
+ *     Every byte below the length is written exactly once, none at or beyond it.
+ *   scratch: 16-byte aligned, at least *scratch_bytes of d3ga_png_capacity; contents need not survive between calls.
+ * d3ga_png_capacity (host): the most PNG bytes of such an image, and the scratch it needs; < 0: a status.
+ * d3ga_png_check (host): the tests of d3ga_png_encode, no launch; no pointer is read.
+ *   Status, nothing launched: C outside {1, 3, 4}, an unknown filter or a misaligned out / scratch D3GA_E_CONFIG; H, W < 1,
+ *   rows_per_strip < 0, W C > INT32_MAX, a strip of more than INT32_MAX filtered bytes or pitch < W C D3GA_E_SIZE; a NULL
+ *   pointer D3GA_E_NULL; out_bytes or scratch_bytes too small D3GA_E_CAPACITY. */
+#define D3GA_PNG_FILTER_ADAPTIVE 5
+int64_t d3ga_png_capacity(int32_t H, int32_t W, int32_t C, int32_t rows_per_strip, int64_t *scratch_bytes);
+int d3ga_png_check(int32_t H, int32_t W, int32_t C, int64_t pitch, int32_t filter, int32_t rows_per_strip, const void *img, const void *out,
+                   int64_t out_bytes, const void *scratch, int64_t scratch_bytes);
+int d3ga_png_encode(int32_t H, int32_t W, int32_t C, int64_t pitch, int32_t filter, int32_t rows_per_strip, const void *img, void *out,
+                    int64_t out_bytes, void *scratch, int64_t scratch_bytes, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
