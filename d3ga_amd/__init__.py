@@ -15,6 +15,7 @@ from .pose_prior import PosePCA  # noqa: F401
 from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Renderer, interpolate_face_attributes,  # noqa: F401
                           rasterize_meshes, to_cameras, vertex_normals)
 from .png import PngBuffer, encode_png, png_bytes, save_image  # noqa: F401
+from .sample_prep import SamplePrep, prepare_actorshq, prepare_goliath  # noqa: F401
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
@@ -23,4 +24,5 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "BaryBinding", "bary_interp", "cage_attr", "mesh_means", "code_lookup", "Embedding", "RowCache", "FramePoses",
            "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA",
            "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter",
-           "PngBuffer", "encode_png", "png_bytes", "save_image"]
+           "PngBuffer", "encode_png", "png_bytes", "save_image",
+           "SamplePrep", "prepare_actorshq", "prepare_goliath"]

@@ -319,6 +319,10 @@ _SIGNATURES = {
     "d3ga_png_capacity": ([ctypes.c_int32] * 4 + [ctypes.POINTER(_i64)], _i64),
     "d3ga_png_check": ([ctypes.c_int32] * 3 + [_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _i64], _i),
     "d3ga_png_encode": ([ctypes.c_int32] * 3 + [_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _i64, _vp], _i),
+    "d3ga_sample_prep_actorshq": ([ctypes.c_int32] * 5 + [_vp, _i64, _i64] * 3 + [ctypes.c_int32, ctypes.c_int32] + [_vp] * 4 +
+                                  [ctypes.POINTER(ctypes.c_int32), _vp], _i),
+    "d3ga_sample_prep_goliath": ([ctypes.c_int32] * 3 + [_vp, _i64, _i64, _i64, _vp, _i64, _i64] + [_vp] * 4 +
+                                 [ctypes.POINTER(ctypes.c_int32), _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

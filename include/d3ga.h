@@ -1413,6 +1413,44 @@ int d3ga_png_check(int32_t H, int32_t W, int32_t C, int64_t pitch, int32_t filte
 int d3ga_png_encode(int32_t H, int32_t W, int32_t C, int64_t pitch, int32_t filter, int32_t rows_per_strip, const void *img, void *out,
                     int64_t out_bytes, void *scratch, int64_t scratch_bytes, d3ga_stream_t stream);
 
+/* ---- Sample preparation (csrc/sample_prep.hip, csrc/sample_prep_math.h) ------------------------------------------
+ * What a loader worker does in numpy between the decoded files and the tensors of a sample, one launch for B frames, from the
+ * uint8 arrays as the decoder delivers them.  No gradient, no scratch, no atomics, no host synchronisation; capturable.
+ * A uint8 source is addressed as  base + b frame + y pitch + x step  in BYTES; no base, pitch or frame stride needs any
+ * alignment (an interleaved 747-wide row is 2241 bytes), every read is a byte read and no byte outside the pixels named below is
+ * touched.  With B == 1 the frame strides are not read.
+ * d3ga_sample_prep_actorshq (datasets/actorshq_dataset.py:244-276, get_boundary_mask :201-217), per pixel (y, x), y < H, x < W:
+ *   m         mask[y][x]: channel 0 of the matte, a plane (mask_step 1) or the first byte of an interleaved pixel (mask_step 3);
+ *   t         0 if m < 128, 1 if m > 128, 128 if m == 128 (the reference's two masked assignments leave that value alone);
+ *   er, di    the minimum / maximum of t over the part of the 3 x 3 window around (y, x) that lies inside the image (cv2.erode /
+ *             cv2.dilate with a 3 x 3 kernel of ones, default border value, centre anchor; H and W may be smaller than the window);
+ *   boundary  uint8(di - er) == 1, or 5 < m < 250;         fg   t == 1;
+ *   label     0 without fg; with fg (r, g, b) = seg[y][x] read as BGR, all three taken as 127 when r + g + b == 0, then in this
+ *             order, the last match winning: r == 255 -> 1, g == 255 -> 2, b == 255 -> 3, r == 127 -> 4 (a native red of 127 is
+ *             gray as well); seg is not read where there is no fg;
+ *   image (B,H,W,3) BGR, pitch >= 3 W;  seg (B,Hs,Ws,3) BGR, Hs >= H, Ws >= W, pitch >= 3 Ws, only its top-left H x W is read;
+ *   mask (B,H,W), pitch >= (W - 1) mask_step + 1.
+ *   image_out (B,3,H,W) RGB planar, uint8, or float32 with image_f32 = 1 (the same integers);  seg_part_out (B,1,H,W) int32 label;
+ *   seg_fg_out, boundary_out (B,1,H,W) float32 0 / 1.  Each may be NULL (skipped).
+ * d3ga_sample_prep_goliath (datasets/goliath_dataset.py:454-481): image (B,3,H,W) and parts (B,1,H,W) planar uint8, step 1,
+ *   image_plane bytes between two channels; oh = H / 2, ow = W / 2 (an odd last row or column is never read); all outputs float32:
+ *   image_out (B,3,oh,ow) and seg_part_out (B,1,oh,ow) the mean of the 2 x 2 block, seg_fg_out that of (parts != 0), boundary_out
+ *   1 - seg_fg: F.interpolate(x.float(), scale_factor=0.5, mode="bilinear") bit for bit (multiples of 1/4 below 256).  Each output
+ *   may be NULL (skipped; without image_out the image is not read).
+ * *path (may be NULL): 1 the launch stored four pixels per thread (16-byte stores; W resp. ow a multiple of 4 and a uint8 image_out
+ *   4-byte aligned), 0 one pixel per thread.  Both paths give the same bytes.
+ *   Status, nothing launched and *path not written: B, H, W, Hs, Ws <= 0 (Goliath: H or W < 2), B > 65535, H W > INT32_MAX, more
+ *   than 262140 (output) rows, Hs < H or Ws < W D3GA_E_SIZE; a pitch smaller than its row, with B > 1 a frame stride (Goliath: or
+ *   an image_plane) smaller than what it spans, mask_step outside {1, 3}, image_f32 outside {0, 1}, or a float32 / int32 output not
+ *   16-byte aligned D3GA_E_CONFIG; an input NULL or every output NULL D3GA_E_NULL.  Sizes are tested first. */
+int d3ga_sample_prep_actorshq(int32_t B, int32_t H, int32_t W, int32_t Hs, int32_t Ws, const uint8_t *image, int64_t image_pitch,
+                              int64_t image_frame, const uint8_t *seg, int64_t seg_pitch, int64_t seg_frame, const uint8_t *mask,
+                              int64_t mask_pitch, int64_t mask_frame, int32_t mask_step, int32_t image_f32, void *image_out,
+                              int32_t *seg_part_out, float *seg_fg_out, float *boundary_out, int32_t *path, d3ga_stream_t stream);
+int d3ga_sample_prep_goliath(int32_t B, int32_t H, int32_t W, const uint8_t *image, int64_t image_pitch, int64_t image_plane,
+                             int64_t image_frame, const uint8_t *parts, int64_t parts_pitch, int64_t parts_frame, float *image_out,
+                             float *seg_part_out, float *seg_fg_out, float *boundary_out, int32_t *path, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
