@@ -17,6 +17,7 @@
 //               backward.
 #include "d3ga_internal.h"
 #include "body_model_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -47,12 +48,6 @@ struct Saved {
     __host__ __device__ int rh() const { return 27 * J + 9; }
     __host__ __device__ int th() const { return 27 * J + 12; }
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // Fixed-order sum of N per-lane values over the workgroup; the totals land in out[0..N) (LDS) after the call.
 template <int N, int W = kWaves>

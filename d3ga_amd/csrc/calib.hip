@@ -27,18 +27,13 @@
 // same threads write exact zeros into their cells of every OTHER camera's map, so the whole (n_cameras,1,bh,bw) gradient is
 // written by the one launch.
 #include "d3ga_internal.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
 constexpr int kCalibTile = 3 * kBlock;                       // float4s per workgroup and trip
 constexpr int kCalibRows = D3GA_CALIB_PARTIALS / 6;          // rows of six partial sums in the scratch
 constexpr int kBiasCells = 32;                               // low-resolution cells per workgroup of the bias backward
-
-__device__ __forceinline__ float calib_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __device__ __forceinline__ int calib_cam(const int32_t *__restrict__ cam, int v, int n_cameras) {
     return min(max(cam[v], 0), n_cameras - 1);
@@ -142,10 +137,7 @@ __global__ __launch_bounds__(kBlock) void color_calib_kernel(int L, int n_camera
     if (sums) {                                              // one row per workgroup: plain stores, fixed order
         float r[6] = {tx[0], tx[1], tx[2], tg[0], tg[1], tg[2]};
 #pragma unroll
-        for (int m = 0; m < 6; ++m) {
-            r[m] = calib_wave_sum(r[m]);
-            if ((tid & 63) == 0) s_part[m][tid >> 6] = r[m];
-        }
+        for (int m = 0; m < 6; ++m) wave_sum_to_lds(r[m], s_part[m]);
         __syncthreads();
         if (tid < 6)
             partials[6 * ((size_t)seg * gridDim.x + blockIdx.x) + tid] =
@@ -174,10 +166,7 @@ __global__ __launch_bounds__(kBlock) void color_calib_finish_kernel(int k, int r
             for (int m = 0; m < 6; ++m) a[m] += p[6 * i + m];
         }
 #pragma unroll
-        for (int m = 0; m < 6; ++m) {
-            a[m] = calib_wave_sum(a[m]);
-            if ((tid & 63) == 0) s_part[m][tid >> 6] = a[m];
-        }
+        for (int m = 0; m < 6; ++m) wave_sum_to_lds(a[m], s_part[m]);
         __syncthreads();
         if (tid < 6) {
             const float s = (s_part[tid][0] + s_part[tid][1]) + (s_part[tid][2] + s_part[tid][3]);
@@ -294,8 +283,6 @@ __global__ __launch_bounds__(kBlock) void pixel_bias_bwd_kernel(int C, int H, in
 }  // namespace d3ga
 
 using namespace d3ga;
-
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // segments and their length; < 0: the sizes are refused
 static inline int calib_shape(int32_t k, int32_t n, int32_t planar, int32_t n_cameras, int32_t identity_idx, int *segs, int *L) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/d3ga.h"
 #include "d3ga_math.h"
 
@@ -213,6 +215,33 @@ static inline int check_launch(hipStream_t s, int debug) {
         hipError_t _e = (expr);                 \
         if (_e != hipSuccess) return (int)_e;   \
     } while (0)
+
+// argument checks of the entry points: an address that is no multiple of mask + 1 (null passes: optional arguments)
+static inline bool misaligned(const void *p, uintptr_t mask = 3) { return ((uintptr_t)p & mask) != 0; }
+static inline bool aligned16(const void *p) { return !misaligned(p, 15); }
+// workgroups of a grid-stride kernel with one lane per item: ceil(n / kBlock), at least 1, at most cap
+static inline unsigned grid_1d(int64_t n, int64_t cap = 65536) {
+    const int64_t blocks = (n + kBlock - 1) / kBlock;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
+// What must happen once per device before a kernel's first launch there (function attributes are per device):
+//   static PerDeviceOnce once;  D3GA_TRY(once.run([&] { return (int)hipFuncSetAttribute(...); }));
+// Entry points are re-entrant across devices and streams (include/d3ga.h), hence atomics: two threads may both run fn, which is
+// harmless, and none skips it before it has succeeded.  A device index past the table runs fn on every call.
+struct PerDeviceOnce {
+    std::atomic<bool> done[64] = {};
+    template <typename Fn>
+    int run(Fn fn) {
+        int dev = 0;
+        D3GA_HIP(hipGetDevice(&dev));
+        const bool listed = dev >= 0 && dev < 64;
+        if (listed && done[dev].load(std::memory_order_acquire)) return 0;
+        D3GA_TRY(fn());
+        if (listed) done[dev].store(true, std::memory_order_release);
+        return 0;
+    }
+};
 
 // Zero-fill as a KERNEL node.  hipMemsetAsync becomes a memset node under stream capture, and on this stack (ROCm 7.2,
 // gfx950) a replayed graph did not reliably order such a node against the kernels around it: with the tile histogram

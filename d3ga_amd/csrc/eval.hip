@@ -28,6 +28,7 @@
 // the 1e-3 dB bar.
 #include "d3ga_internal.h"
 #include "eval_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -35,12 +36,6 @@ static_assert(kEvalBlock == kBlock, "eval_math.h cuts frames for workgroups of k
 
 __device__ constexpr JetTable d_jet = make_jet_table();
 static constexpr JetTable h_jet = make_jet_table();
-
-__device__ __forceinline__ float wave_sum_eval(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // VEC: quads (H W % 4 == 0, all tensors 16-byte aligned);  BF32: boundary_fg is float32, else bytes
 template <bool VEC, bool BF32>
@@ -140,10 +135,7 @@ __global__ __launch_bounds__(kBlock) void eval_frames_kernel(int hw, int passes,
     }
     if (partials) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float w = wave_sum_eval(acc[c]);
-            if ((tid & 63) == 0) s_part[c][tid >> 6] = w;
-        }
+        for (int c = 0; c < 3; ++c) wave_sum_to_lds(acc[c], s_part[c]);
         __syncthreads();
         if (tid < 3) partials[(b * 3 + tid) * gridDim.x + blockIdx.x] = ((s_part[tid][0] + s_part[tid][1]) + s_part[tid][2]) + s_part[tid][3];
     }
@@ -158,16 +150,8 @@ __global__ __launch_bounds__(kBlock) void eval_ssim_kernel(int H, int W, int til
     const size_t o = plane * (size_t)H * W;
     const int ty0 = (tile / tiles_x) * kEvalSsimTile, tx0 = (tile % tiles_x) * kEvalSsimTile;
     float sum = eval_ssim_tile(s_x, s_y, s_h, pred + o, target + o, H, W, ty0, tx0, tid, kBlock, [] { __syncthreads(); });
-    sum = wave_sum_eval(sum);
-    if ((tid & 63) == 0) s_part[tid >> 6] = sum;
-    __syncthreads();
+    wave_sums_to_lds(sum, s_part);
     if (tid == 0) partials[plane * gridDim.x + tile] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-}
-
-__device__ __forceinline__ double wave_sum_eval(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 __global__ __launch_bounds__(kBlock) void eval_finish_kernel(int np, float hw, const float *__restrict__ partials, int64_t np_ssim,
@@ -182,15 +166,14 @@ __global__ __launch_bounds__(kBlock) void eval_finish_kernel(int np, float hw, c
         const float *p = partials + (b * 3 + c) * np;
         float a = 0.f;
         for (int i = tid; i < np; i += kBlock) a += p[i];
-        a = wave_sum_eval(a);
+        a = wave_sum(a);
         if ((tid & 63) == 0) s_part[c][tid >> 6] = a;
     }
     if (ssim_partials) {                                     // tiles of the three channels, in index order, in double
         const float *p = ssim_partials + b * np_ssim;
         double a = 0.0;
         for (int64_t i = tid; i < np_ssim; i += kBlock) a += (double)p[i];
-        a = wave_sum_eval(a);
-        if ((tid & 63) == 0) s_ssim[tid >> 6] = a;
+        wave_sum_to_lds(a, s_ssim);
     }
     __syncthreads();
     if (tid == 0) {

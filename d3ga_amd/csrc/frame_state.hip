@@ -17,6 +17,7 @@
 // was scaled, and the store into EVERY out row that names this table row.  A table row is handled at its first position in
 // idx and skipped at the later ones: renormed once, all copies equal, nothing that was written is read again.
 #include "d3ga_internal.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -49,11 +50,8 @@ __global__ __launch_bounds__(kBlock) void code_lookup_fwd_kernel(float *__restri
         float scale = 1.f;
         bool scaled = false;
         if (max_norm > 0.f) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
             __syncthreads();                                 // the previous row's reads of s_part are done
-            if ((tid & 63) == 0) s_part[tid >> 6] = ss;
-            __syncthreads();
+            wave_sums_to_lds(ss, s_part);
             const float norm = sqrtf(((s_part[0] + s_part[1]) + s_part[2]) + s_part[3]);
             scaled = norm > max_norm;
             if (scaled) scale = max_norm / (norm + 1e-7f);
@@ -177,8 +175,6 @@ __global__ __launch_bounds__(kBlock) void row_cache_kernel(RowPairs desc, int n_
 }  // namespace d3ga
 
 using namespace d3ga;
-
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 static inline int code_shape(int32_t N, int32_t D, int32_t B) {
     if (N < 1 || D < 1 || B < 1 || B > D3GA_CODE_MAX_B || D > D3GA_CODE_MAX_D) return D3GA_E_SIZE;

@@ -22,6 +22,7 @@
 // vertical pass forms eight outputs per thread (one column, 32 LDS reads per eight pixels) and mixes.
 // HBM traffic per pixel and channel: forward 4 B read + 4 B written, backward 8 B read + 4 B written.
 #include "d3ga_internal.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -36,12 +37,6 @@ constexpr int kBlurGridCap = D3GA_BLUR_PARTIALS / 3;       // workgroups of a la
 constexpr float kG3_0 = 0.52201146875401892f, kG3_1 = 0.23899426562299048f;
 constexpr float kG7_0 = 0.28802604575225105f, kG7_1 = 0.22317336074208335f, kG7_2 = 0.10381835124997371f,
                 kG7_3 = 0.028995265131817438f;
-
-__device__ __forceinline__ float wave_sum_tail(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // reflect without repeating the edge sample; positions further out than the padding (tiles that hang over the image: they
 // only feed pixels that are never written) are clamped into the image
@@ -146,7 +141,7 @@ __global__ __launch_bounds__(256) void blur_mix_kernel(int C, int H, int W, int 
         }
     }
     if (BWD && img) {                                      // one partial per workgroup and sum: plain stores, fixed order
-        acc0 = wave_sum_tail(acc0); acc1 = wave_sum_tail(acc1); acc2 = wave_sum_tail(acc2);
+        acc0 = wave_sum(acc0); acc1 = wave_sum(acc1); acc2 = wave_sum(acc2);
         if ((tid & 63) == 0) { s_part[0][tid >> 6] = acc0; s_part[1][tid >> 6] = acc1; s_part[2][tid >> 6] = acc2; }
         __syncthreads();
         if (tid < 3) partials[3 * blockIdx.x + tid] = (s_part[tid][0] + s_part[tid][1]) + (s_part[tid][2] + s_part[tid][3]);
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void blur_finish_kernel(int np, const float
     __shared__ float s_grad[3];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f;
     for (int i = threadIdx.x; i < np; i += kBlock) { a0 += partials[3 * i]; a1 += partials[3 * i + 1]; a2 += partials[3 * i + 2]; }
-    a0 = wave_sum_tail(a0); a1 = wave_sum_tail(a1); a2 = wave_sum_tail(a2);
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
     if ((threadIdx.x & 63) == 0) { s_part[0][threadIdx.x >> 6] = a0; s_part[1][threadIdx.x >> 6] = a1; s_part[2][threadIdx.x >> 6] = a2; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -5,18 +5,13 @@
 //               five depthwise conv2d (11x11, zero padding) plus ~15 elementwise kernels forward and their autograd
 //               backward; here one LDS-tiled separable pass each way.
 #include "d3ga_internal.h"
+#include "wave_prims.h"
 
 #include <stdlib.h>
 
 #include <mutex>
 
 namespace d3ga {
-
-__device__ __forceinline__ float wave_sum_loss(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // sum |a - b| of this workgroup's grid-stride share, times inv_n (every thread returns; thread 0 holds the value)
 __device__ __forceinline__ float l1_block_sum(int64_t n4, int64_t n, const float *__restrict__ a, const float *__restrict__ b,
@@ -35,9 +30,7 @@ __device__ __forceinline__ float l1_block_sum(int64_t n4, int64_t n, const float
         acc += fabsf(x.x - y.x) + fabsf(x.y - y.y) + fabsf(x.z - y.z) + fabsf(x.w - y.w);
     }
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc += fabsf(a[i] - b[i]);
-    acc = wave_sum_loss(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     float t = 0.f;
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -70,9 +63,7 @@ __global__ __launch_bounds__(kBlock) void sum_partials_kernel(int np, const floa
     __shared__ float s_part[kBlock / 64];
     float acc = 0.f;
     for (int i = threadIdx.x; i < np; i += kBlock) acc += partials[i];
-    acc = wave_sum_loss(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     if (threadIdx.x == 0) {
         float t = 0.f;
 #pragma unroll
@@ -101,9 +92,7 @@ __global__ __launch_bounds__(1024) void sum_partials_wide_kernel(int np, const f
         acc += (v.x + v.y) + (v.z + v.w);
     }
     for (int j = 4 * np4 + threadIdx.x; j < np; j += 1024) acc += partials[j];
-    acc = wave_sum_loss(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     if (threadIdx.x == 0) {
         float t = 0.f;
 #pragma unroll
@@ -222,8 +211,8 @@ __global__ __launch_bounds__(kBlock) void ssim_finish_kernel(int np, int slot, f
     __shared__ float s_part[2][kBlock / 64];
     float acc = 0.f, acc_l1 = 0.f;
     for (int i = threadIdx.x; i < np; i += kBlock) { acc += g_ssim_partials[slot][0][i]; acc_l1 += g_ssim_partials[slot][1][i]; }
-    acc = wave_sum_loss(acc);
-    acc_l1 = wave_sum_loss(acc_l1);
+    acc = wave_sum(acc);
+    acc_l1 = wave_sum(acc_l1);
     if ((threadIdx.x & 63) == 0) { s_part[0][threadIdx.x >> 6] = acc; s_part[1][threadIdx.x >> 6] = acc_l1; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -319,8 +308,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(int C, int H, int W, int 
             }
         }
     }
-    local = wave_sum_loss(local);
-    local_l1 = wave_sum_loss(local_l1);
+    local = wave_sum(local);
+    local_l1 = wave_sum(local_l1);
     if ((tid & 63) == 0) { s_part[tid >> 6] = local; s_part[4 + (tid >> 6)] = local_l1; }
     __syncthreads();
     if (tid == 0) {
@@ -534,8 +523,8 @@ __global__ __launch_bounds__(kMarchW, 4) void ssim_march_fwd_kernel(int C, int H
         }
         __syncthreads();                                  // (next item: both buffers are rewritten from row 0 on)
     }
-    local = wave_sum_loss(local);
-    local_l1 = wave_sum_loss(local_l1);
+    local = wave_sum(local);
+    local_l1 = wave_sum(local_l1);
     if ((tid & 63) == 0) { s_part[tid >> 6] = local; s_part[4 + (tid >> 6)] = local_l1; }
     __syncthreads();
     if (tid == 0) {

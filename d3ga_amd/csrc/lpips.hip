@@ -25,6 +25,7 @@
 // gridDim.x = lp_tap_blocks <= kLpPartials.
 #include "d3ga_internal.h"
 #include "lpips_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -103,10 +104,7 @@ __global__ __launch_bounds__(kBlock) void lp_tap_kernel(int hw, int C, int shift
             acc += d;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     if (tid == 0) partials[img * gridDim.x + blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
 }
 
@@ -118,10 +116,7 @@ __global__ __launch_bounds__(kBlock) void lp_finish_kernel(int np, double hw, in
     const float *p = partials + b * (size_t)np;
     double s = 0.0;
     for (int i = tid; i < np; i += kBlock) s += (double)p[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-    if ((tid & 63) == 0) s_part[tid >> 6] = s;
-    __syncthreads();
+    wave_sums_to_lds(s, s_part);
     if (tid == 0) {
         const float mean = (float)((((s_part[0] + s_part[1]) + s_part[2]) + s_part[3]) / hw);
         value[b] = accumulate ? value[b] + mean : mean;

@@ -20,11 +20,11 @@
 // The shade, map and vertex-normal kernels are per-pixel / per-vertex gathers over these outputs.
 #include "d3ga_internal.h"
 #include "mesh_raster_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
 constexpr int kMeshScanBlock = 1024;
-constexpr int kMeshMaxGrid = 1 << 16;           // workgroups of a grid-stride pixel kernel
 constexpr int kMeshCoverGrid = 2048;            // workgroups of the coverage kernel: 8 per CU, four wavefronts each
 
 struct MeshScratch {
@@ -56,22 +56,12 @@ __global__ __launch_bounds__(kBlock) void mesh_clear_kernel(uint64_t *__restrict
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) keys[i] = kMeshEmptyKey;
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void mesh_setup_kernel(int64_t BF, int F, int V, int H, int W, const float *__restrict__ verts,
                                                             const int32_t *__restrict__ faces, const float *__restrict__ cams,
                                                             MeshFaceRec *__restrict__ recs, uint32_t *__restrict__ local,
                                                             uint32_t *__restrict__ block_total) {
     __shared__ uint32_t s_wave[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t g = (int64_t)blockIdx.x * kBlock + tid;
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     uint32_t count = 0;
     if (g < BF) {
         const int64_t b = g / F;
@@ -93,50 +83,15 @@ __global__ __launch_bounds__(kBlock) void mesh_setup_kernel(int64_t BF, int F, i
             if (count) recs[g] = r;
         }
     }
-    const uint32_t incl = wave_incl_scan_u32(count, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) before += s_wave[w];
-        total += s_wave[w];
-    }
-    local[g] = before + incl - count;           // the padding lanes of the last workgroup too: local holds nblk * kBlock words
-    if (tid == 0) block_total[blockIdx.x] = total;
-}
-
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int off) {
-    const uint32_t lo = __shfl_up((uint32_t)v, off), hi = __shfl_up((uint32_t)(v >> 32), off);
-    return ((uint64_t)hi << 32) | lo;
+    uint32_t total;                             // (the padding lanes of the last workgroup store too: local holds nblk * kBlock words)
+    local[g] = block_excl_scan_u32<kBlock / 64>(count, s_wave, &total);
+    if (threadIdx.x == 0) block_total[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kMeshScanBlock) void mesh_scan_kernel(int64_t nblk, const uint32_t *__restrict__ block_total,
                                                                    uint64_t *__restrict__ block_start) {
     __shared__ uint64_t s_wave[kMeshScanBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t carry = 0;
-    for (int64_t base = 0; base < nblk; base += kMeshScanBlock) {
-        const int64_t i = base + tid;
-        const uint64_t v = i < nblk ? (uint64_t)block_total[i] : 0;
-        uint64_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t o = shfl_up_u64(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint64_t before = 0, total = 0;
-        for (int w = 0; w < kMeshScanBlock / 64; ++w) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
-        if (i < nblk) block_start[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) block_start[nblk] = carry;
+    scan_block_totals<kMeshScanBlock>(nblk, block_total, block_start, s_wave);
 }
 
 __global__ __launch_bounds__(kBlock) void mesh_coverage_kernel(int64_t nblk, int64_t BF, int F, int H, int W, const MeshFaceRec *__restrict__ recs,
@@ -329,11 +284,6 @@ __global__ __launch_bounds__(kBlock) void mesh_interp_kernel(int64_t n, int64_t 
     }
 }
 
-static inline unsigned mesh_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > kMeshMaxGrid ? kMeshMaxGrid : blocks));
-}
-
 }  // namespace d3ga
 
 using namespace d3ga;
@@ -345,7 +295,6 @@ static inline int mesh_sizes(int32_t B, int32_t V, int32_t F) {
     return D3GA_OK;
 }
 static inline int mesh_frame(int32_t H, int32_t W) { return (H < 1 || W < 1 || H > kMeshMaxSide || W > kMeshMaxSide) ? D3GA_E_SIZE : D3GA_OK; }
-static inline bool mesh_unaligned(const void *p, uintptr_t mask = 3) { return ((uintptr_t)p & mask) != 0; }
 
 extern "C" int d3ga_mesh_raster_scratch_bytes(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, size_t *bytes) {
     D3GA_TRY(mesh_sizes(B, V, F));
@@ -361,14 +310,14 @@ extern "C" int d3ga_mesh_rasterize(int32_t B, int32_t V, int32_t F, int32_t H, i
     D3GA_TRY(mesh_sizes(B, V, F));
     D3GA_TRY(mesh_frame(H, W));
     if (!scratch || !pix_to_face || !cams || (F > 0 && (!faces || !verts))) return D3GA_E_NULL;
-    if (mesh_unaligned(verts) || mesh_unaligned(faces) || mesh_unaligned(cams) || mesh_unaligned(scratch, 15) || mesh_unaligned(pix_to_face) ||
-        mesh_unaligned(zbuf) || mesh_unaligned(bary))
+    if (misaligned(verts) || misaligned(faces) || misaligned(cams) || misaligned(scratch, 15) || misaligned(pix_to_face) ||
+        misaligned(zbuf) || misaligned(bary))
         return D3GA_E_CONFIG;
     if (B == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W, n = hw * B, BF = (int64_t)B * F, nblk = mesh_blocks(BF);
     const MeshScratch sc = carve_mesh(scratch, B, F, H, W);
-    hipLaunchKernelGGL(mesh_clear_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, sc.keys, n);
+    hipLaunchKernelGGL(mesh_clear_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, sc.keys, n);
     if (BF > 0) {
         hipLaunchKernelGGL(mesh_setup_kernel, dim3((unsigned)nblk), dim3(kBlock), 0, s, BF, F, V, H, W, verts, faces, cams, sc.recs, sc.local,
                            sc.block_total);
@@ -379,7 +328,7 @@ extern "C" int d3ga_mesh_rasterize(int32_t B, int32_t V, int32_t F, int32_t H, i
         hipLaunchKernelGGL(mesh_coverage_kernel, dim3((unsigned)(wgs > kMeshCoverGrid ? kMeshCoverGrid : wgs)), dim3(kBlock), 0, s, nblk, BF, F, H,
                            W, sc.recs, sc.local, sc.block_start, sc.keys);
     }
-    hipLaunchKernelGGL(mesh_resolve_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, hw, W, F, sc.keys, sc.recs, pix_to_face, zbuf, bary);
+    hipLaunchKernelGGL(mesh_resolve_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, hw, W, F, sc.keys, sc.recs, pix_to_face, zbuf, bary);
     return check_launch(s, 0);
 }
 
@@ -389,15 +338,15 @@ extern "C" int d3ga_mesh_shade_flat(int32_t B, int32_t V, int32_t F, int32_t H, 
     D3GA_TRY(mesh_sizes(B, V, F));
     D3GA_TRY(mesh_frame(H, W));
     if (!cams || !pix_to_face || !bary || !bg || !image || (F > 0 && (!faces || !verts))) return D3GA_E_NULL;
-    if (mesh_unaligned(verts) || mesh_unaligned(faces) || mesh_unaligned(verts_rgb) || mesh_unaligned(cams) || mesh_unaligned(pix_to_face) ||
-        mesh_unaligned(bary) || mesh_unaligned(image))
+    if (misaligned(verts) || misaligned(faces) || misaligned(verts_rgb) || misaligned(cams) || misaligned(pix_to_face) ||
+        misaligned(bary) || misaligned(image))
         return D3GA_E_CONFIG;
     if (B == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W, n = hw * B;
     MeshBg b;
     b.v[0] = bg[0]; b.v[1] = bg[1]; b.v[2] = bg[2];
-    hipLaunchKernelGGL(mesh_shade_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, hw, V, F, verts, faces, verts_rgb, cams, pix_to_face, bary,
+    hipLaunchKernelGGL(mesh_shade_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, hw, V, F, verts, faces, verts_rgb, cams, pix_to_face, bary,
                        b, image);
     return check_launch(s, 0);
 }
@@ -407,12 +356,12 @@ extern "C" int d3ga_mesh_vertex_normals(int32_t B, int32_t V, int32_t F, const f
     D3GA_TRY(mesh_sizes(B, V, F));
     if (V > 0 && (!verts || !csr_offsets || !normals)) return D3GA_E_NULL;
     if (F > 0 && (!faces || !csr_faces)) return D3GA_E_NULL;
-    if (mesh_unaligned(verts) || mesh_unaligned(faces) || mesh_unaligned(csr_offsets) || mesh_unaligned(csr_faces) || mesh_unaligned(normals))
+    if (misaligned(verts) || misaligned(faces) || misaligned(csr_offsets) || misaligned(csr_faces) || misaligned(normals))
         return D3GA_E_CONFIG;
     const int64_t n = (int64_t)B * V;
     if (n == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, V, F, verts, faces, csr_offsets, csr_faces,
+    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, V, F, verts, faces, csr_offsets, csr_faces,
                        normals);
     return check_launch(s, 0);
 }
@@ -424,14 +373,14 @@ extern "C" int d3ga_mesh_maps(int32_t B, int32_t V, int32_t F, int32_t H, int32_
     D3GA_TRY(mesh_frame(H, W));
     if (!cams || !pix_to_face || !bary || (F > 0 && (!faces || !verts || !vertex_normals))) return D3GA_E_NULL;
     if (!position && !normal && !depth && !mask) return D3GA_E_NULL;
-    if (mesh_unaligned(verts) || mesh_unaligned(faces) || mesh_unaligned(vertex_normals) || mesh_unaligned(cams) ||
-        mesh_unaligned(pix_to_face) || mesh_unaligned(bary) || mesh_unaligned(position) || mesh_unaligned(normal) || mesh_unaligned(depth) ||
-        mesh_unaligned(mask))
+    if (misaligned(verts) || misaligned(faces) || misaligned(vertex_normals) || misaligned(cams) ||
+        misaligned(pix_to_face) || misaligned(bary) || misaligned(position) || misaligned(normal) || misaligned(depth) ||
+        misaligned(mask))
         return D3GA_E_CONFIG;
     if (B == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W, n = hw * B;
-    hipLaunchKernelGGL(mesh_maps_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, hw, V, F, verts, faces, vertex_normals, cams, pix_to_face,
+    hipLaunchKernelGGL(mesh_maps_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, hw, V, F, verts, faces, vertex_normals, cams, pix_to_face,
                        bary, position, normal, depth, mask);
     return check_launch(s, 0);
 }
@@ -442,9 +391,9 @@ extern "C" int d3ga_interp_face_attrs(int64_t n_pix, int64_t F_total, int D, con
     if (n_pix >= ((int64_t)1 << 40) || F_total >= ((int64_t)1 << 40)) return D3GA_E_SIZE;
     if (n_pix == 0) return D3GA_OK;
     if (!pix_to_face || !bary || !out || (F_total > 0 && !face_attrs)) return D3GA_E_NULL;
-    if (mesh_unaligned(pix_to_face, 7) || mesh_unaligned(bary) || mesh_unaligned(face_attrs) || mesh_unaligned(out)) return D3GA_E_CONFIG;
+    if (misaligned(pix_to_face, 7) || misaligned(bary) || misaligned(face_attrs) || misaligned(out)) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = n_pix * D;
-    hipLaunchKernelGGL(mesh_interp_kernel, dim3(mesh_grid(n)), dim3(kBlock), 0, s, n, F_total, D, pix_to_face, bary, face_attrs, out);
+    hipLaunchKernelGGL(mesh_interp_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, F_total, D, pix_to_face, bary, face_attrs, out);
     return check_launch(s, 0);
 }

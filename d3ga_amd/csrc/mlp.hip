@@ -1064,15 +1064,12 @@ extern "C" int d3ga_mlp_linear(int32_t P, int32_t K, int32_t n_out, const float 
     const bool vec = (K % 4) == 0;
 #define D3GA_MLP_LAUNCH3(NBV, VECV, MASKV, RAGV, PV, XV, SV, MV, YV)                                                  \
     do {                                                                                                              \
-        static bool attr[64] = {};                                                                                    \
-        int dev = 0;                                                                                                  \
-        D3GA_HIP(hipGetDevice(&dev));                                                                                 \
-        if (dev >= 0 && dev < 64 && !attr[dev]) {                                                                     \
-            D3GA_HIP(hipFuncSetAttribute((const void *)linear_kernel<NBV, VECV, MASKV, RAGV>,                         \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,                                  \
-                                         mlp_panel_units(kMlpMaxK, 32 * NBV) * 16 + (kMlpThreads / 64) * kMlpABytes));  \
-            attr[dev] = true;                                                                                         \
-        }                                                                                                             \
+        static PerDeviceOnce once;                                                                                    \
+        D3GA_TRY(once.run([] {                                                                                        \
+            return (int)hipFuncSetAttribute((const void *)linear_kernel<NBV, VECV, MASKV, RAGV>,                      \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,                               \
+                                            mlp_panel_units(kMlpMaxK, 32 * NBV) * 16 + (kMlpThreads / 64) * kMlpABytes);  \
+        }));                                                                                                          \
         const int nt = ((PV) + kMlpRows - 1) / kMlpRows;                                                              \
         hipLaunchKernelGGL((linear_kernel<NBV, VECV, MASKV, RAGV>), dim3(nt < 256 ? nt : 256), dim3(kMlpThreads), lds, \
                            s, (PV), K, n_out, (XV), Wp, bias, out_slope, (SV), (MV), mask_slope, (YV));               \
@@ -1139,28 +1136,22 @@ static int mlp_wgrad_launch(int32_t P, int32_t N, int32_t K, const float *dpre, 
     const bool ws_for_mixed = ws_knob == 2 || (ws_knob == 1 && N <= 16 && K > 16);
 #define D3GA_WG(VA, VB, MX)                                                                                           \
     do {                                                                                                              \
-        static bool attr[64] = {};                                                                                    \
-        int dev = 0;                                                                                                  \
-        D3GA_HIP(hipGetDevice(&dev));                                                                                 \
-        if (dev >= 0 && dev < 64 && !attr[dev]) {                                                                     \
-            D3GA_HIP(hipFuncSetAttribute((const void *)wgrad_kernel<VA, VB, MX>,                                      \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-            attr[dev] = true;                                                                                         \
-        }                                                                                                             \
+        static PerDeviceOnce once;                                                                                    \
+        D3GA_TRY(once.run([&] {                                                                                       \
+            return (int)hipFuncSetAttribute((const void *)wgrad_kernel<VA, VB, MX>,                                   \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
+        }));                                                                                                          \
         hipLaunchKernelGGL((wgrad_kernel<VA, VB, MX>), dim3(grid), dim3(kWgThreads), lds, s, P, N, K, NBk, NBn * NBk, \
                            rows, dpre, X, dW, db);                                                                    \
     } while (0)
 #define D3GA_WS(VA, VB)                                                                                               \
     do {                                                                                                              \
-        static bool attr[64] = {};                                                                                    \
-        int dev = 0;                                                                                                  \
-        D3GA_HIP(hipGetDevice(&dev));                                                                                 \
+        static PerDeviceOnce once;                                                                                    \
         const size_t lds_ws = 2 * (size_t)kWsBufferUnits * 16;                                                        \
-        if (dev >= 0 && dev < 64 && !attr[dev]) {                                                                     \
-            D3GA_HIP(hipFuncSetAttribute((const void *)wgrad_ws_kernel<VA, VB>,                                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ws));                   \
-            attr[dev] = true;                                                                                         \
-        }                                                                                                             \
+        D3GA_TRY(once.run([&] {                                                                                       \
+            return (int)hipFuncSetAttribute((const void *)wgrad_ws_kernel<VA, VB>,                                    \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ws);                 \
+        }));                                                                                                          \
         hipLaunchKernelGGL((wgrad_ws_kernel<VA, VB>), dim3(grid), dim3(kWgThreads), lds_ws, s, P, N, K, NBk, NBn, rows, \
                            dpre, X, dW, db);                                                                          \
     } while (0)
@@ -1248,16 +1239,14 @@ extern "C" int d3ga_mlp_chain_fwd(int32_t P, int32_t K0, const float *X, int32_t
     a.abl = abl;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)kChainSlots * kChainSlotUnits * 16 + (3 * 128 + (kChainThreads / 64) * 32 * kChainStageLd) * sizeof(float);
-    static bool attr[64] = {};
-    int dev = 0;
-    D3GA_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr[dev]) {
+    static PerDeviceOnce once;
+    D3GA_TRY(once.run([&] {
         const void *ks[8] = {(const void *)chain_fwd_kernel<1, false>, (const void *)chain_fwd_kernel<2, false>, (const void *)chain_fwd_kernel<3, false>,
                              (const void *)chain_fwd_kernel<4, false>, (const void *)chain_fwd_kernel<1, true>, (const void *)chain_fwd_kernel<2, true>,
                              (const void *)chain_fwd_kernel<3, true>, (const void *)chain_fwd_kernel<4, true>};
         for (const void *k : ks) D3GA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr[dev] = true;
-    }
+        return 0;
+    }));
     // this call's biases into the panels' tails.  (The BWD instantiation never reads a bias -- the tail still rides along with the
     // panel's DMA, whatever it holds: no launch for it, 5.7 us x 3 chains per colour step.)
     if (!bwd) hipLaunchKernelGGL(chain_bias_kernel, dim3(L), dim3(128), 0, s, ba);

@@ -15,16 +15,13 @@
 // copy node inside the graph (see zero_async in d3ga_internal.h for what this stack does with such nodes).
 #include "d3ga_internal.h"
 #include "objective_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
 constexpr int kObjBlock = 1024;                  // 16 wavefronts: the 9 entries of one frame in one round
 
-__device__ __forceinline__ float obj_wave_sum_dev(float v) {
-#pragma unroll
-    for (int off = kObjLanes / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+static_assert(kObjLanes == 64, "obj_lane_partial deals an entry to the lanes that wave_sum adds: a whole wavefront");
 
 // ---- scale_energy ----------------------------------------------------------------------------------------------------------
 // One partial per workgroup: a thread adds the four terms of a 16-byte load pairwise, its loads in grid-stride order; 64 lanes
@@ -45,9 +42,7 @@ __global__ __launch_bounds__(kBlock) void scale_energy_partial_kernel(int64_t n4
         acc += (scale_energy_term(ACT, x.x) + scale_energy_term(ACT, x.y)) + (scale_energy_term(ACT, x.z) + scale_energy_term(ACT, x.w));
     }
     for (int64_t i = 4 * n4 + gid; i < n; i += stride) acc += scale_energy_term(ACT, DELTA ? a[i] + b[i] : a[i]);
-    acc = obj_wave_sum_dev(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     if (threadIdx.x == 0) {
         float t = 0.f;
 #pragma unroll
@@ -61,9 +56,7 @@ __global__ __launch_bounds__(kBlock) void scale_energy_finish_kernel(int np, con
     __shared__ float s_part[kBlock / 64];
     float acc = 0.f;
     for (int i = threadIdx.x; i < np; i += kBlock) acc += partials[i];
-    acc = obj_wave_sum_dev(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wave_sums_to_lds(acc, s_part);
     if (threadIdx.x == 0) {
         float t = 0.f;
 #pragma unroll
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(kObjBlock) void objective_fwd_kernel(d3ga_objective
     for (int it = wave; it < n_items; it += kObjBlock / 64) {
         const d3ga_objective_entry e = d.entry[it];
         float v = 0.f;
-        if (e.ptr) v = obj_wave_sum_dev(obj_lane_partial(it % D3GA_OBJ_SLOTS, e.ptr, e.len, lane));
+        if (e.ptr) v = wave_sum(obj_lane_partial(it % D3GA_OBJ_SLOTS, e.ptr, e.len, lane));
         if (lane == 0) s_sum[it] = v;
     }
     __syncthreads();
@@ -133,8 +126,6 @@ __global__ __launch_bounds__(kBlock) void objective_bwd_kernel(d3ga_objective_de
 
 using namespace d3ga;
 
-static inline bool obj_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 static inline int scale_energy_grid(int64_t n4, int cap) {
     const int64_t blocks = (n4 + kBlock - 1) / kBlock;
     return (int)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
@@ -145,7 +136,7 @@ extern "C" int d3ga_scale_energy_fwd(int64_t n, const float *scaling, const floa
     if (n <= 0) return D3GA_E_SIZE;
     if (!scaling || !out || !partials) return D3GA_E_NULL;
     if (activation != D3GA_SCALE_ACT_EXP && activation != D3GA_SCALE_ACT_NONE) return D3GA_E_CONFIG;
-    if (!obj_aligned16(scaling) || !obj_aligned16(delta)) return D3GA_E_CONFIG;
+    if (!aligned16(scaling) || !aligned16(delta)) return D3GA_E_CONFIG;
     static_assert(D3GA_SCALE_ENERGY_GRID <= D3GA_LOSS_PARTIALS, "one partial per workgroup");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n4 = n / 4;
@@ -167,7 +158,7 @@ extern "C" int d3ga_scale_energy_bwd(int64_t n, const float *scaling, const floa
     if (n <= 0) return D3GA_E_SIZE;
     if (!scaling || !g || !grad) return D3GA_E_NULL;
     if (activation != D3GA_SCALE_ACT_EXP && activation != D3GA_SCALE_ACT_NONE) return D3GA_E_CONFIG;
-    if (!obj_aligned16(scaling) || !obj_aligned16(delta) || !obj_aligned16(grad)) return D3GA_E_CONFIG;
+    if (!aligned16(scaling) || !aligned16(delta) || !aligned16(grad)) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n4 = n / 4;
     const int nb = scale_energy_grid(n4, 2048);

@@ -16,6 +16,7 @@
 // Traffic of 3: read g, p, m, v, write p, m, v = 7 dwords per element; 1 adds one read of g.  Both are bandwidth-bound:
 // sqrt and the division are the IEEE ones.
 #include "d3ga_internal.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -66,11 +67,8 @@ static inline OptimScratch carve_optim(void *base, int64_t n_chunks, int64_t n_t
 // sum over the 256 threads of a workgroup, in a fixed order (butterfly inside a wavefront, then the four wavefronts in
 // index order); valid in thread 0.  s_red: 4 floats.
 __device__ __forceinline__ float block_sum_256(float x, float *s_red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
     __syncthreads();                                     // the previous chunk's readers are done with s_red
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = x;
-    __syncthreads();
+    wave_sums_to_lds(x, s_red);
     return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 

@@ -283,11 +283,6 @@ __global__ __launch_bounds__(kBlock) void pc_down_bwd_kernel(int C, int H, int W
     }
 }
 
-static inline unsigned pc_grid(int64_t n) {
-    const int64_t b = (n + kBlock - 1) / kBlock;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
 template <int NB>
 static void launch_conv(bool vec, bool mask, dim3 grid, hipStream_t s, int M, int H, int W, int cin, int cout, const float *x,
                         const float *mask_y, const uint4 *panel, const float *bias, int relu, int accumulate, float *y) {
@@ -362,7 +357,7 @@ extern "C" int d3ga_vgg_maxpool2_fwd_n(int32_t N, int32_t H, int32_t W, int32_t 
     if (!x || !y) return D3GA_E_NULL;
     if (x == y) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(pc_grid((int64_t)N * (H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, N, H, W, C, x, y);
+    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(grid_1d((int64_t)N * (H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, N, H, W, C, x, y);
     return check_launch(s, 0);
 }
 
@@ -370,7 +365,7 @@ extern "C" int d3ga_vgg_maxpool2_fwd(int32_t H, int32_t W, int32_t C, const floa
     if (!pc_sizes_ok(H, W, C) || H < 2 || W < 2) return D3GA_E_SIZE;
     if (!x || !y) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(pc_grid((int64_t)(H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, 1, H, W, C, x, y);
+    hipLaunchKernelGGL(pc_pool_fwd_kernel, dim3(grid_1d((int64_t)(H / 2) * (W / 2) * C)), dim3(kBlock), 0, s, 1, H, W, C, x, y);
     return check_launch(s, 0);
 }
 
@@ -379,7 +374,7 @@ extern "C" int d3ga_vgg_maxpool2_bwd(int32_t H, int32_t W, int32_t C, const floa
     if (!pc_sizes_ok(H, W, C) || H < 2 || W < 2) return D3GA_E_SIZE;
     if (!x || !gy || !gx) return D3GA_E_NULL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pc_pool_bwd_kernel, dim3(pc_grid((int64_t)H * W * C)), dim3(kBlock), 0, s, H, W, C, x, gy, gx);
+    hipLaunchKernelGGL(pc_pool_bwd_kernel, dim3(grid_1d((int64_t)H * W * C)), dim3(kBlock), 0, s, H, W, C, x, gy, gx);
     return check_launch(s, 0);
 }
 
@@ -390,7 +385,7 @@ extern "C" int d3ga_vgg_box_down2_fwd(int32_t C, int32_t H, int32_t W, int32_t d
     if (down & ~1) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = down ? (int64_t)(H / 2) * (W / 2) * C : (int64_t)H * W * C;
-    hipLaunchKernelGGL(pc_down_fwd_kernel, dim3(pc_grid(n)), dim3(kBlock), 0, s, C, H, W, down, img, out);
+    hipLaunchKernelGGL(pc_down_fwd_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, C, H, W, down, img, out);
     return check_launch(s, 0);
 }
 
@@ -400,7 +395,7 @@ extern "C" int d3ga_vgg_box_down2_bwd(int32_t C, int32_t H, int32_t W, int32_t d
     if (!g || !g_img) return D3GA_E_NULL;
     if (down & ~1) return D3GA_E_CONFIG;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pc_down_bwd_kernel, dim3(pc_grid((int64_t)H * W * C)), dim3(kBlock), 0, s, C, H, W, down, g, g_img);
+    hipLaunchKernelGGL(pc_down_bwd_kernel, dim3(grid_1d((int64_t)H * W * C)), dim3(kBlock), 0, s, C, H, W, down, g, g_img);
     return check_launch(s, 0);
 }
 

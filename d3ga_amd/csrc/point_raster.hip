@@ -24,6 +24,7 @@
 // d3ga_points_composite is a per-pixel gather over the fragments.
 #include "d3ga_internal.h"
 #include "point_raster_math.h"
+#include "wave_prims.h"
 
 namespace d3ga {
 
@@ -146,53 +147,16 @@ static __global__ __launch_bounds__(kBlock) void points_count_kernel(int64_t BP,
 static __global__ __launch_bounds__(kBlock) void points_local_kernel(const uint32_t *__restrict__ count, uint32_t *__restrict__ local,
                                                                      uint32_t *__restrict__ block_total) {
     __shared__ uint32_t s_wave[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t t = (int64_t)blockIdx.x * kBlock + tid;
-    const uint32_t c = count[t];                 // count holds nblk * kBlock words, the padding cleared with the rest
-    uint32_t incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) before += s_wave[w];
-        total += s_wave[w];
-    }
-    local[t] = before + incl - c;
-    if (tid == 0) block_total[blockIdx.x] = total;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint32_t total;                              // (count holds nblk * kBlock words, the padding cleared with the rest)
+    local[t] = block_excl_scan_u32<kBlock / 64>(count[t], s_wave, &total);
+    if (threadIdx.x == 0) block_total[blockIdx.x] = total;
 }
 
 static __global__ __launch_bounds__(kPointScanBlock) void points_scan_kernel(int64_t nblk, const uint32_t *__restrict__ block_total,
                                                                              uint64_t *__restrict__ block_start) {
     __shared__ uint64_t s_wave[kPointScanBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t carry = 0;
-    for (int64_t base = 0; base < nblk; base += kPointScanBlock) {
-        const int64_t i = base + tid;
-        const uint64_t v = i < nblk ? (uint64_t)block_total[i] : 0;
-        uint64_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t lo = __shfl_up((uint32_t)incl, off), hi = __shfl_up((uint32_t)(incl >> 32), off);
-            if (lane >= off) incl += ((uint64_t)hi << 32) | lo;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint64_t before = 0, total = 0;
-        for (int w = 0; w < kPointScanBlock / 64; ++w) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
-        if (i < nblk) block_start[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) block_start[nblk] = carry;
+    scan_block_totals<kPointScanBlock>(nblk, block_total, block_start, s_wave);
 }
 
 static __global__ __launch_bounds__(kBlock) void points_scatter_kernel(int64_t BP, int P, PointFrame fr, int64_t capacity,
@@ -278,11 +242,6 @@ static __global__ __launch_bounds__(kBlock) void points_composite_kernel(int64_t
     }
 }
 
-static inline unsigned point_grid(int64_t n) {
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > kPointMaxGrid ? kPointMaxGrid : blocks));
-}
-
 template <int K>
 static void launch_tiles(int64_t n_tiles, int64_t nblk, const PointFrame &fr, int64_t capacity, const PointScratch &sc, int32_t *idx, float *zbuf,
                          float *dists, hipStream_t s) {
@@ -306,7 +265,6 @@ static inline int point_settings(int32_t K, float radius) {
     if (!(radius > 0.f) || !(radius <= 3.0e38f)) return D3GA_E_CONFIG;
     return D3GA_OK;
 }
-static inline bool point_unaligned(const void *p, uintptr_t mask = 3) { return ((uintptr_t)p & mask) != 0; }
 
 extern "C" int d3ga_points_raster_scratch_bytes(int32_t B, int32_t P, int32_t H, int32_t W, float radius, size_t *bytes) {
     D3GA_TRY(point_sizes(B, P, H, W));
@@ -325,8 +283,8 @@ extern "C" int d3ga_points_rasterize(int32_t B, int32_t P, int32_t H, int32_t W,
     const int64_t capacity = point_capacity(B, P, H, W, radius);
     if (capacity < 0) return D3GA_E_SIZE;
     if (!scratch || !idx || !cams || (P > 0 && !points)) return D3GA_E_NULL;
-    if (point_unaligned(points) || point_unaligned(cams) || point_unaligned(scratch, 15) || point_unaligned(idx) || point_unaligned(zbuf) ||
-        point_unaligned(dists))
+    if (misaligned(points) || misaligned(cams) || misaligned(scratch, 15) || misaligned(idx) || misaligned(zbuf) ||
+        misaligned(dists))
         return D3GA_E_CONFIG;
     if (B == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -336,7 +294,7 @@ extern "C" int d3ga_points_rasterize(int32_t B, int32_t P, int32_t H, int32_t W,
     fr.r_px = point_radius_px(radius, H, W); fr.s2 = point_ndc_scale2(H, W); fr.r2 = radius * radius;
     const int64_t BP = (int64_t)B * P, n_tiles = (int64_t)B * fr.tiles_x * fr.tiles_y, nblk = point_blocks(B, H, W);
     const PointScratch sc = carve_points(scratch, B, H, W);
-    hipLaunchKernelGGL(points_clear_kernel, dim3(point_grid(nblk * kBlock)), dim3(kBlock), 0, s, sc.count, nblk * kBlock);
+    hipLaunchKernelGGL(points_clear_kernel, dim3(grid_1d(nblk * kBlock)), dim3(kBlock), 0, s, sc.count, nblk * kBlock);
     if (BP > 0)
         hipLaunchKernelGGL(points_count_kernel, dim3((unsigned)((BP + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, BP, P, fr, points, cams, sc.count);
     hipLaunchKernelGGL(points_local_kernel, dim3((unsigned)nblk), dim3(kBlock), 0, s, sc.count, sc.local, sc.block_total);
@@ -362,12 +320,12 @@ extern "C" int d3ga_points_composite(int32_t B, int32_t P, int32_t H, int32_t W,
     D3GA_TRY(point_sizes(B, P, H, W));
     D3GA_TRY(point_settings(K, radius));
     if (!idx || !dists || !bg || !image) return D3GA_E_NULL;
-    if (point_unaligned(idx) || point_unaligned(dists) || point_unaligned(colors) || point_unaligned(image)) return D3GA_E_CONFIG;
+    if (misaligned(idx) || misaligned(dists) || misaligned(colors) || misaligned(image)) return D3GA_E_CONFIG;
     if (B == 0) return D3GA_OK;
     hipStream_t s = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W, n = hw * B;
     PointBg b;
     b.v[0] = bg[0]; b.v[1] = bg[1]; b.v[2] = bg[2];
-    hipLaunchKernelGGL(points_composite_kernel, dim3(point_grid(n)), dim3(kBlock), 0, s, n, hw, P, K, radius * radius, idx, dists, colors, b, image);
+    hipLaunchKernelGGL(points_composite_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, s, n, hw, P, K, radius * radius, idx, dists, colors, b, image);
     return check_launch(s, 0);
 }

@@ -647,14 +647,11 @@ extern "C" int d3ga_raster_bin_sort(const d3ga_raster_params *prm, void *geom, v
     // (... and running the two list kernels on a side stream beside the per-tile kernel -- fork / join events, parallel graph
     // branches under capture: the events cost more than the overlap saves, bin+sort 49 -> 64 us eager, step 0.409 -> 0.422 ms.)
     {   // > 64 KiB of dynamic LDS needs an explicit opt-in, once per device (function attributes are per device)
-        static std::atomic<bool> attr_set[64] = {};
-        int dev = 0;
-        D3GA_HIP(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev].load(std::memory_order_relaxed)) {
-            D3GA_HIP(hipFuncSetAttribute((const void *)tile_sort_lds_list_kernel<1024, kSortLarge>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds_bytes(kSortLarge, 1024, true)));
-            attr_set[dev].store(true, std::memory_order_relaxed);
-        }
+        static PerDeviceOnce once;
+        D3GA_TRY(once.run([] {
+            return (int)hipFuncSetAttribute((const void *)tile_sort_lds_list_kernel<1024, kSortLarge>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds_bytes(kSortLarge, 1024, true));
+        }));
     }
     // (48 KB of LDS: three workgroups of the 2049..4096 class fit a CU -- at 4K with 2M Gaussians thousands of tiles are in it;
     //  96 KB: one workgroup of the larger class per CU)
