@@ -16,6 +16,7 @@ from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Ren
                           rasterize_meshes, to_cameras, vertex_normals)
 from .png import PngBuffer, encode_png, png_bytes, save_image  # noqa: F401
 from .sample_prep import SamplePrep, prepare_actorshq, prepare_goliath  # noqa: F401
+from .mesh_labels import FaceNeighbours, LabelTransfer, face_neighbours, grow_mask_region, majority_vote, median_filter_mesh  # noqa: F401
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
@@ -25,4 +26,5 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "convert_optimizer_state", "scale_energy", "TrainingObjective", "PosePCA",
            "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter",
            "PngBuffer", "encode_png", "png_bytes", "save_image",
-           "SamplePrep", "prepare_actorshq", "prepare_goliath"]
+           "SamplePrep", "prepare_actorshq", "prepare_goliath",
+           "FaceNeighbours", "LabelTransfer", "face_neighbours", "grow_mask_region", "majority_vote", "median_filter_mesh"]

@@ -141,6 +141,9 @@ GRID_OUT_F32_CHW, GRID_OUT_F32_HWC, GRID_OUT_U8_SAVE_IMAGE, GRID_OUT_U8_CLIP = 0
 GRID_BGR, GRID_FORCE_SCALAR = 1, 2       # D3GA_GRID_*: flags of the grid
 PANEL_BOTTOM, PANEL_BOLD = 1, 2          # D3GA_PANEL_*: flags of a panel
 PNG_FILTER_ADAPTIVE = 5                  # D3GA_PNG_FILTER_ADAPTIVE: filter argument of d3ga_png_encode (0..4 force a type)
+LABELS_MAX, LABEL_RINGS_MAX = 32, 4096   # D3GA_LABELS_MAX, D3GA_LABEL_RINGS_MAX (include/d3ga.h): columns of a label histogram, rings of one growth call
+LABEL_EVERY_PIXEL = 1                    # D3GA_LABEL_EVERY_PIXEL: flag of d3ga_label_vote (measurement only)
+LABEL_STATUS_RANGE = 1                   # D3GA_LABEL_STATUS_RANGE: bit of the vote's status word
 
 
 class GridPanel(ctypes.Structure):
@@ -323,6 +326,10 @@ _SIGNATURES = {
                                   [ctypes.POINTER(ctypes.c_int32), _vp], _i),
     "d3ga_sample_prep_goliath": ([ctypes.c_int32] * 3 + [_vp, _i64, _i64, _i64, _vp, _i64, _i64] + [_vp] * 4 +
                                  [ctypes.POINTER(ctypes.c_int32), _vp], _i),
+    "d3ga_label_vote": ([ctypes.c_int32] * 5 + [_vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp, _vp, ctypes.c_int32, _vp], _i),
+    "d3ga_label_majority": ([ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
+    "d3ga_label_median": ([ctypes.c_int32] + [_vp] * 3 + [_vp], _i),
+    "d3ga_label_grow": ([ctypes.c_int32] * 2 + [_vp] * 4 + [_vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -34,6 +34,12 @@ __device__ __forceinline__ void wave_sums_to_lds(T v, T *s_part) {
     __syncthreads();
 }
 
+// The value lane + 1 holds, by a lane shift; lane 63 has no successor and gets `last`.  Every lane of the wavefront must call.
+__device__ __forceinline__ int32_t wave_next_lane(int32_t v, int32_t last) {
+    const int32_t n = __shfl_down(v, 1);
+    return (threadIdx.x & 63) == 63 ? last : n;
+}
+
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {

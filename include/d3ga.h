@@ -1451,6 +1451,52 @@ int d3ga_sample_prep_goliath(int32_t B, int32_t H, int32_t W, const uint8_t *ima
                              int64_t image_frame, const uint8_t *parts, int64_t parts_pitch, int64_t parts_frame, float *image_out,
                              float *seg_part_out, float *seg_fg_out, float *boundary_out, int32_t *path, d3ga_stream_t stream);
 
+/* ---- Part-label transfer onto a mesh (csrc/mesh_labels.hip, csrc/mesh_labels_math.h) ------------------------------
+ * What lib/segmentation.py::Segmenter.run does between the rasterizer's fragments and face_to_label.npy (Renderer.forward
+ * :59-74, majority_vote :112-123, utils/mesh_utils.py::median_filter_mesh) and lib/cage.py::grow_mask_region :131-153.  All
+ * integer, forward only, no host synchronisation, capturable; results do not depend on scheduling.
+ *   neighbours (F,3) int32, -1 padded: per face the faces across those of its three edges that occur in exactly two faces
+ *   (trimesh's face_adjacency rule, built on the host; a pair that shares two edges appears twice).  An entry outside [0, F)
+ *   counts as absent.
+ * d3ga_label_vote: B views of H x W vote once each for every face they show.  Two launches.
+ *   pick       per view and face f: the pixel with the largest y W + x among those with pix_to_face == f (the last in raster
+ *              order: what the reference's index-put keeps on the CPU); none: no vote.  pix_to_face (B,H,W) int32, per-mesh
+ *              indices as d3ga_mesh_rasterize writes them; values < 0 or >= F are ignored.
+ *   labels     the label image, int32 (label_u8 = 0) or uint8 (1): pixel (b, y, x) at byte  labels + b label_frame +
+ *              y label_pitch + x elem  -- (B,1,H,W) and (B,H,W) views, row-padded buffers.  With B == 1 label_frame is not read.
+ *   hist       (F,L) int32, L <= D3GA_LABELS_MAX: a pick with label l in [0, L) adds 1 to hist[f][l] (column 0: the views that
+ *              saw the face as background); any other label adds nothing and sets D3GA_LABEL_STATUS_RANGE in *status (sticky:
+ *              the word is only ever or-ed into).  Every view votes on its own -- a departure from the reference at B > 1, where
+ *              the labels of a batch's views are ADDED into each other; at B = 1, its default, the results are the same.
+ *   cells      (B,F) uint32 scratch, ALL ZERO on entry and all zero again on exit (the second launch writes back what the
+ *              first one set): clear it once.
+ *   flags      0, or D3GA_LABEL_EVERY_PIXEL: every pixel sends its atomic (without it a pixel whose right neighbour in the same
+ *              wavefront shows the same face sends none).  The results are the same; the flag exists for the measurement.
+ * d3ga_label_majority: hist (F,L) -> labels (F,): over labels 1 .. L-1 the largest count, ties to the smallest label; all 0 -> 0.
+ * d3ga_label_median: out[f] = the median of labels[n] over f's neighbours (f itself not among them): one -> it, two ->
+ *   (a + b) / 2 (labels are not negative), three -> the middle one, none -> labels[f] (the reference raises KeyError there).
+ *   out must not be labels.
+ * d3ga_label_grow: n_rings rounds of  out[j] = mask[j] | any(i qualifies for i in N(j)),  i qualifying when
+ *   0 < #{n in N(i): mask[n]} < #N(i) with duplicates counted on both sides; every round reads the previous round's result only.
+ *   mask, out (F,) uint8 (non-zero = set; out holds 0 / 1), no byte in common; scratch 2 F bytes, no byte in common with either, read and
+ *   written with n_rings >= 2 only (else may be NULL).  n_rings = 0 copies.  One launch per ring, all enqueued by this call.
+ *   Status, nothing launched: a size <= 0, L > D3GA_LABELS_MAX, B > 65535, H W >= INT32_MAX, more than
+ *   262140 rows, B F or F L or 3 F > INT32_MAX, n_rings outside [0, D3GA_LABEL_RINGS_MAX] D3GA_E_SIZE; label_u8 outside {0, 1}, an
+ *   unknown flag, a pitch smaller than its row, with B > 1 a frame stride smaller than what it spans, an int32 pointer (or int32
+ *   label pitch / frame stride) that is no multiple of 4, or buffers that must differ and do not D3GA_E_CONFIG; a required pointer
+ *   NULL D3GA_E_NULL.  Sizes are tested first. */
+#define D3GA_LABELS_MAX 32
+#define D3GA_LABEL_RINGS_MAX 4096
+#define D3GA_LABEL_EVERY_PIXEL 1
+#define D3GA_LABEL_STATUS_RANGE 1
+int d3ga_label_vote(int32_t B, int32_t F, int32_t L, int32_t H, int32_t W, const int32_t *pix_to_face, const void *labels, int32_t label_u8,
+                    int64_t label_pitch, int64_t label_frame, uint32_t *cells, int32_t *hist, uint32_t *status, int32_t flags,
+                    d3ga_stream_t stream);
+int d3ga_label_majority(int32_t F, int32_t L, const int32_t *hist, int32_t *labels, d3ga_stream_t stream);
+int d3ga_label_median(int32_t F, const int32_t *neighbours, const int32_t *labels, int32_t *out, d3ga_stream_t stream);
+int d3ga_label_grow(int32_t F, int32_t n_rings, const int32_t *neighbours, const uint8_t *mask, uint8_t *out, uint8_t *scratch,
+                    d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
