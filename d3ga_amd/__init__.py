@@ -17,6 +17,8 @@ from .mesh_render import (Fragments, MeshCameras, MeshScratch, MeshTopology, Ren
 from .png import PngBuffer, encode_png, png_bytes, save_image  # noqa: F401
 from .sample_prep import SamplePrep, prepare_actorshq, prepare_goliath  # noqa: F401
 from .mesh_labels import FaceNeighbours, LabelTransfer, face_neighbours, grow_mask_region, majority_vote, median_filter_mesh  # noqa: F401
+from .gauss_init import (SurfaceSamples, body_surface_draws, inflate, init_cage_parameters, sample_initial_points,  # noqa: F401
+                         sample_surface, vertex_normals_angle)
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
@@ -27,4 +29,6 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "Panel", "compose_grid", "compose_panels", "to_uint8", "write_text", "GridWriter",
            "PngBuffer", "encode_png", "png_bytes", "save_image",
            "SamplePrep", "prepare_actorshq", "prepare_goliath",
-           "FaceNeighbours", "LabelTransfer", "face_neighbours", "grow_mask_region", "majority_vote", "median_filter_mesh"]
+           "FaceNeighbours", "LabelTransfer", "face_neighbours", "grow_mask_region", "majority_vote", "median_filter_mesh",
+           "SurfaceSamples", "sample_surface", "vertex_normals_angle", "inflate", "body_surface_draws", "sample_initial_points",
+           "init_cage_parameters"]

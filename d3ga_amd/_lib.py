@@ -144,6 +144,8 @@ PNG_FILTER_ADAPTIVE = 5                  # D3GA_PNG_FILTER_ADAPTIVE: filter argu
 LABELS_MAX, LABEL_RINGS_MAX = 32, 4096   # D3GA_LABELS_MAX, D3GA_LABEL_RINGS_MAX (include/d3ga.h): columns of a label histogram, rings of one growth call
 LABEL_EVERY_PIXEL = 1                    # D3GA_LABEL_EVERY_PIXEL: flag of d3ga_label_vote (measurement only)
 LABEL_STATUS_RANGE = 1                   # D3GA_LABEL_STATUS_RANGE: bit of the vote's status word
+SAMPLE_MAX_FACES = 1 << 24               # D3GA_SAMPLE_MAX_FACES (include/d3ga.h): d3ga_surface_sample takes fewer faces than this
+SAMPLE_STATUS_EMPTY, SAMPLE_STATUS_RANGE = 1, 2    # D3GA_SAMPLE_STATUS_*: bits of the surface sampler's status word
 
 
 class GridPanel(ctypes.Structure):
@@ -330,6 +332,9 @@ _SIGNATURES = {
     "d3ga_label_majority": ([ctypes.c_int32] * 2 + [_vp, _vp, _vp], _i),
     "d3ga_label_median": ([ctypes.c_int32] + [_vp] * 3 + [_vp], _i),
     "d3ga_label_grow": ([ctypes.c_int32] * 2 + [_vp] * 4 + [_vp], _i),
+    "d3ga_surface_sample_scratch_bytes": ([ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_surface_sample": ([ctypes.c_int32] * 3 + [_vp] * 10 + [_i64, _vp, ctypes.c_int32, _vp], _i),
+    "d3ga_vertex_normals_angle": ([ctypes.c_int32] * 2 + [_vp] * 4 + [ctypes.c_double] + [_vp] * 3 + [_vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -72,10 +72,34 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t count, uint32_t
     return before + incl - count;
 }
 
-// The second level: ONE workgroup of BLOCK lanes turns the nblk workgroup totals into their exclusive 64-bit prefix, BLOCK at a
-// time with the running total carried along; block_start[nblk] = the total of all.  s_wave: BLOCK / 64 words of LDS.
-template <int BLOCK>
-__device__ __forceinline__ void scan_block_totals(int64_t nblk, const uint32_t *__restrict__ block_total,
+// The same over 64-bit values, inclusive: the prefix of `v` up to and including this lane, and the workgroup's total in every
+// lane.  s_wave: NW 64-bit words of LDS.  Every lane of the workgroup must call this (one barrier inside).
+template <int NW>
+__device__ __forceinline__ uint64_t block_incl_scan_u64(uint64_t v, uint64_t *s_wave, uint64_t *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t o = shfl_up_u64(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if (w < wave) before += s_wave[w];
+        sum += s_wave[w];
+    }
+    *total = sum;
+    return before + incl;
+}
+
+// The second level: ONE workgroup of BLOCK lanes turns the nblk workgroup totals (uint32_t or uint64_t) into their exclusive
+// 64-bit prefix, BLOCK at a time with the running total carried along; block_start[nblk] = the total of all.  s_wave: BLOCK / 64
+// words of LDS.
+template <int BLOCK, typename T>
+__device__ __forceinline__ void scan_block_totals(int64_t nblk, const T *__restrict__ block_total,
                                                   uint64_t *__restrict__ block_start, uint64_t *s_wave) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t carry = 0;

@@ -1497,6 +1497,42 @@ int d3ga_label_median(int32_t F, const int32_t *neighbours, const int32_t *label
 int d3ga_label_grow(int32_t F, int32_t n_rings, const int32_t *neighbours, const uint8_t *mask, uint8_t *out, uint8_t *scratch,
                     d3ga_stream_t stream);
 
+/* ---- Gaussian initialisation: area-weighted surface samples (csrc/gauss_init.hip, csrc/gauss_init_math.h) -----------
+ * What lib/cage.py::CageBase.sample_initial_points :262-296 does between a mesh and (points, rotations, faces, barys), and the
+ * angle-weighted vertex normals behind `mesh.vertex_normals * inflate` :271-272.  float64 arithmetic, ONE rounding to float32 per
+ * output element; the face weights are INTEGERS (areas scaled by a power of two and floored), so the prefix sum is exact and the
+ * results depend on neither launch geometry nor scheduling.  The random numbers are an input.  No float atomics, no host
+ * synchronisation; capturable.  Additive to ABI 112.
+ *
+ * d3ga_surface_sample: n samples.  Five launches: clear, largest area (uint64 atomicMax over the doubles' bits), weights + scan
+ *   per block of 256 faces, scan of the block totals, one thread per sample.
+ *   verts (V,3) f64;  faces (F,3) int32;  face_mask (F) bytes or NULL (0: the face is left out);  uniforms (n,3) f64 in [0,1):
+ *   column 0 picks the face, columns 1 and 2 the point (a value outside is clamped for the pick).
+ *   points (n,3) f32;  rotations (n,4) f32 wxyz (written with 16-byte stores when 16-byte aligned);  out_faces (n,3) int32 the
+ *   vertices of the chosen face;  face_id (n) int32 its index in `faces`;  barys (n,3) f32 of the float32 point.
+ *   A face of weight 0 -- masked out, degenerate, below 2^-(62 - ceil(log2 F)) of 2^E (max area < 2^E) -- is never chosen.
+ *   scratch: d3ga_surface_sample_scratch_bytes(F) bytes, 256-byte aligned; needs no initialisation and is reusable.
+ *   status (sticky, OR-ed): D3GA_SAMPLE_STATUS_EMPTY when every weight is 0 (the outputs are then zeros, face_id -1);
+ *   D3GA_SAMPLE_STATUS_RANGE when a face names a vertex outside [0, V) (such a face weighs 0 and nothing is read for it).
+ *   block: lanes per workgroup of the per-sample launch, 0 (= 256), 64, 128, 256, 512 or 1024; the results do not depend on it.
+ * d3ga_vertex_normals_angle: n_v = normalize(sum over v's faces, in list order, of angle_f(v) normalize(e0 x e1)), zero for a
+ *   zero sum; normalize = x / max(|x|, 1e-12).  csr_offsets (V+1), csr_faces: the faces of every vertex, ascending.  normals (V,3)
+ *   f64 and / or inflated (V,3) f64 = verts + amount normals; either may be NULL, neither may be verts.  One launch.  A list entry
+ *   outside [0, F), a face that does not touch its vertex or names one outside [0, V) is skipped and sets D3GA_SAMPLE_STATUS_RANGE.
+ *   Status, nothing launched: V, F, n <= 0, F >= D3GA_SAMPLE_MAX_FACES, 3 V or 4 n > INT32_MAX D3GA_E_SIZE; an unknown block, an
+ *   amount that is not finite, a pointer not aligned to its element (scratch: 256 bytes) or an output that is verts
+ *   D3GA_E_CONFIG; a required pointer NULL D3GA_E_NULL; scratch_bytes too small D3GA_E_CAPACITY.  Sizes are tested first. */
+#define D3GA_SAMPLE_MAX_FACES 16777216 /* 2^24 */
+#define D3GA_SAMPLE_STATUS_EMPTY 1
+#define D3GA_SAMPLE_STATUS_RANGE 2
+int d3ga_surface_sample_scratch_bytes(int32_t F, int64_t *bytes);
+int d3ga_surface_sample(int32_t V, int32_t F, int32_t n, const double *verts, const int32_t *faces, const uint8_t *face_mask,
+                        const double *uniforms, float *points, float *rotations, int32_t *out_faces, int32_t *face_id, float *barys,
+                        void *scratch, int64_t scratch_bytes, uint32_t *status, int32_t block, d3ga_stream_t stream);
+int d3ga_vertex_normals_angle(int32_t V, int32_t F, const double *verts, const int32_t *faces, const int32_t *csr_offsets,
+                              const int32_t *csr_faces, double amount, double *normals, double *inflated, uint32_t *status,
+                              d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
