@@ -19,6 +19,8 @@ from .sample_prep import SamplePrep, prepare_actorshq, prepare_goliath  # noqa: 
 from .mesh_labels import FaceNeighbours, LabelTransfer, face_neighbours, grow_mask_region, majority_vote, median_filter_mesh  # noqa: F401
 from .gauss_init import (SurfaceSamples, body_surface_draws, inflate, init_cage_parameters, sample_initial_points,  # noqa: F401
                          sample_surface, vertex_normals_angle)
+from .template_bind import (CageBinding, LoopPlan, TemplateBinding, Unposed, beta_table, bind_body_template, bind_cage,  # noqa: F401
+                            bind_cage_skin, loop_plan, loop_subdivide, nearest_vertex, star_pose, unpose)
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
 __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "compute_heatmap", "error_heatmap", "psnr", "LPIPS",
@@ -31,4 +33,6 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "SamplePrep", "prepare_actorshq", "prepare_goliath",
            "FaceNeighbours", "LabelTransfer", "face_neighbours", "grow_mask_region", "majority_vote", "median_filter_mesh",
            "SurfaceSamples", "sample_surface", "vertex_normals_angle", "inflate", "body_surface_draws", "sample_initial_points",
-           "init_cage_parameters"]
+           "init_cage_parameters",
+           "LoopPlan", "loop_plan", "loop_subdivide", "beta_table", "nearest_vertex", "Unposed", "unpose", "star_pose", "TemplateBinding",
+           "bind_body_template", "CageBinding", "bind_cage", "bind_cage_skin"]

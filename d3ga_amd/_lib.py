@@ -146,6 +146,15 @@ LABEL_EVERY_PIXEL = 1                    # D3GA_LABEL_EVERY_PIXEL: flag of d3ga_
 LABEL_STATUS_RANGE = 1                   # D3GA_LABEL_STATUS_RANGE: bit of the vote's status word
 SAMPLE_MAX_FACES = 1 << 24               # D3GA_SAMPLE_MAX_FACES (include/d3ga.h): d3ga_surface_sample takes fewer faces than this
 SAMPLE_STATUS_EMPTY, SAMPLE_STATUS_RANGE = 1, 2    # D3GA_SAMPLE_STATUS_*: bits of the surface sampler's status word
+BIND_STATUS_RANGE, BIND_STATUS_NONMANIFOLD, BIND_STATUS_DEGENERATE, BIND_STATUS_SINGULAR = 1, 2, 4, 8    # D3GA_BIND_STATUS_*: template binding
+LOOP_BAD_KEY = 2 ** 63 - 1                         # D3GA_LOOP_BAD_KEY: the key of a face that takes no part in a Loop plan
+
+
+class LoopPlanTables(ctypes.Structure):
+    """struct d3ga_loop_plan (include/d3ga.h): sizes and device tables of one level of Loop subdivision."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("V", "F", "E", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("edge_verts", "edge_opp", "edge_faces", "edge_boundary", "face_edge", "vert_offsets",
+                                               "vert_nbr", "vert_boundary")]
 
 
 class GridPanel(ctypes.Structure):
@@ -335,6 +344,12 @@ _SIGNATURES = {
     "d3ga_surface_sample_scratch_bytes": ([ctypes.c_int32, ctypes.POINTER(_i64)], _i),
     "d3ga_surface_sample": ([ctypes.c_int32] * 3 + [_vp] * 10 + [_i64, _vp, ctypes.c_int32, _vp], _i),
     "d3ga_vertex_normals_angle": ([ctypes.c_int32] * 2 + [_vp] * 4 + [ctypes.c_double] + [_vp] * 3 + [_vp], _i),
+    "d3ga_loop_edge_keys": ([ctypes.c_int32] * 2 + [_vp] * 3 + [_vp], _i),
+    "d3ga_loop_plan_scratch_bytes": ([ctypes.c_int32] * 2 + [ctypes.POINTER(_i64)], _i),
+    "d3ga_loop_plan_build": ([ctypes.POINTER(LoopPlanTables)] + [_vp] * 5 + [_i64, _vp], _i),
+    "d3ga_loop_subdivide": ([ctypes.POINTER(LoopPlanTables), ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_loop_faces": ([ctypes.POINTER(LoopPlanTables), _vp, _vp, _vp], _i),
+    "d3ga_unpose": ([ctypes.c_int32] * 4 + [_vp] * 3 + [ctypes.c_int32] + [_vp] * 3 + [ctypes.c_int32, _vp, _vp, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1533,6 +1533,64 @@ int d3ga_vertex_normals_angle(int32_t V, int32_t F, const double *verts, const i
                               const int32_t *csr_faces, double amount, double *normals, double *inflated, uint32_t *status,
                               d3ga_stream_t stream);
 
+/* ---- Template binding: Loop subdivision with attribute columns, unpose (csrc/template_bind.hip, csrc/template_bind_math.h;
+ * DESIGN.md 4.4t) ---------------------------------------------------------------------------------------------------------------
+ * What lib/smplman.py::Smplman.create_body_model :67-110 and lib/cage_smplman.py::CageSmpl.create_cage_model :54-76 need between a
+ * body model and (skin_weights, nn_ids, body_template_vertices): utils/mesh_utils.py::subdivide_loop :105-325 and Smplman.unpose
+ * :55-59.  float64 arithmetic, ONE rounding to float32 per output element, every sum in a fixed order (the header states them); no
+ * float atomics; the results depend on neither launch geometry nor scheduling.  No host synchronisation.  Additive to ABI 112.
+ *
+ * One level of topology is a d3ga_loop_plan.  Unique edges are numbered in ascending order of (larger endpoint, smaller endpoint).
+ *   d3ga_loop_edge_keys: keys[3 f + c] = larger << 32 | smaller of face edge c = (faces[f][c], faces[f][(c + 1) % 3]); a face that names
+ *     a vertex outside [0, V) (D3GA_BIND_STATUS_RANGE) or one vertex twice (D3GA_BIND_STATUS_DEGENERATE) gets D3GA_LOOP_BAD_KEY three
+ *     times and takes no part in the plan.  The caller sorts the keys (stable, ascending) and passes them on with the permutation.
+ *   d3ga_loop_plan_build: fills the tables of `plan` (every table sized for E = 3 F; plan->E is not read) from the sorted keys and
+ *     `perm` (sorted position -> face edge).  info (4 int32): [0] = E, [1] = the largest valence, [2] = the status word (sticky:
+ *     OR-ed, never cleared -- pass it to d3ga_loop_edge_keys as well), [3] unused.  An edge in three or more faces sets D3GA_BIND_STATUS_NONMANIFOLD (its first two faces are kept).  A vertex is a
+ *     boundary vertex when it is an end of an edge of one face.  Neighbour lists are ascending.  scratch:
+ *     d3ga_loop_plan_scratch_bytes(V, F) bytes, 256-byte aligned, no initialisation needed.
+ *   d3ga_loop_subdivide: x (V, D) f64 -> out (V + E, D) f32; rows 0..V-1 the even vertices, row V + e the odd vertex of edge e.
+ *     odd, interior: 0.375 x0 + 0.375 x1 + x2 / 8 + x3 / 8 (x0 the smaller endpoint, x2 opposite in the face of lower index), left to
+ *     right; odd, boundary: (x0 + x1) / 2; even, interior: beta[k] S + (1 - k beta[k]) x, S the neighbours' sum in ascending index
+ *     order; even, boundary: S' / 8 + 0.75 x, S' over the neighbours that are boundary vertices (every one, also across an interior
+ *     edge); a vertex of no face: x.  beta (n_beta) f64 on the device, indexed by valence k; n_beta > the largest valence.
+ *   d3ga_loop_faces: face f = (a, b, c) -> rows 4f..4f+3 = (a,o0,o2), (o0,b,o1), (o2,o1,c), (o0,o1,o2), o_c = V + face_edge[3 f + c].
+ * d3ga_unpose: x_i = M^-1 (v_i - t / s) - offsets[r], r = rows[i] (rows NULL: r = i), [M t; 0 0 0 s] = sum_j w_rj A_j in float64, M^-1
+ *   the cofactor inverse.  Terms of weight 0 are skipped, the others are added in stored order.  vertices (n,3) f64; joint_mats
+ *   (J,4,4) f64 row-major (the bottom rows are taken as 0 0 0 1); skin_w (R, K) f32 (w_f64 = 0) or f64 (1); skin_idx (R, K) int32, or
+ *   NULL for the dense table (K = J); rows (n) int64 or NULL; offsets (n_offsets, 3) f64 or NULL; out (n,3) f32.  |det M| or |s|
+ *   below 1e-12 (or not a number) sets D3GA_BIND_STATUS_SINGULAR and the row is zeros; a row or a joint outside its table sets
+ *   D3GA_BIND_STATUS_RANGE (the row is zeros, the joint is skipped).  One launch.
+ *   Status, nothing launched: V, F, D, n, J, R, K <= 0, 6 F > INT32_MAX, R K or 16 J > INT32_MAX, K != J with the dense table D3GA_E_SIZE; a
+ *   required pointer NULL D3GA_E_NULL; a pointer not aligned to its element (scratch: 256 bytes) D3GA_E_CONFIG; scratch_bytes too
+ *   small D3GA_E_CAPACITY.  Sizes are tested first. */
+#define D3GA_BIND_STATUS_RANGE 1
+#define D3GA_BIND_STATUS_NONMANIFOLD 2
+#define D3GA_BIND_STATUS_DEGENERATE 4
+#define D3GA_BIND_STATUS_SINGULAR 8
+#define D3GA_LOOP_BAD_KEY 0x7fffffffffffffffLL
+typedef struct d3ga_loop_plan {
+    int32_t V, F, E, reserved;
+    int32_t *edge_verts;     /* (E,2) smaller, larger endpoint */
+    int32_t *edge_opp;       /* (E,2) the opposite vertex in the face of lower index; in the other face, or -1 */
+    int32_t *edge_faces;     /* (E,2) the face of lower index; the other face, or -1 */
+    uint8_t *edge_boundary;  /* (E) 1: the edge has one face */
+    int32_t *face_edge;      /* (3 F) face edge -> unique edge (-1: a face that takes no part) */
+    int32_t *vert_offsets;   /* (V + 1) */
+    int32_t *vert_nbr;       /* (2 E) the neighbours of every vertex, ascending */
+    uint8_t *vert_boundary;  /* (V) */
+} d3ga_loop_plan;
+int d3ga_loop_edge_keys(int32_t V, int32_t F, const int32_t *faces, int64_t *keys, uint32_t *status, d3ga_stream_t stream);
+int d3ga_loop_plan_scratch_bytes(int32_t V, int32_t F, int64_t *bytes);
+int d3ga_loop_plan_build(const d3ga_loop_plan *plan, const int32_t *faces, const int64_t *sorted_keys, const int64_t *perm, int32_t *info,
+                         void *scratch, int64_t scratch_bytes, d3ga_stream_t stream);
+int d3ga_loop_subdivide(const d3ga_loop_plan *plan, int32_t D, const double *x, const double *beta, int32_t n_beta, float *out,
+                        uint32_t *status, d3ga_stream_t stream);
+int d3ga_loop_faces(const d3ga_loop_plan *plan, const int32_t *faces, int32_t *out, d3ga_stream_t stream);
+int d3ga_unpose(int32_t n, int32_t J, int32_t R, int32_t K, const double *vertices, const double *joint_mats, const void *skin_w,
+                int32_t w_f64, const int32_t *skin_idx, const int64_t *rows, const double *offsets, int32_t n_offsets, float *out,
+                uint32_t *status, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
