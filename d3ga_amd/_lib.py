@@ -157,6 +157,30 @@ class LoopPlanTables(ctypes.Structure):
                                                "vert_nbr", "vert_boundary")]
 
 
+CAGE_MAX_RADIUS, CAGE_MAX_ITERATIONS = 511, 4096   # D3GA_CAGE_MAX_* (include/d3ga.h): cage surface authoring
+CAGE_STATUS_RANGE, CAGE_STATUS_ISOLATED, CAGE_STATUS_ZERO_EDGE = 1, 2, 4    # D3GA_CAGE_STATUS_*: bits of its status words
+CAGE_FILL_BEGIN, CAGE_FILL_ROUND, CAGE_FILL_FINISH = 0, 1, 2               # D3GA_CAGE_FILL_*: stages of d3ga_cage_fill
+CAGE_SMOOTH_IMPROVED, CAGE_SMOOTH_TAUBIN = 0, 1                            # D3GA_CAGE_SMOOTH_*: modes of d3ga_cage_smooth
+CAGE_PARTS_BEGIN, CAGE_PARTS_ROUND = 0, 1                                  # D3GA_CAGE_PARTS_*: stages of d3ga_cage_components
+
+
+class VoxelGridDesc(ctypes.Structure):
+    """struct d3ga_voxel_grid (include/d3ga.h): a bit-packed occupancy grid of (2 radius + 1)^3 voxels."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("radius", "D", "W", "reserved")] + [("bits", ctypes.c_void_p)]
+
+
+class CageIsoDesc(ctypes.Structure):
+    """struct d3ga_cage_iso_desc (include/d3ga.h): where the isosurface goes and how grid coordinates map to it."""
+    _fields_ = [("n_vertices", ctypes.c_int32), ("n_faces", ctypes.c_int32), ("centre", ctypes.c_double * 3), ("scale", ctypes.c_double * 3),
+                ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p)]
+
+
+class CageSmoothDesc(ctypes.Structure):
+    """struct d3ga_cage_smooth_desc (include/d3ga.h): one run of a smoother."""
+    _fields_ = [("mode", ctypes.c_int32), ("iterations", ctypes.c_int32), ("lam", ctypes.c_double), ("mu", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "work", "normals", "faces", "csr_offsets", "csr_faces", "out", "status")]
+
+
 class GridPanel(ctypes.Structure):
     """struct d3ga_grid_panel (include/d3ga.h): a source view, where it goes on the canvas, and its label."""
     _fields_ = [("src", ctypes.c_void_p), ("value", ctypes.c_void_p), ("sc", ctypes.c_int64), ("sh", ctypes.c_int64),
@@ -350,6 +374,13 @@ _SIGNATURES = {
     "d3ga_loop_subdivide": ([ctypes.POINTER(LoopPlanTables), ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp], _i),
     "d3ga_loop_faces": ([ctypes.POINTER(LoopPlanTables), _vp, _vp, _vp], _i),
     "d3ga_unpose": ([ctypes.c_int32] * 4 + [_vp] * 3 + [ctypes.c_int32] + [_vp] * 3 + [ctypes.c_int32, _vp, _vp, _vp], _i),
+    "d3ga_cage_voxelize": ([ctypes.POINTER(VoxelGridDesc), ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "d3ga_cage_fill": ([ctypes.POINTER(VoxelGridDesc), ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "d3ga_cage_iso_scratch_bytes": ([ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_cage_iso_count": ([ctypes.POINTER(VoxelGridDesc), _vp, _i64, _vp, _vp], _i),
+    "d3ga_cage_iso_emit": ([ctypes.POINTER(VoxelGridDesc), ctypes.POINTER(CageIsoDesc), _vp, _i64, _vp], _i),
+    "d3ga_cage_smooth": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(CageSmoothDesc), _vp], _i),
+    "d3ga_cage_components": ([ctypes.POINTER(LoopPlanTables), ctypes.c_int32, _vp, _vp, _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

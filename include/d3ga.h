@@ -1591,6 +1591,77 @@ int d3ga_unpose(int32_t n, int32_t J, int32_t R, int32_t K, const double *vertic
                 int32_t w_f64, const int32_t *skin_idx, const int64_t *rows, const double *offsets, int32_t n_offsets, float *out,
                 uint32_t *status, d3ga_stream_t stream);
 
+/* ---- Cage surface authoring: voxelise, fill, isosurface, smooth, parts (csrc/cage_author.hip, csrc/cage_author_math.h; DESIGN.md
+ * 4.4u) ----------------------------------------------------------------------------------------------------------------------------
+ * What cager/ops.py::cage_processor :140-148 does between the star-pose body mesh and the surface TetGen fills, without trimesh,
+ * mcubes or open3d; parity with those packages is UNPINNED -- the rules are the header's.  float64 arithmetic, one rounding to
+ * float32 per output element, fixed summation orders, integer atomics only; results depend on neither launch geometry nor
+ * scheduling.  No kernel waits on another workgroup: where a step must see the whole grid the launch boundary is the hand-off.
+ * No entry point synchronises with the host; the caller reads `changed` / `counts` back between calls.  Additive to ABI 112.
+ *
+ * A d3ga_voxel_grid is D = 2 radius + 1 voxels per axis, bit-packed along x: word ((z D + y) W + (x >> 6)), bit x & 63,
+ * W = ceil(D / 64); voxel (i,j,k) is the closed cube of side pitch = 1 / (radius + 0.1) centred at ((i,j,k) - radius) pitch.
+ *   d3ga_cage_voxelize: clears the grid, then sets every voxel some triangle meets (13-axis separating-axis test, float64, the
+ *     header's operation order; integer atomicOr).  verts (V,3) f64, faces (F,3) int32.  Geometry outside the grid is clipped.  A face
+ *     index outside [0, V) or a coordinate that is not finite sets D3GA_CAGE_STATUS_RANGE and the face is left out.
+ *   d3ga_cage_fill: scipy.ndimage.binary_fill_holes in stages.  BEGIN: outside = the empty border voxels.  ROUND: one sweep along
+ *     x, y and z, forward and back; *changed |= 1 if a bit was set (the caller clears it, reads it back and repeats ROUND until it
+ *     stays 0).  FINISH: filled = everything but outside.  `outside` and `filled` are grids' bit arrays of the same size as surface->bits.
+ *   d3ga_cage_iso_count / _emit: marching tetrahedra (six Kuhn tetrahedra per cell, the grid padded with one empty layer).  count
+ *     leaves the prefix sums in scratch (d3ga_cage_iso_scratch_bytes(radius), 256-byte aligned) and counts[0] = vertices,
+ *     counts[1] = faces (device int64); emit, with the same scratch, writes vertices (n_vertices,3) f32 =
+ *     ((x / radius - 1) + centre) / scale per coordinate and faces (n_faces,3) int32, oriented from occupied to empty.
+ *   d3ga_cage_smooth: `iterations` Jacobi iterations on x (V,3) f64 (overwritten; work and normals are (V,3) f64 scratch), neighbours
+ *     from plan->vert_offsets / vert_nbr; out (V,3) f32.  IMPROVED: the normal-aware Laplacian with step lam (mu unused); needs faces
+ *     and the vertex -> face lists csr_offsets (V+1) / csr_faces (ascending).  TAUBIN: two uniform steps per iteration, lam then mu.
+ *     Status bits: D3GA_CAGE_STATUS_ISOLATED (a vertex of no face or no neighbour), _ZERO_EDGE (a neighbour at distance 0); such a
+ *     vertex stays where it is.
+ *   d3ga_cage_components: BEGIN: label[f] = f.  ROUND: every edge of plan->edge_faces hooks the larger of its two roots to the
+ *     smaller (integer atomicMin), then every face jumps to its root; *changed |= 1 if an edge joined two roots.  At the fixed
+ *     point label[f] is the smallest face index of f's part.
+ *   Status, nothing launched: radius outside 1 .. D3GA_CAGE_MAX_RADIUS or D, W that do not belong to it, sizes <= 0 or past
+ *   INT32_MAX / 3, iterations outside 1 .. D3GA_CAGE_MAX_ITERATIONS D3GA_E_SIZE; a required pointer NULL D3GA_E_NULL; a pointer not
+ *   aligned to its element (scratch: 256 bytes), an unknown stage or mode, aliased buffers, values that are not finite D3GA_E_CONFIG;
+ *   scratch_bytes too small D3GA_E_CAPACITY. */
+#define D3GA_CAGE_MAX_RADIUS 511
+#define D3GA_CAGE_MAX_ITERATIONS 4096
+#define D3GA_CAGE_STATUS_RANGE 1
+#define D3GA_CAGE_STATUS_ISOLATED 2
+#define D3GA_CAGE_STATUS_ZERO_EDGE 4
+#define D3GA_CAGE_FILL_BEGIN 0
+#define D3GA_CAGE_FILL_ROUND 1
+#define D3GA_CAGE_FILL_FINISH 2
+#define D3GA_CAGE_SMOOTH_IMPROVED 0
+#define D3GA_CAGE_SMOOTH_TAUBIN 1
+#define D3GA_CAGE_PARTS_BEGIN 0
+#define D3GA_CAGE_PARTS_ROUND 1
+typedef struct d3ga_voxel_grid {
+    int32_t radius, D, W, reserved;
+    uint64_t *bits;          /* (D, D, W) words indexed [z][y][x >> 6] */
+} d3ga_voxel_grid;
+typedef struct d3ga_cage_iso_desc {
+    int32_t n_vertices, n_faces;     /* what d3ga_cage_iso_count reported */
+    double centre[3], scale[3];
+    float *vertices;         /* (n_vertices, 3) */
+    int32_t *faces;          /* (n_faces, 3) */
+} d3ga_cage_iso_desc;
+typedef struct d3ga_cage_smooth_desc {
+    int32_t mode, iterations;
+    double lam, mu;
+    double *x, *work, *normals;      /* (V,3) each; normals may be NULL for TAUBIN */
+    const int32_t *faces, *csr_offsets, *csr_faces;      /* IMPROVED only */
+    float *out;              /* (V,3) */
+    uint32_t *status;
+} d3ga_cage_smooth_desc;
+int d3ga_cage_voxelize(const d3ga_voxel_grid *grid, int32_t V, int32_t F, const double *verts, const int32_t *faces, uint32_t *status,
+                       d3ga_stream_t stream);
+int d3ga_cage_fill(const d3ga_voxel_grid *surface, int32_t stage, uint64_t *outside, uint64_t *filled, int32_t *changed, d3ga_stream_t stream);
+int d3ga_cage_iso_scratch_bytes(int32_t radius, int64_t *bytes);
+int d3ga_cage_iso_count(const d3ga_voxel_grid *grid, void *scratch, int64_t scratch_bytes, int64_t *counts, d3ga_stream_t stream);
+int d3ga_cage_iso_emit(const d3ga_voxel_grid *grid, const d3ga_cage_iso_desc *out, void *scratch, int64_t scratch_bytes, d3ga_stream_t stream);
+int d3ga_cage_smooth(const d3ga_loop_plan *plan, const d3ga_cage_smooth_desc *smooth, d3ga_stream_t stream);
+int d3ga_cage_components(const d3ga_loop_plan *plan, int32_t stage, int32_t *label, int32_t *changed, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
