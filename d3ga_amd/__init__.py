@@ -21,7 +21,7 @@ from .gauss_init import (SurfaceSamples, body_surface_draws, inflate, init_cage_
                          sample_surface, vertex_normals_angle)
 from .template_bind import (CageBinding, LoopPlan, TemplateBinding, Unposed, beta_table, bind_body_template, bind_cage,  # noqa: F401
                             bind_cage_skin, loop_plan, loop_subdivide, nearest_vertex, star_pose, unpose)
-from .cage_author import (Smoothed, VoxelGrid, cage_processor, create_cage, face_components, fill_holes, isosurface,  # noqa: F401
+from .cage_author import (Decimated, Smoothed, VoxelGrid, cage_processor, create_cage, decimate, face_components, fill_holes, isosurface,  # noqa: F401
                           keep_components, prepare, simplify, smooth_cage, smooth_improved, smooth_taubin, voxelize)
 from .point_render import PCRenderer, PointFragments, PointScratch, rasterize_points  # noqa: F401
 
@@ -39,4 +39,4 @@ __all__ = ["D3GAError", "lib", "library_path", "Evaluator", "compute_errors", "c
            "LoopPlan", "loop_plan", "loop_subdivide", "beta_table", "nearest_vertex", "Unposed", "unpose", "star_pose", "TemplateBinding",
            "bind_body_template", "CageBinding", "bind_cage", "bind_cage_skin",
            "VoxelGrid", "Smoothed", "prepare", "voxelize", "fill_holes", "isosurface", "smooth_improved", "smooth_taubin", "face_components",
-           "keep_components", "create_cage", "smooth_cage", "simplify", "cage_processor"]
+           "keep_components", "create_cage", "smooth_cage", "simplify", "cage_processor", "Decimated", "decimate"]

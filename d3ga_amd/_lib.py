@@ -162,6 +162,7 @@ CAGE_STATUS_RANGE, CAGE_STATUS_ISOLATED, CAGE_STATUS_ZERO_EDGE = 1, 2, 4    # D3
 CAGE_FILL_BEGIN, CAGE_FILL_ROUND, CAGE_FILL_FINISH = 0, 1, 2               # D3GA_CAGE_FILL_*: stages of d3ga_cage_fill
 CAGE_SMOOTH_IMPROVED, CAGE_SMOOTH_TAUBIN = 0, 1                            # D3GA_CAGE_SMOOTH_*: modes of d3ga_cage_smooth
 CAGE_PARTS_BEGIN, CAGE_PARTS_ROUND = 0, 1                                  # D3GA_CAGE_PARTS_*: stages of d3ga_cage_components
+CAGE_STATUS_STUCK = 8                                                      # D3GA_CAGE_STATUS_STUCK: decimation ended above its target
 
 
 class VoxelGridDesc(ctypes.Structure):
@@ -179,6 +180,14 @@ class CageSmoothDesc(ctypes.Structure):
     """struct d3ga_cage_smooth_desc (include/d3ga.h): one run of a smoother."""
     _fields_ = [("mode", ctypes.c_int32), ("iterations", ctypes.c_int32), ("lam", ctypes.c_double), ("mu", ctypes.c_double)] + \
                [(n, ctypes.c_void_p) for n in ("x", "work", "normals", "faces", "csr_offsets", "csr_faces", "out", "status")]
+
+
+class DecimateDesc(ctypes.Structure):
+    """struct d3ga_decimate_desc (include/d3ga.h): the state and the per-round tables of quadric decimation."""
+    _fields_ = [("n_admit", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "quadrics", "faces", "csr_offsets", "csr_faces", "keys", "placement", "sorted_keys", "owner",
+                                               "remap", "faces_out", "scratch")] + \
+               [("scratch_bytes", ctypes.c_int64), ("counts", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 class GridPanel(ctypes.Structure):
@@ -381,6 +390,12 @@ _SIGNATURES = {
     "d3ga_cage_iso_emit": ([ctypes.POINTER(VoxelGridDesc), ctypes.POINTER(CageIsoDesc), _vp, _i64, _vp], _i),
     "d3ga_cage_smooth": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(CageSmoothDesc), _vp], _i),
     "d3ga_cage_components": ([ctypes.POINTER(LoopPlanTables), ctypes.c_int32, _vp, _vp, _vp], _i),
+    # quadric decimation (decimate.hip)
+    "d3ga_decimate_scratch_bytes": ([ctypes.c_int32, ctypes.POINTER(_i64)], _i),
+    "d3ga_decimate_quadrics": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(DecimateDesc), _vp], _i),
+    "d3ga_decimate_candidates": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(DecimateDesc), _vp], _i),
+    "d3ga_decimate_collapse": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(DecimateDesc), _vp], _i),
+    "d3ga_decimate_faces": ([ctypes.POINTER(LoopPlanTables), ctypes.POINTER(DecimateDesc), _vp], _i),
 }
 EXPORTS = tuple(_SIGNATURES)
 

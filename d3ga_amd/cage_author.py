@@ -4,6 +4,7 @@ TetGen fills -- with no trimesh, no mcubes, no open3d and no pass through the ho
     cager/ops.py:63-96    create_cage (scale, inflate, centre, voxelise, fill, isosurface)      prepare, voxelize, isosurface, create_cage
     cager/ops.py:38-60    smoothing(use_improved=True), 25 rounds                               smooth_improved, smooth_cage
     cager/ops.py:121-137  simplify: Taubin filter, winding, connected components                smooth_taubin, keep_components, simplify
+    cager/ops.py:127-130  simplify_quadric_decimation (open3d)                                  decimate (csrc/decimate.hip)
     cager/ops.py:140-148  cage_processor                                                        cage_processor
 
 The rules are pinned by csrc/cage_author_math.h, whose g++ build gives the kernels' bits.  Parity with trimesh's voxeliser, with
@@ -12,7 +13,9 @@ mcubes and with open3d is UNPINNED: none of them can run next to this library, s
 TETRAHEDRA (six Kuhn tetrahedra per cell) on the grid padded with one empty layer, so the surface is always closed and a
 2-manifold; Jacobi smoothers in float64 with one rounding to float32; parts labelled by their smallest face index.
 
-Departures from the reference: quadric decimation is not built (`tris_target > 0` raises NotImplementedError); `keep_components`
+Departures from the reference: quadric decimation runs only when asked for (`decimation="quadric"`; with the default None
+`tris_target > 0` raises NotImplementedError) and is this library's rule -- rounds of independent collapses, csrc/decimate_math.h -- not
+open3d's serial queue; `keep_components`
 drops the vertices no kept face names (`drop_unreferenced=False` keeps them); a smoother never writes NaN -- a vertex without
 faces or with a neighbour at distance 0 stays put and sets a status bit that `.check()` turns into ValueError; the winding repair
 is one test of the signed volume (the isosurface is outward by construction).
@@ -31,7 +34,7 @@ from .gauss_init import inflate as _inflate
 from .template_bind import LoopPlan, _as_faces, _faces_i32, loop_plan
 
 __all__ = ["VoxelGrid", "Smoothed", "prepare", "voxelize", "fill_holes", "isosurface", "smooth_improved", "smooth_taubin", "face_components",
-           "keep_components", "create_cage", "smooth_cage", "simplify", "cage_processor"]
+           "keep_components", "create_cage", "smooth_cage", "simplify", "cage_processor", "Decimated", "decimate"]
 
 _DECIMATION = "quadric decimation is not built yet; choose `radius` for the triangle count or decimate outside"
 
@@ -350,24 +353,122 @@ def smooth_cage(vertices, faces=None, num_iter=25, lbd=0.25):
     return smooth_improved(vertices, faces, num_iter, lbd).check().vertices, faces
 
 
-def simplify(vertices, faces=None, tris_target=0):
-    """cager/ops.py::simplify -> (vertices, faces): the Taubin filter, then winding and `keep_components(min_faces=70)`.
-    tris_target > 0 (quadric decimation) raises NotImplementedError."""
-    tris_target = _count("simplify", "tris_target", tris_target, 0, 2 ** 31 - 1)
-    if tris_target > 0:
+class Decimated:
+    """What `decimate` returns: vertices (V',3) float32, faces (F',3) int32, the sticky status word (1,) int32 on the device and the
+    number of rounds run.  Unpacks as (vertices, faces); `check()` reads the status back and raises ValueError when the decimation
+    ended above its target."""
+
+    def __init__(self, vertices, faces, status, rounds, target):
+        self.vertices, self.faces, self.status, self.rounds, self.target = vertices, faces, status, rounds, target
+
+    def __iter__(self):
+        return iter((self.vertices, self.faces))
+
+    def check(self):
+        s = int(self.status.item())
+        if s & _lib.CAGE_STATUS_RANGE:
+            raise ValueError("decimate: an index outside its table")
+        if s & _lib.CAGE_STATUS_STUCK:
+            raise ValueError(f"decimate: stopped at {self.faces.shape[0]} faces after {self.rounds} rounds, the target was {self.target}: no edge "
+                             f"may collapse any more (boundaries are fixed, the link condition, flipped faces) or max_rounds is too small")
+        return self
+
+
+def decimate(vertices, faces=None, tris_target=None, max_rounds=None):
+    """Quadric-error-metric edge-collapse decimation down to `tris_target` triangles (the place of open3d's
+    `simplify_quadric_decimation`) -> Decimated(vertices (V',3) float32, faces (F',3) int32, status, rounds).  Rounds of independent
+    collapses by the rules of csrc/decimate_math.h: per round the `loop_plan` of the current faces, a key per edge, one `torch.sort`,
+    the ceil((F - target) / 2) cheapest edges admitted, an independent set of them collapsed, the faces compacted; two counts are
+    read back.  A closed 2-manifold stays one, with its Euler characteristic and its parts; F' is the target or one less.  Boundary
+    vertices never move.  tris_target >= F returns the input (without the vertices no face names) in zero rounds.  A round without
+    a valid edge, or `max_rounds` (default CAGE_MAX_ITERATIONS) reached, sets the STUCK bit: the mesh as it stands is returned and
+    `.check()` raises.  A mesh with an edge in three faces raises `LoopPlan.check()`'s ValueError."""
+    what = "decimate"
+    if tris_target is None:
+        raise ValueError(f"{what}: tris_target is required")
+    target = _count(what, "tris_target", tris_target, 1, 2 ** 31 - 1)
+    max_rounds = _count(what, "max_rounds", _lib.CAGE_MAX_ITERATIONS if max_rounds is None else max_rounds, 1, _lib.CAGE_MAX_ITERATIONS)
+    v, f = _checked_mesh(what, vertices, faces)
+    require_cuda(v, f)
+    dev, V = v.device, v.shape[0]
+    L, s = _lib.lib(), stream_handle()
+    x = v.clone()                                            # overwritten by the collapses
+    quadrics = torch.empty((V, 10), dtype=torch.float64, device=dev)
+    owner = torch.empty(V, dtype=torch.int64, device=dev)
+    remap = torch.empty(V, dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = ctypes.c_int64()
+    check(L.d3ga_decimate_scratch_bytes(f.shape[0], ctypes.byref(nbytes)), "d3ga_decimate_scratch_bytes")
+    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    d = _lib.DecimateDesc(x=x.data_ptr(), quadrics=quadrics.data_ptr(), owner=owner.data_ptr(), remap=remap.data_ptr(), scratch=scratch.data_ptr(),
+                          scratch_bytes=nbytes.value, counts=counts.data_ptr(), status=status.data_ptr())
+    rounds = 0
+    with torch.no_grad():
+        while True:
+            F = f.shape[0]
+            need = (F - target + 1) // 2
+            if need <= 0:
+                break
+            if rounds >= max_rounds:
+                status |= _lib.CAGE_STATUS_STUCK
+                break
+            plan = _plan_for(what, None, f, V)
+            offsets, idx = _vertex_faces(plan)
+            st = plan.struct()
+            keys = torch.empty(plan.E, dtype=torch.int64, device=dev)
+            placement = torch.empty((plan.E, 3), dtype=torch.float64, device=dev)
+            f_next = torch.empty_like(f)
+            d.faces, d.csr_offsets, d.csr_faces, d.keys, d.placement, d.faces_out = (t.data_ptr() for t in (f, offsets, idx, keys, placement, f_next))
+            if rounds == 0:
+                check(L.d3ga_decimate_quadrics(ctypes.byref(st), ctypes.byref(d), s), "d3ga_decimate_quadrics")
+            check(L.d3ga_decimate_candidates(ctypes.byref(st), ctypes.byref(d), s), "d3ga_decimate_candidates")
+            sorted_keys = torch.sort(keys).values             # the keys are distinct: every one carries its edge
+            d.sorted_keys, d.n_admit = sorted_keys.data_ptr(), min(need, plan.E)
+            check(L.d3ga_decimate_collapse(ctypes.byref(st), ctypes.byref(d), s), "d3ga_decimate_collapse")
+            check(L.d3ga_decimate_faces(ctypes.byref(st), ctypes.byref(d), s), "d3ga_decimate_faces")
+            rounds += 1
+            kept, valid = (int(c) for c in counts.cpu().tolist())           # the read-back
+            if valid == 0:
+                status |= _lib.CAGE_STATUS_STUCK
+                break
+            f = f_next[:kept]
+        used = torch.zeros(V, dtype=torch.bool, device=dev)
+        used[f.reshape(-1).long()] = True
+        renumber = torch.cumsum(used, 0) - 1
+        out_v, out_f = x[used].to(torch.float32).contiguous(), renumber[f.long()].to(torch.int32).contiguous()
+    return Decimated(out_v, out_f, status, rounds, target)
+
+
+def _decimation(what, decimation, tris_target):
+    """-> whether to decimate; keeps the refusal of a positive target unless quadric decimation is asked for"""
+    if decimation is not None and decimation != "quadric":
+        raise ValueError(f"{what}: decimation must be None or 'quadric', got {decimation!r}")
+    if tris_target > 0 and decimation is None:
         raise NotImplementedError(_DECIMATION)
+    return tris_target > 0
+
+
+def simplify(vertices, faces=None, tris_target=0, decimation=None):
+    """cager/ops.py::simplify -> (vertices, faces): the Taubin filter, with decimation="quadric" and tris_target > 0 `decimate` down to
+    tris_target, then winding and `keep_components(min_faces=70)`.  tris_target > 0 with decimation=None raises NotImplementedError."""
+    tris_target = _count("simplify", "tris_target", tris_target, 0, 2 ** 31 - 1)
+    reduce = _decimation("simplify", decimation, tris_target)
     vertices, faces = _split("simplify", vertices, faces)
     v = smooth_taubin(vertices, faces, iterations=10).check().vertices
+    if reduce:
+        v, faces = decimate(v, faces, tris_target).check()
     return keep_components(v, faces, min_faces=70)
 
 
-def cage_processor(vertices, faces=None, cage_tris_target=0, radius=60, inflate=0.01):
-    """cager/ops.py::cage_processor -> (vertices (1,V,3) float32, faces (1,F,3) int64), as the reference returns them."""
-    if _count("cage_processor", "cage_tris_target", cage_tris_target, 0, 2 ** 31 - 1) > 0:
-        raise NotImplementedError(_DECIMATION)
+def cage_processor(vertices, faces=None, cage_tris_target=0, radius=60, inflate=0.01, decimation=None):
+    """cager/ops.py::cage_processor -> (vertices (1,V,3) float32, faces (1,F,3) int64), as the reference returns them.
+    cage_tris_target > 0 needs decimation="quadric" (`simplify`)."""
+    target = _count("cage_processor", "cage_tris_target", cage_tris_target, 0, 2 ** 31 - 1)
+    _decimation("cage_processor", decimation, target)
     v, f = create_cage(vertices, faces, radius, inflate)
     if f.shape[0] == 0:
         raise ValueError("cage_processor: the voxelisation is empty: the mesh lies outside the grid")
     v, f = smooth_cage(v, f)
-    v, f = simplify(v, f, 0)
+    v, f = simplify(v, f, target, decimation)
     return v.float()[None], f.long()[None]

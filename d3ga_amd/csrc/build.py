@@ -4,9 +4,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["deform.hip", "raster_pre.hip", "raster_bin.hip", "raster_composite.hip", "raster_composite_scan.hip", "raster_api.hip", "bary.hip", "loss.hip", "image_tail.hip", "calib.hip", "frame_prep.hip", "eval.hip", "mesh_raster.hip", "point_raster.hip", "optim.hip", "mlp.hip", "encoding.hip", "body_model.hip", "skeleton.hip", "perceptual.hip", "lpips.hip", "knn.hip", "bary_interp.hip", "frame_state.hip", "objective.hip", "pose_prior.hip", "frame_grid.hip", "png.hip", "sample_prep.hip", "mesh_labels.hip", "gauss_init.hip", "template_bind.hip", "cage_author.hip"]
+SOURCES = ["deform.hip", "raster_pre.hip", "raster_bin.hip", "raster_composite.hip", "raster_composite_scan.hip", "raster_api.hip", "bary.hip", "loss.hip", "image_tail.hip", "calib.hip", "frame_prep.hip", "eval.hip", "mesh_raster.hip", "point_raster.hip", "optim.hip", "mlp.hip", "encoding.hip", "body_model.hip", "skeleton.hip", "perceptual.hip", "lpips.hip", "knn.hip", "bary_interp.hip", "frame_state.hip", "objective.hip", "pose_prior.hip", "frame_grid.hip", "png.hip", "sample_prep.hip", "mesh_labels.hip", "gauss_init.hip", "template_bind.hip", "cage_author.hip", "decimate.hip"]
 LINK_MAP = os.path.join(HERE, "d3ga.map")
-HEADERS = ["d3ga_math.h", "d3ga_internal.h", "wave_prims.h", "raster_pre_body.h", "deform_tail.h", "composite_common.h", "body_model_math.h", "skeleton_math.h", "frame_prep_math.h", "eval_math.h", "mesh_raster_math.h", "point_raster_math.h", "perceptual_math.h", "lpips_math.h", "knn_math.h", "objective_math.h", "pose_prior_math.h", "frame_grid_math.h", "frame_grid_font.h", "bary_math.h", "png_math.h", "sample_prep_math.h", "mesh_labels_math.h", "gauss_init_math.h", "template_bind_math.h", "cage_author_math.h", os.path.join("..", "..", "include", "d3ga.h")]
+HEADERS = ["d3ga_math.h", "d3ga_internal.h", "wave_prims.h", "raster_pre_body.h", "deform_tail.h", "composite_common.h", "body_model_math.h", "skeleton_math.h", "frame_prep_math.h", "eval_math.h", "mesh_raster_math.h", "point_raster_math.h", "perceptual_math.h", "lpips_math.h", "knn_math.h", "objective_math.h", "pose_prior_math.h", "frame_grid_math.h", "frame_grid_font.h", "bary_math.h", "png_math.h", "sample_prep_math.h", "mesh_labels_math.h", "gauss_init_math.h", "template_bind_math.h", "cage_author_math.h", "decimate_math.h", os.path.join("..", "..", "include", "d3ga.h")]
 ABL = os.environ.get("D3GA_SCAN_ABL")       # timing ablation of the compositing backward (wrong results): own objects + .so
 VARIANT = os.environ.get("D3GA_VARIANT")    # A/B build of compile-time knobs: "tag:-DNAME=value,-DOTHER=value" -> tools/_build/libd3ga_hip_<tag>.so (correct results)
 DIAG = os.environ.get("D3GA_DIAG") or (("abl" + ABL) if ABL else None) or (("var" + VARIANT.split(":")[0]) if VARIANT else None)          # diagnostic build: its own objects and its own .so (D3GA_LIB_PATH selects it)
@@ -43,6 +43,7 @@ EXTRA["bary.hip"] = ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=
 EXTRA["gauss_init.hip"] = ["-ffp-contract=off"]                        # the g++ build of gauss_init_math.h is the yardstick: float64, same bits
 EXTRA["template_bind.hip"] = ["-ffp-contract=off"]                     # the g++ build of template_bind_math.h is the yardstick: float64, same bits
 EXTRA["cage_author.hip"] = ["-ffp-contract=off"]                       # the g++ build of cage_author_math.h is the yardstick: float64, same bits
+EXTRA["decimate.hip"] = ["-ffp-contract=off"]                          # the g++ build of decimate_math.h is the yardstick: a last bit of a cost changes the winner
 if os.environ.get("D3GA_CHAIN_WAVES"):                      # A/B: wavefronts per workgroup of the fused field-network kernel
     FLAGS.append("-DD3GA_CHAIN_WAVES=" + os.environ["D3GA_CHAIN_WAVES"])
 if os.environ.get("D3GA_CHAIN_CS"):                           # A/B: k-steps per weight chunk of the fused field-network kernel

@@ -1662,6 +1662,52 @@ int d3ga_cage_iso_emit(const d3ga_voxel_grid *grid, const d3ga_cage_iso_desc *ou
 int d3ga_cage_smooth(const d3ga_loop_plan *plan, const d3ga_cage_smooth_desc *smooth, d3ga_stream_t stream);
 int d3ga_cage_components(const d3ga_loop_plan *plan, int32_t stage, int32_t *label, int32_t *changed, d3ga_stream_t stream);
 
+/* ---- Quadric edge-collapse decimation of the cage surface (csrc/decimate.hip, csrc/decimate_math.h) -----------------
+ * What cager/ops.py::simplify :121-137 asks of open3d's simplify_quadric_decimation, as ROUNDS OF INDEPENDENT COLLAPSES; parity with
+ * open3d's serial queue is UNPINNED -- the rules are the header's.  float64 arithmetic in a fixed order, integer atomics only; the
+ * result depends on the mesh and the target alone.  No kernel waits on another workgroup and no entry point synchronises with the
+ * host: per round the caller builds the d3ga_loop_plan of the current faces and their vertex -> face lists, calls the stages in
+ * order, sorts `keys` (ascending, signed 64-bit) between candidates and collapse, and reads `counts` back after faces.  Additive to
+ * ABI 112.
+ *   d3ga_decimate_quadrics (once): quadrics[v] = the sum of area * p p^T over the faces of v in ascending face index, p the unit
+ *     plane of the face, as 10 float64 (xx xy xz xw yy yz yw zz zw ww).  A face without area adds nothing.
+ *   d3ga_decimate_candidates: owner[v] = all ones, remap[v] = v, counts[1] = 0; then for every edge e = (u, w), u < w, of the plan:
+ *     keys[e] = (float32 bits of the cost) << 32 | e and placement[e] = the point both ends move to, or keys[e] = D3GA_LOOP_BAD_KEY
+ *     for an edge that must not collapse (a boundary end, the link condition, a flipped face, a cost that is not finite).
+ *     counts[1] += the number of valid edges.
+ *   d3ga_decimate_collapse: the first n_admit entries of sorted_keys that are valid are admitted.  Launch 1: each does a 64-bit
+ *     integer atomicMin of its key into owner[u] and owner[w].  Launch 2: an admitted edge with owner[t] >= key for every t in the
+ *     closed neighbourhoods of u and w is selected and applied: x[u] = placement[e], quadrics[u] += quadrics[w], remap[w] = u.
+ *   d3ga_decimate_faces: every face is relabelled through remap; the faces that still name three vertices are written to faces_out
+ *     in order; counts[0] = their number.  scratch: d3ga_decimate_scratch_bytes(F) bytes, 256-byte aligned, no initialisation needed.
+ *   A table entry outside its table sets D3GA_CAGE_STATUS_RANGE in *status (sticky) and is left out.  D3GA_CAGE_STATUS_STUCK is set
+ *   by the caller when a round finds no valid edge or the round limit is reached.
+ *   Status, nothing launched: sizes as d3ga_cage_smooth; n_admit outside 1 .. E D3GA_E_SIZE; a required pointer NULL D3GA_E_NULL; a
+ *   pointer not aligned to its element (scratch: 256 bytes) or faces_out == faces D3GA_E_CONFIG; scratch too small D3GA_E_CAPACITY. */
+#define D3GA_CAGE_STATUS_STUCK 8
+typedef struct d3ga_decimate_desc {
+    int32_t n_admit, reserved;       /* collapse: how many of the cheapest edges are admitted */
+    double *x;                       /* (V,3) positions */
+    double *quadrics;                /* (V,10) */
+    const int32_t *faces;            /* (F,3) the faces the plan was built from */
+    const int32_t *csr_offsets, *csr_faces;      /* vertex -> faces, ascending: (V+1), (3 F) */
+    int64_t *keys;                   /* (E) candidates writes them */
+    double *placement;               /* (E,3) */
+    const int64_t *sorted_keys;      /* (E) collapse reads them */
+    uint64_t *owner;                 /* (V) */
+    int32_t *remap;                  /* (V) */
+    int32_t *faces_out;              /* (F,3) */
+    void *scratch;
+    int64_t scratch_bytes;
+    int64_t *counts;                 /* [0] faces after the round, [1] valid edges of the round */
+    uint32_t *status;
+} d3ga_decimate_desc;
+int d3ga_decimate_scratch_bytes(int32_t F, int64_t *bytes);
+int d3ga_decimate_quadrics(const d3ga_loop_plan *plan, const d3ga_decimate_desc *desc, d3ga_stream_t stream);
+int d3ga_decimate_candidates(const d3ga_loop_plan *plan, const d3ga_decimate_desc *desc, d3ga_stream_t stream);
+int d3ga_decimate_collapse(const d3ga_loop_plan *plan, const d3ga_decimate_desc *desc, d3ga_stream_t stream);
+int d3ga_decimate_faces(const d3ga_loop_plan *plan, const d3ga_decimate_desc *desc, d3ga_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
