@@ -40,9 +40,13 @@ D3GA_HD void sh_view_basis(const d3ga_raster_params &prm, const float *means3D, 
 // acc[c] += sum_k B[k] * coeff[k][c]  AND  J[3 dir + c] = sum_k dY_k/d(dir)(x, y, z) * coeff[k][c] -- the derivative of the
 // (unclamped, un-offset) SH colour w.r.t. the unit direction -- in ONE walk over the row: every coefficient is read once and
 // the three derivative values of a basis function are formed where they are used (no 3 x 16 gradient arrays: the forward's
-// staging kernel has no registers for them).  Same polynomials as sh_basis_grad.
+// staging kernel has no registers for them).  Same polynomials as sh_basis_grad.  Without contraction, the sums by explicit fmaf:
+// the function is inlined into the forward's full-wavefront path and into its generic slab path, and the compiler contracted the
+// two copies differently -- J, and with it dL/dmeans3D of the same Gaussian, then depended in the last bit on whether its row
+// fell into a full wavefront (tests/test_gpu_preprocess_alone.py: layout).
 struct ShColJ { float a0, a1, a2, j0, j1, j2, j3, j4, j5, j6, j7, j8; };      // by value: as arrays behind pointers these landed in scratch memory
 D3GA_HD ShColJ sh_accumulate_jacobian(const float B[16], float x, float y, float z, const float *row, int nb, ShColJ o) {
+    D3GA_NO_CONTRACT
     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
     o.j0 = o.j1 = o.j2 = o.j3 = o.j4 = o.j5 = o.j6 = o.j7 = o.j8 = 0.f;
 #define D3GA_SHJ(K, GX, GY, GZ)                                                                             \
@@ -50,9 +54,9 @@ D3GA_HD ShColJ sh_accumulate_jacobian(const float B[16], float x, float y, float
         const float r0 = row[3 * K], r1 = row[3 * K + 1], r2 = row[3 * K + 2];                              \
         o.a0 = fmaf(B[K], r0, o.a0); o.a1 = fmaf(B[K], r1, o.a1); o.a2 = fmaf(B[K], r2, o.a2);   /* as sh_accumulate, bit for bit */                                            \
         const float gx_ = (GX), gy_ = (GY), gz_ = (GZ);                                                     \
-        o.j0 += gx_ * r0; o.j1 += gx_ * r1; o.j2 += gx_ * r2;                                               \
-        o.j3 += gy_ * r0; o.j4 += gy_ * r1; o.j5 += gy_ * r2;                                               \
-        o.j6 += gz_ * r0; o.j7 += gz_ * r1; o.j8 += gz_ * r2;                                               \
+        o.j0 = fmaf(gx_, r0, o.j0); o.j1 = fmaf(gx_, r1, o.j1); o.j2 = fmaf(gx_, r2, o.j2);                 \
+        o.j3 = fmaf(gy_, r0, o.j3); o.j4 = fmaf(gy_, r1, o.j4); o.j5 = fmaf(gy_, r2, o.j5);                 \
+        o.j6 = fmaf(gz_, r0, o.j6); o.j7 = fmaf(gz_, r1, o.j7); o.j8 = fmaf(gz_, r2, o.j8);                 \
     }
     if (0 < nb) { o.a0 = fmaf(B[0], row[0], o.a0); o.a1 = fmaf(B[0], row[1], o.a1); o.a2 = fmaf(B[0], row[2], o.a2); }
     D3GA_SHJ(1, 0.f, -kC1, 0.f)
